@@ -15,6 +15,11 @@ unavailable, the RCCL all-reduce - then every rank applies the identical update.
 `python bench.py --gpus N` with N > 1 and no torchrun environment launches its own N ranks (torch.distributed.run on
 127.0.0.1); under torchrun (RANK / WORLD_SIZE set, the driver's form) it is one of the ranks.  Both forms print ONE JSON line.
 
+`--dump-outputs DIR` writes what the last of the K timed steps left to its caller - parameters, optimizer state, aux (DLA's
+propensity parameters / the pairwise algorithms' t+ | t-), the step's scores and step scalars - as DIR/<name>.npy (float32, rank 0).
+The timed region starts from the initial state and the batches are seeded, so the same arguments give the same inputs on every
+run and two builds can be compared output for output.
+
 `value` is the API-faithful figure of SURVEY 8(d): every step is followed by the read of its loss on the host (the
 reference's `loss.item()`, here a spin on the update kernel's report in host-mapped memory); the same loop without the
 per-step read is `queries_per_sec_no_host_sync`.
@@ -715,6 +720,20 @@ def eval_leg(cfg, device, lib, params0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32); returns {name: shape} for the result line."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` outside torchrun: launch N ranks of this script (one per GPU) and pass rank 0's line on."""
     import socket
@@ -748,6 +767,8 @@ def main():
     ap.add_argument("--spinup-ms", type=float, default=None,
                     help="untimed steps for this many ms in front of the W warm-up steps (shader clocks settle; default 300 for config 2)")
     ap.add_argument("--timer-stride", type=int, default=None, help="the dominant kernel is timed on every stride-th step of the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (parameters, optimizer state, aux, scores, step scalars) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)  # does not return
@@ -788,6 +809,15 @@ def main():
     npool = len(pool)
     eng = W.eng
     engs = {"main": eng}
+    # every attempt at the timed region starts from these initial parameters / optimizer state / aux: the spin-up runs for a time,
+    # not a number of steps, so only then does what the K timed steps compute depend on the arguments alone (--dump-outputs)
+    initial = [(t, t.clone()) for t in (params, state, aux) if t is not None]
+
+    def restore_initial_state():
+        for t, t0 in initial:
+            t.copy_(t0)
+        if cfg["model"] == "dnn":
+            hip_ops.weight_copy(shape).get(params)  # rebuild the split-half weight copies now, not inside the first timed step
 
     def step(i, e=None):
         f, nd, ids, y, _ = pool[i % npool]
@@ -932,6 +962,7 @@ def main():
         del engs["selftest"]
     # ---- the timed region: EXACTLY K steps, each followed by the host's read of its loss (the reference's loss.item()) ----
     def timed_region():
+        restore_initial_state()
         barrier()
         ta = time.perf_counter()
         for i in range(args.steps):
@@ -963,6 +994,12 @@ def main():
             step(i)
         _lib.check(lib.ultr_prof_set_stride(stride), "ultr_prof_set_stride")
         _lib.check(lib.ultr_prof_enable(1 << dom, 4 * (args.steps // stride + 2)), "ultr_prof_enable")
+    # what a caller of the timed path holds after its last step, taken before anything else runs on this state
+    outputs = None
+    if args.dump_outputs is not None:
+        outputs = {"params": params, "optimizer_state": state, "aux": aux, "scores": eng.scores,
+                   "step_scalars": eng.scalars[:10]}  # loss, grad norm, clip coefficient, ... (include/ultr_hip.h: scalars_out)
+        outputs = {k: v.detach().float().cpu().numpy() for k, v in outputs.items() if v is not None}
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=device)
     if pg is not None:
         torch.distributed.all_reduce(elapsed, op=torch.distributed.ReduceOp.MAX)
@@ -1294,6 +1331,8 @@ def main():
             out["plugin_device_feed_queries_per_sec"] = plugin[1]  # IPWrank.train(DeviceClickFeed batch)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, pool, params0)
+        if outputs is not None:
+            out["dump_outputs"] = write_outputs(args.dump_outputs, outputs)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(out), flush=True)

@@ -31,10 +31,11 @@ def perturbed_params(O, F, hidden, rng):
 @pytest.mark.parametrize("which", ["both", "fwd", "bwd"])
 def test_big_path_vs_oracle(F, hidden, B, L, act, which, monkeypatch):
     from oracle import ultr_oracle as O
-    if max([F] + hidden) > 512 + 256 and which != "both":
-        pytest.skip("the row-tile kernels do not hold 1024-wide rows in LDS: only the per-layer path runs this shape")
-    monkeypatch.setenv("ULTR_BIG_FWD", "2" if which in ("both", "fwd") else "0")
-    monkeypatch.setenv("ULTR_BIG_BWD", "2" if which in ("both", "bwd") else "0")
+    # the stage not forced onto the per-layer path runs on the row-tile kernels (knob 0) - except where they cannot hold the
+    # rows in LDS (1024 wide): there it takes its default plan (knob 1), which is the per-layer path for such rows as well
+    other = "1" if max([F] + hidden) > 512 + 256 else "0"
+    monkeypatch.setenv("ULTR_BIG_FWD", "2" if which in ("both", "fwd") else other)
+    monkeypatch.setenv("ULTR_BIG_BWD", "2" if which in ("both", "bwd") else other)
     feats, ids, labels = synth(F, B, L, 5)
     rng = np.random.RandomState(9)
     params = perturbed_params(O, F, hidden, rng)
