@@ -200,6 +200,16 @@ int ultr_regem_loss(const float* scores, const float* labels, const float* prope
                     uint64_t seed, uint64_t step, int32_t batch, int32_t list_size, float* dscores,
                     float* pseudo_labels_out, void* loss_ws, void* stream);
 
+/* ---- PRSrank: propensity-ratio-scored LambdaRank -------------------------------------
+ * Replaces PRSrank.train's propensity + loss section (prs_rank.py:94-176) + dcg/compute_delta_ndcg
+ * (prs_rank.py:207-251): ipw[l] = ipw_table[min(l, n_ipw-1)] for EVERY position (clicked or not), pw = 1/ipw
+ * (0 where ipw == 0), per-list descending sort, prs_ij = ipw_i * pw_j on the pairs i < j of the sorted order,
+ * delta-NDCG-weighted F.binary_cross_entropy (logs clamped at -100) of 1 / (exp(-sigma (s_i - s_j)) + 1),
+ * batch-global natural-log IDCG (kept separate as D).  The gradient is autograd's through that composition,
+ * including its explosion where x rounds to 1 and its NaN where exp overflows in the lower triangle. */
+int ultr_prs_loss(const float* scores, const float* labels, const float* ipw_table, int32_t n_ipw, float sigma,
+                  int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
+
 /* ---- next row 8f.1: the SetRank ranking model --------------------------------------------
  * Replaces SetRank.build / Encoder.forward (ranking_model/SetRank.py:143-156, 229-255) and its autograd
  * backward: input LayerNorm (eps 1e-6) -> FFN(F -> dff -> d_model) -> num_layers x [multi-head self-attention
@@ -240,7 +250,8 @@ int ultr_setrank_backward(const ultr_setrank_desc* c, const float* params, int32
  * (base_algorithm.py:223-226; ipw_rank.py:96), DLA.separate_gradient_update
  * (dla.py:141-177: per-model clip, fresh = stateless Adagrad), and the t_plus/t_minus EM
  * updates (pairwise_debias.py:159-163, lambda_rank.py:136-142). */
-enum ultr_algo { ULTR_ALGO_SOFTMAX = 0, ULTR_ALGO_DLA = 1, ULTR_ALGO_PAIRDEBIAS = 2, ULTR_ALGO_LAMBDARANK = 3, ULTR_ALGO_REGEM = 4 };
+enum ultr_algo { ULTR_ALGO_SOFTMAX = 0, ULTR_ALGO_DLA = 1, ULTR_ALGO_PAIRDEBIAS = 2, ULTR_ALGO_LAMBDARANK = 3, ULTR_ALGO_REGEM = 4,
+                 ULTR_ALGO_PRS = 5 };
 enum ultr_opt { ULTR_OPT_ADAGRAD = 0, ULTR_OPT_SGD = 1 };
 
 typedef struct ultr_update_desc {
@@ -285,7 +296,7 @@ typedef struct ultr_update_desc {
 
 /* params/state [P] updated in place; grads = the buffer ultr_dnn_backward filled (possibly
  * all-reduced).  aux = prop_params[L+1] (DLA) or [t_plus(L) | t_minus(L)] (PairDebias /
- * LambdaRank), updated in place; NULL for SOFTMAX.  d + wt (both may be NULL): keep the k-major weight copy
+ * LambdaRank), updated in place; NULL for SOFTMAX and PRS.  d + wt (both may be NULL): keep the k-major weight copy
  * in sync with the updated parameters.  bwd_ws = the workspace ultr_dnn_backward (or
  * ultr_grad_sumsq) left the sum-of-squares partials in.
  * scalars_out[16]: [0] loss [1] ranker grad norm (pre-clip) [2] clip coef [3] D
@@ -298,7 +309,8 @@ int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* 
  * ultr_dnn_forward -> ultr_<loss by upd->algo> -> ultr_dnn_backward -> ultr_apply_update, enqueued by ONE host
  * call (what `model.train(input_feed)` does between marshalling the feed and `loss.item()`).  A data-parallel
  * caller sets skip_update, all-reduces `grads`, then calls ultr_grad_sumsq + ultr_apply_update itself.
- * aux: prop_params (DLA) or [t_plus | t_minus] (PairDebias / LambdaRank) or propensity [L] (RegressionEM) or NULL. */
+ * aux: prop_params (DLA) or [t_plus | t_minus] (PairDebias / LambdaRank) or propensity [L] (RegressionEM) or NULL.
+ * ipw_table / n_ipw: the IPW_list of IPW (SOFTMAX) and PRS.  sigma: LambdaRank and PRS. */
 typedef struct ultr_step_args {
   const ultr_dnn_desc* desc;
   const ultr_update_desc* upd;
@@ -324,7 +336,7 @@ typedef struct ultr_step_args {
   int32_t list_size;
   int32_t batch_total; /* PairDebias: global batch (0 = batch) */
   int32_t skip_update;
-  float sigma;         /* LambdaRank */
+  float sigma;         /* LambdaRank / PRS */
   const float* uniforms; /* RegressionEM: [B, L] uniforms of the Bernoulli draw, or NULL = Philox(rng_seed, rng_step) */
   uint64_t rng_seed;
   uint64_t rng_step;

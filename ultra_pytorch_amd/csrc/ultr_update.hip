@@ -144,6 +144,10 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
       gs = 1.0f / D;
       loss = loss_sum / D;
       break;
+    case ULTR_ALGO_PRS:  // delta-NDCG weights are normalised by the batch-global IDCG (prs_rank.py:240)
+      gs = 1.0f / D;
+      loss = loss_sum / D;
+      break;
   }
   float norm = fabsf(gs) * sqrtf(ss);
   // l2_loss > 0 (ipw_rank.py:154-157 and siblings): g += lam * p, loss += l2_loss * sum p^2 / 2.  Every algorithm but DLA
@@ -441,12 +445,13 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
   if (wt != nullptr) {
     if (!ultr_make_dnn_plan(d, 0, &dp) || dp.P != u->n_params) return ULTR_E_BADARG;
   }
-  if (u->algo < 0 || u->algo > ULTR_ALGO_REGEM || (u->optimizer != ULTR_OPT_ADAGRAD && u->optimizer != ULTR_OPT_SGD))
+  if (u->algo < 0 || u->algo > ULTR_ALGO_PRS || (u->optimizer != ULTR_OPT_ADAGRAD && u->optimizer != ULTR_OPT_SGD))
     return ULTR_E_BADARG;
-  if (u->algo != ULTR_ALGO_SOFTMAX && !aux) return ULTR_E_BADARG;
+  if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && !aux) return ULTR_E_BADARG;
   if (u->optimizer == ULTR_OPT_ADAGRAD && u->algo != ULTR_ALGO_DLA && !state) return ULTR_E_BADARG;
-  if (u->l2_loss < 0.f || (u->l2_loss > 0.f && !scalars_out) || (u->l2_loss > 0.f && u->algo == ULTR_ALGO_LAMBDARANK))
-    return ULTR_E_BADARG;  // LambdaRank has no l2_loss hyper-parameter (lambda_rank.py:42-49)
+  if (u->l2_loss < 0.f || (u->l2_loss > 0.f && !scalars_out) ||
+      (u->l2_loss > 0.f && (u->algo == ULTR_ALGO_LAMBDARANK || u->algo == ULTR_ALGO_PRS)))
+    return ULTR_E_BADARG;  // LambdaRank and PRSrank have no l2_loss hyper-parameter (lambda_rank.py:42-49, prs_rank.py:43-50)
   const int tail = (int)ultr_tail_len(u->list_size);
   const int nsq = (int)ultr_red_blocks(u->n_params, tail);
   const float* l2_sums = nullptr;

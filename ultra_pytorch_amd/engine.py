@@ -21,7 +21,7 @@ import torch
 from . import _lib, hip_ops
 
 ALGOS = {"softmax": _lib.ALGO_SOFTMAX, "dla": _lib.ALGO_DLA, "pairdebias": _lib.ALGO_PAIRDEBIAS,
-         "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM}
+         "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM, "prs": _lib.ALGO_PRS}
 
 
 def _f32(n, device, zero=False):
@@ -129,6 +129,10 @@ class StepEngine:
             hip_ops.pairdebias_loss(self.scores, labels, aux[:L], aux[L:], B, L, self.batch_total, self.dscores, self.loss_ws)
         elif self.algo == "lambdarank":
             hip_ops.lambdarank_loss(self.scores, labels, aux[:L], aux[L:], self.sigma, B, L, self.dscores, self.loss_ws)
+        elif self.algo == "prs":
+            if ipw_table is None:
+                raise ValueError("PRSrank's loss needs the IPW table (ipw_table=)")
+            hip_ops.prs_loss(self.scores, labels, ipw_table, self.sigma, B, L, self.dscores, self.loss_ws)
         elif self.algo == "regem":
             hip_ops.regem_loss(self.scores, labels, aux, B, L, self.dscores, self.loss_ws, uniforms=uniforms,
                                seed=self.rng_seed, step=self.rng_step)

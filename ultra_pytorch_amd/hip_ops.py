@@ -304,6 +304,12 @@ def lambdarank_loss(scores, labels, t_plus, t_minus, sigma, B, L, dscores, loss_
                                            _p(dscores), _p(loss_ws), _stream()), "ultr_lambdarank_loss")
 
 
+def prs_loss(scores, labels, ipw_table, sigma, B, L, dscores, loss_ws):
+    """PRSrank: propensity-ratio-scored, delta-NDCG-weighted pairwise BCE on the sorted list; ipw_table = the IPW_list (fp32)."""
+    check(_lib.load().ultr_prs_loss(_p(scores), _p(labels), _p(ipw_table), int(ipw_table.numel()), float(sigma), int(B), int(L),
+                                    _p(dscores), _p(loss_ws), _stream()), "ultr_prs_loss")
+
+
 def regem_loss(scores, labels, propensity, B, L, dscores, loss_ws, uniforms=None, seed=0, step=0, pseudo_out=None):
     """RegressionEM estimation + BCE loss; uniforms [B, L] teacher-forces the Bernoulli draw."""
     check(_lib.load().ultr_regem_loss(_p(scores), _p(labels), _p(propensity), _p(uniforms), int(seed), int(step), int(B),

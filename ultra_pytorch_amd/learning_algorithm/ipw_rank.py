@@ -11,6 +11,15 @@ from ..utils import HParams
 from .base_algorithm import BaseAlgorithm
 
 
+def load_ipw_list(path):
+    """BasicPropensityEstimator.loadEstimatorFromFile: the JSON's "IPW_list" (propensity_estimator.py:44-56)."""
+    if not os.path.exists(path):  # the reference resolves its default relative to the repo root; we ship the same table
+        alt = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", os.path.basename(path))
+        path = alt if os.path.exists(alt) else path
+    with open(path) as fin:
+        return [float(x) for x in json.load(fin)["IPW_list"]]
+
+
 class _LazyColumn(collections.abc.Sequence):
     """`propensity_weights{l}` as the reference leaves it in the feed (a Python list of B floats, ipw_rank.py:118-128),
     materialised on first use: nothing in main.py reads these entries, and ten `.tolist()` calls per step were a third of the
@@ -63,13 +72,7 @@ class IPWrank(BaseAlgorithm):
         self.hparams.parse(exp_settings["learning_algorithm_hparams"])
         self._check_hparams()
         self._setup(data_set, exp_settings)
-        # BasicPropensityEstimator.loadEstimatorFromFile: the JSON's "IPW_list" (propensity_estimator.py:44-56)
-        path = self.hparams.propensity_estimator_json
-        if not os.path.exists(path):  # the reference resolves its default relative to the repo root; we ship the same table
-            alt = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", os.path.basename(path))
-            path = alt if os.path.exists(alt) else path
-        with open(path) as fin:
-            self.IPW_list = [float(x) for x in json.load(fin)["IPW_list"]]
+        self.IPW_list = load_ipw_list(self.hparams.propensity_estimator_json)
         self.ipw_table = torch.tensor(self.IPW_list, dtype=torch.float32, device=self.cuda)
         self._pw_table, self._lazy_pw = None, None
         self._pw_names = ["propensity_weights{0}".format(l) for l in range(self.max_candidate_num)]
