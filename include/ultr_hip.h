@@ -352,7 +352,8 @@ int ultr_train_step(const ultr_step_args* a, void* stream);
  * Replaces remove_padding_for_metric_eval (base_algorithm.py:88-116) and
  * normalized_discounted_cumulative_gain (metrics.py:191-265, 456-495):  pads
  * (docid == n_docs) -> -100000, labels < 0 -> label 0 / score rowmin-1e-6, stable descending
- * sort, gains 2^l - 1, log2 discounts, topn clipped to L, mean over the batch.
+ * sort, gains 2^l - 1, log2 discounts, topn clipped to L, mean over the batch.  As in torch: a NaN
+ * score sorts above every number, and a NaN in a list makes its rowmin NaN.
  * ndcg_out[n_topn]; order_out (may be NULL) [B, L] int32 = the descending permutation;
  * masked_out (may be NULL) [B, L] = the masked scores.  ndcg_ws: batch*n_topn floats. */
 int ultr_ndcg(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,

@@ -3,7 +3,8 @@
 // Replaces BaseAlgorithm.remove_padding_for_metric_eval (reference base_algorithm.py:88-116) and
 // ultra.utils.metrics.normalized_discounted_cumulative_gain with weights=None (metrics.py:191-265, 456-495).
 // One wavefront per list; the descending sort is rank-by-counting from LDS (stable: ties keep index order,
-// which is what torch's CPU sort yields for the all-equal padding scores).
+// which is what torch's CPU sort yields for the all-equal padding scores).  A NaN score ranks above every number, as in torch's
+// descending sort, and a NaN in a list becomes the row minimum that its invalid labels take, as torch.min does.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -14,6 +15,13 @@
 
 #define NDCG_LPW 4
 #define NDCG_MAX_TOPN 16
+
+// the descending order of scores as an unsigned key: -0 and +0 equal, every NaN equal and above +inf
+__device__ __forceinline__ unsigned score_key(float s) {
+  if (s != s) return 0xFFFFFFFFu;
+  const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
 
 struct TopN {
   int n;
@@ -37,7 +45,7 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
                                                                  int32_t* __restrict__ order_out,
                                                                  float* __restrict__ masked_out, NdcgTail tail) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sm_s = smem;                 // [LPW][L] masked + validated predictions
+  float* sm_s = smem;                 // [LPW][L] masked + validated predictions (then their order keys)
   float* sm_y = sm_s + NDCG_LPW * L;  // [LPW][L] validated labels
   float* sm_d = sm_y + NDCG_LPW * L;  // [LPW][L] discounted gains by predicted rank
   float* sm_i = sm_d + NDCG_LPW * L;  // [LPW][L] discounted gains by ideal rank
@@ -56,6 +64,7 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
   // pad mask, then metrics.py:251-264: invalid labels (< 0) -> label 0, prediction rowmin - 1e-6
   // (score, doc id and label of a position are requested together: the kernel is a chain of dependent round trips, not bytes)
   float mn = INFINITY;
+  bool nan_seen = false;
   for (int l = lane; l < L; l += 64) {
     float s = scores[(int64_t)b * L + l];
     const float y = labels[(int64_t)l * B + b];
@@ -64,23 +73,28 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
     ms[l] = s;
     my[l] = y;
     mn = fminf(mn, s);
+    nan_seen = nan_seen || s != s;
   }
   mn = -wave_max(-mn);
+  if (__ballot(nan_seen) != 0) mn = __builtin_nanf("");  // torch.min propagates a NaN (fminf drops it)
+  unsigned* mk = reinterpret_cast<unsigned*>(ms);  // the validated predictions, from here on as order keys (score_key)
   for (int l = lane; l < L; l += 64) {
     const float y = my[l];
     const bool ok = y >= 0.f;
     my[l] = ok ? y : 0.f;
-    if (!ok) ms[l] = -1e-6f + mn;
+    mk[l] = score_key(ok ? ms[l] : -1e-6f + mn);
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   for (int i = lane; i < L; i += 64) {
-    const float si = ms[i], yi = my[i];
+    const unsigned ki = mk[i];
+    const float yi = my[i];
     int rs = 0, ry = 0;
     for (int j = 0; j < L; ++j) {
-      const float sj = ms[j], yj = my[j];
-      rs += (sj > si || (sj == si && j < i)) ? 1 : 0;
+      const unsigned kj = mk[j];
+      const float yj = my[j];
+      rs += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
       ry += (yj > yi || (yj == yi && j < i)) ? 1 : 0;
     }
     const float gain = exp2f(yi) - 1.0f;  // weights = 1: gains = 2^label - 1 (metrics.py:213)
