@@ -210,6 +210,17 @@ int ultr_regem_loss(const float* scores, const float* labels, const float* prope
 int ultr_prs_loss(const float* scores, const float* labels, const float* ipw_table, int32_t n_ipw, float sigma,
                   int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
 
+/* ---- PDGD: Pairwise Differentiable Gradient Descent (online) ---------------------------
+ * Replaces PDGD.train's pair construction and loss (pdgd.py:107-205) over the list_size positions the forward scored
+ * (max_candidate_num there): e = exp(tau (s - max s)) in fp32, zeroed for PADs (docids[l,b] == n_docs) at l < cutoff
+ * only (pdgd.py:120-126); pairs (l, k) with l < cutoff valid and label_l > 0, k in 0 .. l+1, k < cutoff, k valid and
+ * label_k < label_l (pdgd.py:138-172); weight 1 / (1 + exp(min(delta, 20))) with delta the flipped list's sum of log
+ * suffix sums minus the original's (pdgd.py:128-134, 160-176), a constant; loss = sum of -w e^{s_l} / (e^{s_l} + e^{s_k}) on
+ * the raw scores (pdgd.py:193-205), its gradient autograd's through that expression (NaN where exp overflows).
+ * Plain sum (D = 1).  Deterministic (no atomics).  list_size > 256: ULTR_E_UNSUPPORTED. */
+int ultr_pdgd_loss(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, float tau,
+                   int32_t cutoff, int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
+
 /* ---- next row 8f.1: the SetRank ranking model --------------------------------------------
  * Replaces SetRank.build / Encoder.forward (ranking_model/SetRank.py:143-156, 229-255) and its autograd
  * backward: input LayerNorm (eps 1e-6) -> FFN(F -> dff -> d_model) -> num_layers x [multi-head self-attention
@@ -251,7 +262,7 @@ int ultr_setrank_backward(const ultr_setrank_desc* c, const float* params, int32
  * (dla.py:141-177: per-model clip, fresh = stateless Adagrad), and the t_plus/t_minus EM
  * updates (pairwise_debias.py:159-163, lambda_rank.py:136-142). */
 enum ultr_algo { ULTR_ALGO_SOFTMAX = 0, ULTR_ALGO_DLA = 1, ULTR_ALGO_PAIRDEBIAS = 2, ULTR_ALGO_LAMBDARANK = 3, ULTR_ALGO_REGEM = 4,
-                 ULTR_ALGO_PRS = 5 };
+                 ULTR_ALGO_PRS = 5, ULTR_ALGO_PDGD = 6 };
 enum ultr_opt { ULTR_OPT_ADAGRAD = 0, ULTR_OPT_SGD = 1 };
 
 typedef struct ultr_update_desc {
@@ -310,7 +321,9 @@ int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* 
  * call (what `model.train(input_feed)` does between marshalling the feed and `loss.item()`).  A data-parallel
  * caller sets skip_update, all-reduces `grads`, then calls ultr_grad_sumsq + ultr_apply_update itself.
  * aux: prop_params (DLA) or [t_plus | t_minus] (PairDebias / LambdaRank) or propensity [L] (RegressionEM) or NULL.
- * ipw_table / n_ipw: the IPW_list of IPW (SOFTMAX) and PRS.  sigma: LambdaRank and PRS. */
+ * ipw_table / n_ipw: the IPW_list of IPW (SOFTMAX) and PRS.  sigma: LambdaRank and PRS.
+ * PDGD (no IPW table, no sigma): sigma carries tau and n_ipw the cutoff (selection_bias_cutoff); docids / n_docs mark
+ * the PADs. */
 typedef struct ultr_step_args {
   const ultr_dnn_desc* desc;
   const ultr_update_desc* upd;
@@ -331,12 +344,12 @@ typedef struct ultr_step_args {
   float* grads;
   float* scalars;
   int64_t n_docs;
-  int32_t n_ipw;
+  int32_t n_ipw;       /* PDGD: the cutoff */
   int32_t batch;
   int32_t list_size;
   int32_t batch_total; /* PairDebias: global batch (0 = batch) */
   int32_t skip_update;
-  float sigma;         /* LambdaRank / PRS */
+  float sigma;         /* LambdaRank / PRS; PDGD: tau */
   const float* uniforms; /* RegressionEM: [B, L] uniforms of the Bernoulli draw, or NULL = Philox(rng_seed, rng_step) */
   uint64_t rng_seed;
   uint64_t rng_step;

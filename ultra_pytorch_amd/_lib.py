@@ -13,7 +13,7 @@ ULTR_MAX_HIDDEN = 7
 COMM_HANDLE_BYTES, COMM_MAX_WORLD = 64, 8
 ACT = {"elu": 0, "relu": 1, "tanh": 2, "sigmoid": 3}  # base_ranking_model.py:63-69 ("selu" raises in the reference)
 ATTN_DTYPE = {"fp32": 0, "fp16": 1}
-ALGO_SOFTMAX, ALGO_DLA, ALGO_PAIRDEBIAS, ALGO_LAMBDARANK, ALGO_REGEM, ALGO_PRS = 0, 1, 2, 3, 4, 5
+ALGO_SOFTMAX, ALGO_DLA, ALGO_PAIRDEBIAS, ALGO_LAMBDARANK, ALGO_REGEM, ALGO_PRS, ALGO_PDGD = 0, 1, 2, 3, 4, 5, 6
 OPT_ADAGRAD, OPT_SGD = 0, 1
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
@@ -84,6 +84,7 @@ SIGNATURES = {
     "ultr_pairdebias_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_lambdarank_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_prs_loss": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ultr_pdgd_loss": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_regem_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "ultr_setrank_param_count": (c_i64, [ctypes.POINTER(SetRankDesc)]),
     "ultr_setrank_saved_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),

@@ -88,7 +88,7 @@ __device__ __forceinline__ bool comm_flags_and_wait(const CommDev& c, int64_t sl
 __device__ __forceinline__ void comm_early_report(const EarlyReport& er, float loss_sum, float D, float loss2, float D2) {
   float loss = loss_sum / D;
   if (er.algo == ULTR_ALGO_DLA) loss = loss2 / D2 + er.rlw * (loss_sum / D);
-  else if (er.algo == ULTR_ALGO_PAIRDEBIAS) loss = loss_sum;
+  else if (er.algo == ULTR_ALGO_PAIRDEBIAS || er.algo == ULTR_ALGO_PDGD) loss = loss_sum;
   __hip_atomic_store(er.host, loss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __hip_atomic_store(reinterpret_cast<uint32_t*>(er.host) + 10, er.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -82,7 +82,7 @@ __device__ __forceinline__ void wg_spare_roles(const DnnPlan& p, const BwdPlan& 
       const float loss_sum = gh[0], D = gh[1], loss2 = gh[2], D2 = gh[3];
       float loss = loss_sum / D;
       if (er.algo == ULTR_ALGO_DLA) loss = loss2 / D2 + er.rlw * (loss_sum / D);
-      else if (er.algo == ULTR_ALGO_PAIRDEBIAS) loss = loss_sum;
+      else if (er.algo == ULTR_ALGO_PAIRDEBIAS || er.algo == ULTR_ALGO_PDGD) loss = loss_sum;
       if (lane == 0) {
         __hip_atomic_store(er.host, loss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -105,6 +105,10 @@ extern "C" int ultr_train_step(const ultr_step_args* a, void* stream) {
       rc = ultr_prs_loss(a->scores, a->labels, a->ipw_table, a->n_ipw, a->sigma, a->batch, a->list_size, a->dscores,
                          a->loss_ws, stream);
       break;
+    case ULTR_ALGO_PDGD:
+      rc = ultr_pdgd_loss(a->scores, a->labels, a->docids, a->n_docs, a->sigma, a->n_ipw, a->batch, a->list_size, a->dscores,
+                          a->loss_ws, stream);
+      break;
     case ULTR_ALGO_REGEM:
       rc = ultr_regem_loss(a->scores, a->labels, a->aux, a->uniforms, a->rng_seed, a->rng_step, a->batch, a->list_size,
                            a->dscores, nullptr, a->loss_ws, stream);

@@ -119,7 +119,7 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
                                             const uint32_t* __restrict__ h3flag = nullptr) {
   const int64_t P = u.n_params;
   const int L = u.list_size;
-  const float loss_sum = tail[0], D = tail[1], loss2 = tail[2], D2 = tail[3];
+  const float loss_sum = tail[0], D = u.algo == ULTR_ALGO_PDGD ? 1.0f : tail[1], loss2 = tail[2], D2 = tail[3];
   float gs = 1.0f, loss = loss_sum, rank_loss = 0.f, exam_loss = 0.f;
   switch (u.algo) {
     case ULTR_ALGO_SOFTMAX:  // loss = sum_b loss_b / sum w   (base_algorithm.py:330)
@@ -148,11 +148,16 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
       gs = 1.0f / D;
       loss = loss_sum / D;
       break;
+    case ULTR_ALGO_PDGD:  // the weighted pair terms are summed (pdgd.py:197-205)
+      gs = 1.0f;
+      loss = loss_sum;
+      break;
   }
   float norm = fabsf(gs) * sqrtf(ss);
   // l2_loss > 0 (ipw_rank.py:154-157 and siblings): g += lam * p, loss += l2_loss * sum p^2 / 2.  Every algorithm but DLA
-  // hands clip_grad_norm_ a parameter generator the L2 loop has already exhausted, so NOTHING is clipped (Appendix A.8);
-  // DLA adds the term to rank_loss (scaled by ranker_loss_weight with it) and clips the full gradient (dla.py:146-162).
+  // and PDGD hands clip_grad_norm_ a parameter generator the L2 loop has already exhausted, so NOTHING is clipped (Appendix
+  // A.8); DLA adds the term to rank_loss (scaled by ranker_loss_weight with it) and clips the full gradient (dla.py:146-162);
+  // PDGD passes a FRESH model.parameters() to opt_step (pdgd.py:206-212) and clips the full gradient too.
   float lam = 0.f;
   bool clip = u.max_gradient_norm > 0.f;
   if (u.l2_loss > 0.f && l2_sums != nullptr) {
@@ -164,7 +169,7 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
     } else {
       lam = u.l2_loss;
       loss += u.l2_loss * (0.5f * sp2);
-      clip = false;
+      clip = clip && u.algo == ULTR_ALGO_PDGD;
     }
     norm = sqrtf(fmaxf(gs * gs * ss + 2.0f * gs * lam * sgp + lam * lam * sp2, 0.f));
   }
@@ -445,9 +450,9 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
   if (wt != nullptr) {
     if (!ultr_make_dnn_plan(d, 0, &dp) || dp.P != u->n_params) return ULTR_E_BADARG;
   }
-  if (u->algo < 0 || u->algo > ULTR_ALGO_PRS || (u->optimizer != ULTR_OPT_ADAGRAD && u->optimizer != ULTR_OPT_SGD))
+  if (u->algo < 0 || u->algo > ULTR_ALGO_PDGD || (u->optimizer != ULTR_OPT_ADAGRAD && u->optimizer != ULTR_OPT_SGD))
     return ULTR_E_BADARG;
-  if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && !aux) return ULTR_E_BADARG;
+  if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && u->algo != ULTR_ALGO_PDGD && !aux) return ULTR_E_BADARG;
   if (u->optimizer == ULTR_OPT_ADAGRAD && u->algo != ULTR_ALGO_DLA && !state) return ULTR_E_BADARG;
   if (u->l2_loss < 0.f || (u->l2_loss > 0.f && !scalars_out) ||
       (u->l2_loss > 0.f && (u->algo == ULTR_ALGO_LAMBDARANK || u->algo == ULTR_ALGO_PRS)))

@@ -21,7 +21,8 @@ import torch
 from . import _lib, hip_ops
 
 ALGOS = {"softmax": _lib.ALGO_SOFTMAX, "dla": _lib.ALGO_DLA, "pairdebias": _lib.ALGO_PAIRDEBIAS,
-         "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM, "prs": _lib.ALGO_PRS}
+         "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM, "prs": _lib.ALGO_PRS,
+         "pdgd": _lib.ALGO_PDGD}
 
 
 def _f32(n, device, zero=False):
@@ -33,10 +34,12 @@ class StepEngine:
     def __init__(self, shape, batch, list_size, device, algo="softmax", optimizer="ada", learning_rate=0.05,
                  max_gradient_norm=5.0, ranker_loss_weight=1.0, propensity_learning_rate=None, em_step_size=0.05,
                  regulation_p=1.0, sigma=1.0, logits_to_prob="softmax", process_group=None, rng_seed=0, l2_loss=0.0,
-                 batch_total=None, comm=None, no_peer_comm=False):
+                 batch_total=None, comm=None, no_peer_comm=False, cutoff=None):
         if not torch.cuda.is_available():
             raise RuntimeError("ultra_pytorch_amd needs an MI355X/ROCm GPU: there is no CPU fallback")
         self.shape, self.B, self.L, self.device = shape, int(batch), int(list_size), device
+        # PDGD: the pairs stop at the cutoff (selection_bias_cutoff); tau rides in sigma (include/ultr_hip.h: ultr_step_args)
+        self.cutoff = self.L if cutoff is None else int(cutoff)
         shape.lib.ultr_config_reload()  # the ULTR_* knobs are read when an engine is built, never per step
         self.N = self.B * self.L
         self.algo = algo
@@ -119,7 +122,7 @@ class StepEngine:
         return scores
 
     # ---- loss stage ------------------------------------------------------------------------------
-    def loss(self, labels, aux=None, ipw_table=None, pw=None, uniforms=None):
+    def loss(self, labels, aux=None, ipw_table=None, pw=None, uniforms=None, docids=None, n_docs=None):
         B, L = self.B, self.L
         if self.algo == "softmax":
             hip_ops.softmax_ce(self.scores, labels, B, L, self.dscores, self.loss_ws, pw=pw, ipw_table=ipw_table)
@@ -133,6 +136,10 @@ class StepEngine:
             if ipw_table is None:
                 raise ValueError("PRSrank's loss needs the IPW table (ipw_table=)")
             hip_ops.prs_loss(self.scores, labels, ipw_table, self.sigma, B, L, self.dscores, self.loss_ws)
+        elif self.algo == "pdgd":
+            if docids is None or n_docs is None:
+                raise ValueError("PDGD's loss needs the docids and n_docs (its PADs)")
+            hip_ops.pdgd_loss(self.scores, labels, docids, n_docs, self.sigma, self.cutoff, B, L, self.dscores, self.loss_ws)
         elif self.algo == "regem":
             hip_ops.regem_loss(self.scores, labels, aux, B, L, self.dscores, self.loss_ws, uniforms=uniforms,
                                seed=self.rng_seed, step=self.rng_step)
@@ -289,6 +296,8 @@ class StepEngine:
         if ipw_table is not c[7]:
             a.ipw_table = ipw_table.data_ptr() if ipw_table is not None else None
             a.n_ipw = int(ipw_table.numel()) if ipw_table is not None else 0
+        if self.algo == "pdgd":
+            a.n_ipw = self.cutoff
         self._cached = (params, state, aux, features, docids, labels, pw, ipw_table)
         if self.algo == "regem":
             a.uniforms = uniforms.data_ptr() if uniforms is not None else None
@@ -429,7 +438,7 @@ class SetRankStepEngine(StepEngine):
         if self.algo == "regem":
             self.loss(labels, aux=aux, uniforms=uniforms)
         else:
-            self.loss(labels, aux=aux, ipw_table=ipw_table, pw=pw)
+            self.loss(labels, aux=aux, ipw_table=ipw_table, pw=pw, docids=docids, n_docs=n_docs)
         self.backward(params, features, n_docs, docids)
         self.update(params, state, aux)
         src = self.next_click_source

@@ -310,6 +310,13 @@ def prs_loss(scores, labels, ipw_table, sigma, B, L, dscores, loss_ws):
                                     _p(dscores), _p(loss_ws), _stream()), "ultr_prs_loss")
 
 
+def pdgd_loss(scores, labels, docids, n_docs, tau, cutoff, B, L, dscores, loss_ws):
+    """PDGD: the pairs of clicked documents with lower-labelled ones above them (or just below), each weighted by the
+    Plackett-Luce probability ratio of the swapped ranking; docids [L, B] int32 mark the PADs (== n_docs)."""
+    check(_lib.load().ultr_pdgd_loss(_p(scores), _p(labels), _p(docids), int(n_docs), float(tau), int(cutoff), int(B), int(L),
+                                     _p(dscores), _p(loss_ws), _stream()), "ultr_pdgd_loss")
+
+
 def regem_loss(scores, labels, propensity, B, L, dscores, loss_ws, uniforms=None, seed=0, step=0, pseudo_out=None):
     """RegressionEM estimation + BCE loss; uniforms [B, L] teacher-forces the Bernoulli draw."""
     check(_lib.load().ultr_regem_loss(_p(scores), _p(labels), _p(propensity), _p(uniforms), int(seed), int(step), int(B),

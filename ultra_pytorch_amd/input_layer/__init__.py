@@ -4,3 +4,5 @@ from .base_input_feed import BaseInputFeed  # noqa: F401
 from .click_simulation_feed import ClickSimulationFeed  # noqa: F401
 from .direct_label_feed import DirectLabelFeed  # noqa: F401
 from .device_click_feed import DeviceClickFeed, ResidentDataset  # noqa: F401
+from .stochastic_online_simulation_feed import StochasticOnlineSimulationFeed  # noqa: F401
+from .deterministic_online_simulation_feed import DeterministicOnlineSimulationFeed  # noqa: F401

@@ -9,3 +9,4 @@ from .pairwise_debias import PairDebias  # noqa: F401
 from .lambda_rank import LambdaRank  # noqa: F401
 from .regression_EM import RegressionEM  # noqa: F401
 from .prs_rank import PRSrank  # noqa: F401
+from .pdgd import PDGD  # noqa: F401
