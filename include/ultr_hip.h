@@ -428,6 +428,50 @@ typedef struct ultr_click_args {
 int ultr_click_batch_args(const ultr_click_args* c, void* stream);
 int ultr_feed_train_step(const ultr_step_args* a, const ultr_click_args* next, void* stream);
 
+/* ---- device-resident online simulation (ultr_online.hip; additive within ABI 8) -----------------------------------------
+ * Counterpart of {Stochastic,Deterministic}OnlineSimulationFeed.get_batch (stochastic_online_simulation_feed.py:96-226) for a
+ * dataset RESIDENT in HBM (lists / labels as for ultr_click_batch).  Two launches around the caller's scoring forward:
+ *   ultr_online_pick_args   per batch slot b: a query q drawn uniformly - among `eligible` [n_eligible] (query indexes whose
+ *                           max_candidates labels do not sum to 0: the check_validation filter, precomputed by the caller) or among
+ *                           all n_queries when eligible == NULL - and its first max_candidates candidates: cand_docids [M, B]
+ *                           (global ids, PAD = n_docs), cand_labels [M, B] (0 at a PAD), query_idx [B] (optional).
+ *   ultr_online_rerank_args per slot: list_len = 1 + the last non-PAD position; the first list_len candidates re-ranked by
+ *                           `scores` [B, M] - mode ULTR_ONLINE_DETERMINISTIC: descending and stable, scores ordered as unsigned keys
+ *                           (every NaN above +inf, -0 == +0); ULTR_ONLINE_STOCHASTIC: a Plackett-Luce draw at temperature tau (an
+ *                           exponential race; a document whose fp32 probability exp(tau (s - max)) / sum is 0 - log p < ln 2^-150 - follows all drawn ones,
+ *                           in index order) - then clicks on the first min(list_len, rank_list_size) positions of the new order
+ *                           (click_model as ultr_click_batch; oracle_mode: the relevance labels), redrawn on the SAME order up to
+ *                           max_redraws more times while the list has no click.  Writes docids [M, B], labels [M, B] (0 past the
+ *                           cutoff) and, when non-NULL, perm [M, B] (candidate index at each rank; identity past list_len).
+ * Randomness: Philox-4x32-10 keyed by (seed, step) as ultr_click_batch, own counter tags for the query pick, the race and the clicks
+ * (slot, attempt, position): a batch is a pure function of (seed, step, scores).  No atomics.  max_candidates > 256: ULTR_E_BADARG. */
+#define ULTR_ONLINE_DETERMINISTIC 0
+#define ULTR_ONLINE_STOCHASTIC 1
+typedef struct ultr_online_args {
+  const int32_t* lists;
+  const float* labels;
+  int64_t n_queries, n_docs;
+  const int32_t* eligible;
+  int64_t n_eligible;
+  const float* exam_prob;
+  const float* click_prob;
+  int32_t lmax, n_exam, n_rel, click_model;
+  uint64_t seed, step;
+  int32_t batch, max_candidates, rank_list_size, max_redraws;
+  int32_t mode, oracle_mode;
+  float tau;
+  int32_t pad_;
+  int32_t* cand_docids;
+  float* cand_labels;
+  const float* scores;
+  int32_t* docids;
+  float* out_labels;
+  int32_t* perm;
+  int32_t* query_idx;
+} ultr_online_args;
+int ultr_online_pick_args(const ultr_online_args* a, void* stream);
+int ultr_online_rerank_args(const ultr_online_args* a, void* stream);
+
 /* ---- e: data-parallel gradient exchange over xGMI -----------------------------
  * No reference counterpart: the reference is single-process.  One process per GPU; queries shard across ranks,
  * parameters / optimizer / EM state are replicated, and ONE sum per step of the flat vector

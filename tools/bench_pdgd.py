@@ -5,9 +5,13 @@ B 256, L 10) and config 4's (700-d, DNN[512,256,128], B 256, L 50), with PBM-lik
 The engines of one shape live in one process and are timed in alternating blocks of --block steps (device events around each
 block, steps queued back to back), so clock and thermal drift hit all alike.  Then the host online loop at config 2's shape:
 StochasticOnlineSimulationFeed.get_batch (GPU scoring, Plackett-Luce draw, click simulation on the host) + PDGD.train, per batch
-(feed-bound; reported, no target).  Prints one JSON line.
+(feed-bound; reported, no target).  Then the device online loop (input_layer.DeviceStochasticOnlineSimulationFeed /
+DeviceDeterministicOnlineSimulationFeed: pick, scoring forward, re-rank and clicks on the GPU) + PDGD.train at config 2's and
+config 4's shapes, per batch: device events around --device-online batches queued back to back, one synchronise at the end.
+Prints one JSON line.
 
-    python tools/bench_pdgd.py [--blocks 20] [--block 50] [--warmup 200] [--online 20] [--out profiles/pdgd_bench.json]
+    python tools/bench_pdgd.py [--blocks 20] [--block 50] [--warmup 200] [--online 20] [--device-online 200]
+                               [--out profiles/pdgd_bench.json]
 """
 import argparse
 import json
@@ -110,12 +114,44 @@ def time_online(n_batches):
             "batch_ms": 1e3 * (tf + ts) / n_batches}
 
 
+def time_device_online(name, n_batches, mode, warmup=20):
+    from ultra_pytorch_amd import input_layer
+    from ultra_pytorch_amd.utils import find_class
+    F, hidden, B, L = SHAPES[name]
+    exp = {"learning_algorithm": "ultra_pytorch_amd.learning_algorithm.PDGD", "learning_algorithm_hparams": "",
+           "ranking_model": "ultra_pytorch_amd.ranking_model.DNN", "ranking_model_hparams": "hidden_layer_sizes=%s" % json.dumps(hidden),
+           "max_candidate_num": L, "selection_bias_cutoff": L, "metrics": ["ndcg"], "metrics_topn": [1, 3]}
+    ds = _DS(2000, L, F, 0)
+    import contextlib
+    import io
+    cls = input_layer.DeviceStochasticOnlineSimulationFeed if mode == "stochastic" else input_layer.DeviceDeterministicOnlineSimulationFeed
+    with contextlib.redirect_stdout(io.StringIO()):
+        algo = find_class(exp["learning_algorithm"])(ds, exp)
+        feed = cls(algo, B, "", seed=0)
+        for _ in range(warmup):
+            algo.train(feed.get_batch(ds, check_validation=True)[0])
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        losses = []
+        for _ in range(n_batches):
+            f, _ = feed.get_batch(ds, check_validation=True)
+            losses.append(algo.train(f)[0])
+        e1.record()
+        e1.synchronize()
+        wall = time.perf_counter() - t0
+    return {"batches": n_batches, "mode": mode, "batch_ms": e0.elapsed_time(e1) / n_batches, "wall_batch_ms": 1e3 * wall / n_batches,
+            "finite_losses": bool(np.all(np.isfinite(losses)))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=20)
     ap.add_argument("--block", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--online", type=int, default=20)
+    ap.add_argument("--device-online", type=int, default=200)
     ap.add_argument("--shapes", default="cfg2,cfg4")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -124,6 +160,12 @@ def main():
         res[name] = time_shape(*SHAPES[name], args)
     if args.online > 0:
         res["online_cfg2"] = time_online(args.online)
+    if args.device_online > 0:
+        for name in args.shapes.split(","):
+            for mode in ("stochastic", "deterministic"):
+                res["device_online_%s_%s" % (name, mode)] = time_device_online(name, args.device_online, mode)
+        if "online_cfg2" in res and "device_online_cfg2_stochastic" in res:
+            res["device_online_speedup_cfg2"] = res["online_cfg2"]["batch_ms"] / res["device_online_cfg2_stochastic"]["batch_ms"]
     line = json.dumps(res)
     print(line)
     if args.out:

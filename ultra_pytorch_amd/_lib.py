@@ -43,6 +43,18 @@ class ClickArgs(ctypes.Structure):  # ultr_click_args (ABI 7)
                 ("docids", c_vp), ("clicks", c_vp), ("query_idx", c_vp)]
 
 
+class OnlineArgs(ctypes.Structure):  # ultr_online_args (ultr_online_pick_args / ultr_online_rerank_args)
+    _fields_ = [("lists", c_vp), ("labels", c_vp), ("n_queries", c_i64), ("n_docs", c_i64), ("eligible", c_vp), ("n_eligible", c_i64),
+                ("exam_prob", c_vp), ("click_prob", c_vp), ("lmax", c_i32), ("n_exam", c_i32), ("n_rel", c_i32), ("click_model", c_i32),
+                ("seed", ctypes.c_uint64), ("step", ctypes.c_uint64), ("batch", c_i32), ("max_candidates", c_i32),
+                ("rank_list_size", c_i32), ("max_redraws", c_i32), ("mode", c_i32), ("oracle_mode", c_i32), ("tau", c_f32),
+                ("pad_", c_i32), ("cand_docids", c_vp), ("cand_labels", c_vp), ("scores", c_vp), ("docids", c_vp),
+                ("out_labels", c_vp), ("perm", c_vp), ("query_idx", c_vp)]
+
+
+ONLINE_DETERMINISTIC, ONLINE_STOCHASTIC = 0, 1  # ultr_online_args::mode
+
+
 class SetRankDesc(ctypes.Structure):
     _fields_ = [("feature_size", c_i32), ("d_model", c_i32), ("num_heads", c_i32), ("num_layers", c_i32), ("dff", c_i32),
                 ("attention_dtype", c_i32), ("flags", c_i32)]
@@ -100,6 +112,8 @@ SIGNATURES = {
                                  c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "ultr_click_batch_args": (c_i32, [c_vp, c_vp]),
     "ultr_feed_train_step": (c_i32, [c_vp, c_vp, c_vp]),
+    "ultr_online_pick_args": (c_i32, [c_vp, c_vp]),
+    "ultr_online_rerank_args": (c_i32, [c_vp, c_vp]),
     "ultr_comm_create": (c_i32, [c_i32, c_i32, c_i64, ctypes.POINTER(c_vp)]),
     "ultr_comm_export": (c_i32, [c_vp, c_vp]),
     "ultr_comm_import": (c_i32, [c_vp, c_i32, c_vp]),

@@ -1,11 +1,59 @@
 // ultr_feed.h - the click draw of ultr_feed.hip as a device function: its own launch (click_batch_kernel) or a rider on the update
 // launch of the step in front of it (update_tiled_kernel: extra workgroups behind the update's own - ultr_feed_train_step).
+// click_decide, its per-position PBM / cascade / UBM decisions, is shared with the online re-rank (online_rerank_kernel, ultr_online.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ultr_hip.h"
 #include "ultr_device.h"
+
+// The click decision of position l = l0 + lane (in: l < L) of one chunk of 64 positions of an L-position list, from its label y and its
+// uniform u: PBM, cascade or UBM as ultr_click_batch draws them.  clicked_before (cascade: a click in an earlier chunk) and last_click
+// (UBM: the rank of the last click so far) are wave-uniform and carried from chunk to chunk; the caller starts them at false / -1.
+__device__ __forceinline__ float click_decide(int model, const float* __restrict__ exam, int n_exam, const float* __restrict__ cprob,
+                                              int n_rel, int L, int l0, int lane, bool in, float y, float u, bool& clicked_before,
+                                              int& last_click) {
+  const int l = l0 + lane;
+  float ck = 0.f;
+  if (in) {
+    const int lab = y > 0.f ? (int)y : 0;
+    const float cp = cprob[lab < n_rel ? lab : n_rel - 1];
+    if (model == ULTR_CLICK_UBM) {
+      // click iff u < exam x cp: the walk below compares u / cp with the examination probability; cp == 0 (a relevance level that
+      // is never clicked) gives +inf or NaN, and both compare false against every probability - no click, as intended
+      ck = u / cp;
+    } else {
+      ck = (u < exam[l < n_exam ? l : n_exam - 1] * cp) ? 1.f : 0.f;
+    }
+  }
+  if (model == ULTR_CLICK_UBM) {
+    // exam = dense [n_exam][n_exam] image of the triangular table (row = rank, column = distance - 1); getExamProb,
+    // click_models.py:175-186: beyond the table the LAST row serves - the last entry when no click precedes the position,
+    // else column distance - 1 saturating at the second-to-last
+    const float ratio = ck;
+    ck = 0.f;
+    const int hi = (L - l0) < 64 ? (L - l0) : 64;
+    for (int k = 0; k < hi; ++k) {
+      const int rank = l0 + k, dist = rank - last_click;
+      float ex;
+      if (rank < n_exam) ex = exam[rank * n_exam + dist - 1];
+      else if (dist > rank) ex = exam[(n_exam - 1) * n_exam + n_exam - 1];
+      else ex = exam[(n_exam - 1) * n_exam + (dist < n_exam - 1 ? dist - 1 : (n_exam >= 2 ? n_exam - 2 : 0))];
+      const float rk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ratio), k));
+      const bool hit = rk < ex;
+      if (hit) last_click = rank;
+      if (lane == k && hit) ck = 1.f;
+    }
+  }
+  if (model == ULTR_CLICK_CASCADE) {  // only the first click of the list counts (the draws behind it are made and ignored, as in the reference)
+    const uint64_t hit = __ballot(ck > 0.f);
+    const int first = hit ? (int)__builtin_ctzll(hit) : 64;
+    if (clicked_before || lane > first) ck = 0.f;
+    clicked_before = clicked_before || hit != 0;
+  }
+  return ck;
+}
 
 // one workgroup of 256 threads = four batch slots (one per wave); `block` = the workgroup's index among the draw's (batch + 3) / 4
 __device__ __forceinline__ void click_draw(const ultr_click_args& ca, int block) {
@@ -34,55 +82,21 @@ __device__ __forceinline__ void click_draw(const ultr_click_args& ca, int block)
     int last_click = -1;          // user-browsing model: rank of the last click so far
     for (int l0 = 0; l0 < L; l0 += 64) {
       const int l = l0 + lane;
-      float ck = 0.f;
       int32_t id = (int32_t)n_docs;
+      float y = 0.f, u = 0.f;
       if (l < L) {
         const int32_t d = (l < Lmax) ? lists[q * Lmax + l] : -1;
         // a PAD position counts as a label-0 document and CAN be clicked, exactly as in the reference feed
         // (click_simulation_feed.py:74-81 builds the label list with 0 for pads and samples every position)
-        float y = 0.f;
         if (d >= 0) {
           id = d;
           y = rel[q * Lmax + l];
         }
-        const int lab = y > 0.f ? (int)y : 0;
         uint32_t r[4] = {(uint32_t)b, (uint32_t)attempt, (uint32_t)(l >> 2), 0x2545F491u};
         rng(r);
-        const float cp = cprob[lab < n_rel ? lab : n_rel - 1];
-        const float u = u01(r[l & 3]);
-        if (model == ULTR_CLICK_UBM) {
-          // click iff u < exam x cp: the walk below compares u / cp with the examination probability; cp == 0 (a relevance level that
-          // is never clicked) gives +inf or NaN, and both compare false against every probability - no click, as intended
-          ck = u / cp;
-        } else {
-          ck = (u < exam[l < n_exam ? l : n_exam - 1] * cp) ? 1.f : 0.f;
-        }
+        u = u01(r[l & 3]);
       }
-      if (model == ULTR_CLICK_UBM) {
-        // exam = dense [n_exam][n_exam] image of the triangular table (row = rank, column = distance - 1); getExamProb,
-        // click_models.py:175-186: beyond the table the LAST row serves - the last entry when no click precedes the position,
-        // else column distance - 1 saturating at the second-to-last
-        const float ratio = ck;
-        ck = 0.f;
-        const int hi = (L - l0) < 64 ? (L - l0) : 64;
-        for (int k = 0; k < hi; ++k) {
-          const int rank = l0 + k, dist = rank - last_click;
-          float ex;
-          if (rank < n_exam) ex = exam[rank * n_exam + dist - 1];
-          else if (dist > rank) ex = exam[(n_exam - 1) * n_exam + n_exam - 1];
-          else ex = exam[(n_exam - 1) * n_exam + (dist < n_exam - 1 ? dist - 1 : (n_exam >= 2 ? n_exam - 2 : 0))];
-          const float rk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ratio), k));
-          const bool hit = rk < ex;
-          if (hit) last_click = rank;
-          if (lane == k && hit) ck = 1.f;
-        }
-      }
-      if (model == ULTR_CLICK_CASCADE) {  // only the first click of the list counts (the draws behind it are made and ignored, as in the reference)
-        const uint64_t hit = __ballot(ck > 0.f);
-        const int first = hit ? (int)__builtin_ctzll(hit) : 64;
-        if (clicked_before || lane > first) ck = 0.f;
-        clicked_before = clicked_before || hit != 0;
-      }
+      const float ck = click_decide(model, exam, n_exam, cprob, n_rel, L, l0, lane, l < L, y, u, clicked_before, last_click);
       if (l < L) {
         docids[(int64_t)l * B + b] = id;
         clicks[(int64_t)l * B + b] = ck;

@@ -6,3 +6,5 @@ from .direct_label_feed import DirectLabelFeed  # noqa: F401
 from .device_click_feed import DeviceClickFeed, ResidentDataset  # noqa: F401
 from .stochastic_online_simulation_feed import StochasticOnlineSimulationFeed  # noqa: F401
 from .deterministic_online_simulation_feed import DeterministicOnlineSimulationFeed  # noqa: F401
+from .device_online_simulation_feed import (DeviceOnlineSimulationFeed, DeviceStochasticOnlineSimulationFeed,  # noqa: F401
+                                            DeviceDeterministicOnlineSimulationFeed)
