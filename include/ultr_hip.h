@@ -262,7 +262,9 @@ int ultr_setrank_backward(const ultr_setrank_desc* c, const float* params, int32
  * (dla.py:141-177: per-model clip, fresh = stateless Adagrad), and the t_plus/t_minus EM
  * updates (pairwise_debias.py:159-163, lambda_rank.py:136-142). */
 enum ultr_algo { ULTR_ALGO_SOFTMAX = 0, ULTR_ALGO_DLA = 1, ULTR_ALGO_PAIRDEBIAS = 2, ULTR_ALGO_LAMBDARANK = 3, ULTR_ALGO_REGEM = 4,
-                 ULTR_ALGO_PRS = 5, ULTR_ALGO_PDGD = 6 };
+                 ULTR_ALGO_PRS = 5, ULTR_ALGO_PDGD = 6,
+                 /* DBGD / MGD: grads from ultr_dbgd_grad_args, loss in the step tail, D = 1 (no l2_loss) */
+                 ULTR_ALGO_DBGD = 7 };
 enum ultr_opt { ULTR_OPT_ADAGRAD = 0, ULTR_OPT_SGD = 1 };
 
 typedef struct ultr_update_desc {
@@ -471,6 +473,72 @@ typedef struct ultr_online_args {
 } ultr_online_args;
 int ultr_online_pick_args(const ultr_online_args* a, void* stream);
 int ultr_online_rerank_args(const ultr_online_args* a, void* stream);
+
+/* ---- DBGD / MGD: weight-perturbing online learners (ultr_dbgd.hip; additive within ABI 8) ---------------------------------
+ * Counterpart of DBGD.train / MGD.train (dbgd.py:125-330, mgd.py:86-232) and TeamDraftInterleaving (team_draft_interleave.py).
+ * R = n_rankers candidates (DBGD 1, MGD ranker_num); ranker 0 is the current model.  A step, on one stream:
+ *   ultr_dbgd_noise_args       noise [R, P]: per Linear parameter F.normalize(N(0, 1), dim = 0) - per input column of a weight
+ *                              (over `out`), over a whole bias; the [1, in] scorer row becomes sign(z) - and 0 on the LayerNorm
+ *                              entries; cand_params [R, cand_stride] = params + noise_rate * noise.  noise_in [R, P] (optional): the raw
+ *                              normals instead of the Philox draw (entries of LayerNorm parameters unused).
+ *   the caller's R + 1 forwards (ultr_dnn_forward with saved = NULL, ultr_dnn_build_wt before each candidate's) into
+ *   scores [R + 1, B, L]: L = max_candidates with need_interleave, rank_list_size without.
+ *   ultr_dbgd_interleave_args  (need_interleave) per list: list_len = 1 + the last non-PAD position (docids [M, B], PAD = n_docs);
+ *                              each ranker's order of the first list_len candidates (mode as ultr_online_rerank_args: the stable
+ *                              descending sort or the Plackett-Luce race at tau); the team-draft multileave (the agreed prefix is
+ *                              team -1, then a fresh shuffle of the rankers every R + 1 picks); clicks (click_model as
+ *                              ultr_click_batch) on labels [M, B] in the multileaved order, first min(list_len, rank_list_size)
+ *                              positions, redrawn up to max_redraws more times while the list has none; winners [B, R + 1] =
+ *                              clicks of team r / (clicks of all teams + 1e-7).  Optional outputs [M, B]: interleaved (candidate
+ *                              index, -1 past list_len), teams (-1 agreed prefix, -2 past list_len), clicks (0 past the cutoff);
+ *                              loss_scores [B, rank_list_size] = ranker 0's first rank_list_size scores (for ultr_ndcg).
+ *                              Optional injected draws: shuffles_in [B, M, R + 1] (the ranker order of round t of list b) and
+ *                              clicks_in [M, B] (the clicks; no redraw).
+ *   the caller's ultr_ndcg (docids = NULL: PADs unmasked, as dbgd.py:138-149) of NDCG@rank_list_size into ndcg [R + 1]:
+ *                              ndcg[0] of the current model (the loss is 1 - ndcg[0]); without interleaving every ranker's.
+ *   ultr_dbgd_grad_args        grads [P + ultr_step_tail_floats(max_candidates)] = -sum_r c_r noise_r (the update steps TOWARD the
+ *                              winners), c_r = mean_b winners[b, r] (need_interleave) or the mean of the reference's batch-level
+ *                              winners ceil(ndcg_r - ndcg_0) / (sum + 1e-9); step tail [0] = the loss, [1] = 1; the sum-of-squares
+ *                              partials at the head of bwd_ws.  Then ultr_apply_update (algo ULTR_ALGO_DBGD, l2_loss = 0,
+ *                              list_size = max_candidates).
+ * Randomness: Philox-4x32-10 keyed by (seed, step), own counter tags for the noise (element, ranker), the race (list, ranker,
+ * position), the shuffles (list, round) and the clicks (list, attempt, position).  No atomics.
+ * ULTR_E_BADARG: max_candidates > 256, n_rankers + 1 > 16, rank_list_size > max_candidates, n_params != the desc's. */
+#define ULTR_DBGD_MAX_M 256
+#define ULTR_DBGD_MAX_RANKERS 16 /* R + 1 */
+typedef struct ultr_dbgd_args {
+  const ultr_dnn_desc* desc;
+  int64_t n_params;
+  int32_t n_rankers, batch, max_candidates, rank_list_size;
+  int32_t need_interleave, mode, max_redraws, click_model;
+  int32_t n_exam, n_rel;
+  float noise_rate, tau;
+  uint64_t seed, step;
+  const float* params;
+  const float* noise_in;
+  float* noise;
+  float* cand_params;
+  int64_t cand_stride; /* floats from one candidate vector to the next (0: n_params); a multiple of 4 keeps each 16-byte aligned */
+  const float* scores;
+  const int32_t* docids;
+  int64_t n_docs;
+  const float* labels;
+  const float* exam_prob;
+  const float* click_prob;
+  const int32_t* shuffles_in;
+  const float* clicks_in;
+  float* winners;
+  int32_t* interleaved;
+  int32_t* teams;
+  float* clicks;
+  float* loss_scores;
+  const float* ndcg;
+  float* grads;
+  void* bwd_ws;
+} ultr_dbgd_args;
+int ultr_dbgd_noise_args(const ultr_dbgd_args* a, void* stream);
+int ultr_dbgd_interleave_args(const ultr_dbgd_args* a, void* stream);
+int ultr_dbgd_grad_args(const ultr_dbgd_args* a, void* stream);
 
 /* ---- e: data-parallel gradient exchange over xGMI -----------------------------
  * No reference counterpart: the reference is single-process.  One process per GPU; queries shard across ranks,

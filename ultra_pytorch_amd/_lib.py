@@ -13,7 +13,7 @@ ULTR_MAX_HIDDEN = 7
 COMM_HANDLE_BYTES, COMM_MAX_WORLD = 64, 8
 ACT = {"elu": 0, "relu": 1, "tanh": 2, "sigmoid": 3}  # base_ranking_model.py:63-69 ("selu" raises in the reference)
 ATTN_DTYPE = {"fp32": 0, "fp16": 1}
-ALGO_SOFTMAX, ALGO_DLA, ALGO_PAIRDEBIAS, ALGO_LAMBDARANK, ALGO_REGEM, ALGO_PRS, ALGO_PDGD = 0, 1, 2, 3, 4, 5, 6
+ALGO_SOFTMAX, ALGO_DLA, ALGO_PAIRDEBIAS, ALGO_LAMBDARANK, ALGO_REGEM, ALGO_PRS, ALGO_PDGD, ALGO_DBGD = 0, 1, 2, 3, 4, 5, 6, 7
 OPT_ADAGRAD, OPT_SGD = 0, 1
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
@@ -53,6 +53,20 @@ class OnlineArgs(ctypes.Structure):  # ultr_online_args (ultr_online_pick_args /
 
 
 ONLINE_DETERMINISTIC, ONLINE_STOCHASTIC = 0, 1  # ultr_online_args::mode
+
+
+class DbgdArgs(ctypes.Structure):  # ultr_dbgd_args (ultr_dbgd_noise_args / ultr_dbgd_interleave_args / ultr_dbgd_grad_args)
+    _fields_ = [("desc", ctypes.POINTER(DnnDesc)), ("n_params", c_i64), ("n_rankers", c_i32), ("batch", c_i32),
+                ("max_candidates", c_i32), ("rank_list_size", c_i32), ("need_interleave", c_i32), ("mode", c_i32),
+                ("max_redraws", c_i32), ("click_model", c_i32), ("n_exam", c_i32), ("n_rel", c_i32), ("noise_rate", c_f32),
+                ("tau", c_f32), ("seed", ctypes.c_uint64), ("step", ctypes.c_uint64), ("params", c_vp), ("noise_in", c_vp),
+                ("noise", c_vp), ("cand_params", c_vp), ("cand_stride", c_i64), ("scores", c_vp), ("docids", c_vp), ("n_docs", c_i64), ("labels", c_vp),
+                ("exam_prob", c_vp), ("click_prob", c_vp), ("shuffles_in", c_vp), ("clicks_in", c_vp), ("winners", c_vp),
+                ("interleaved", c_vp), ("teams", c_vp), ("clicks", c_vp), ("loss_scores", c_vp), ("ndcg", c_vp), ("grads", c_vp),
+                ("bwd_ws", c_vp)]
+
+
+DBGD_MAX_M, DBGD_MAX_RANKERS = 256, 16  # include/ultr_hip.h: ULTR_DBGD_MAX_M, ULTR_DBGD_MAX_RANKERS (R + 1)
 
 
 class SetRankDesc(ctypes.Structure):
@@ -114,6 +128,9 @@ SIGNATURES = {
     "ultr_feed_train_step": (c_i32, [c_vp, c_vp, c_vp]),
     "ultr_online_pick_args": (c_i32, [c_vp, c_vp]),
     "ultr_online_rerank_args": (c_i32, [c_vp, c_vp]),
+    "ultr_dbgd_noise_args": (c_i32, [c_vp, c_vp]),
+    "ultr_dbgd_interleave_args": (c_i32, [c_vp, c_vp]),
+    "ultr_dbgd_grad_args": (c_i32, [c_vp, c_vp]),
     "ultr_comm_create": (c_i32, [c_i32, c_i32, c_i64, ctypes.POINTER(c_vp)]),
     "ultr_comm_export": (c_i32, [c_vp, c_vp]),
     "ultr_comm_import": (c_i32, [c_vp, c_i32, c_vp]),

@@ -27,27 +27,15 @@
 #include "../../include/ultr_hip.h"
 #include "ultr_device.h"
 #include "ultr_feed.h"
+#include "ultr_rank.h"
 
 #define ONLINE_MAX_M 256
 #define ONLINE_QUERY_TAG 0x0F1A3E01u
 #define ONLINE_RACE_TAG 0x0F1A3E02u
 #define ONLINE_CLICK_TAG 0x0F1A3E03u
-#define ONLINE_LN_ZERO_PROB -103.97208f  // ln 2^-150: an fp32 probability below it rounds to 0
 
 __device__ __forceinline__ Philox online_rng(uint64_t seed, uint64_t step) {
   return Philox{(uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step};
-}
-
-// the descending order of scores as an unsigned key (ndcg_list_kernel's order): -0 and +0 equal, every NaN equal and above +inf
-__device__ __forceinline__ unsigned online_key(float s) {
-  if (s != s) return 0xFFFFFFFFu;
-  const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ int wave_max_int(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
 }
 
 // one workgroup of 256 threads = four batch slots (one per wave)
@@ -95,46 +83,12 @@ __global__ __launch_bounds__(256) void online_rerank_kernel(ultr_online_args a) 
     if (a.cand_docids[(int64_t)l * B + b] != pad) last = l;
   const int len = wave_max_int(last) + 1;
 
-  // keys of the first list_len positions
-  float sum = 0.f, mxs = -INFINITY;
-  if (a.mode == ULTR_ONLINE_STOCHASTIC) {
-    for (int l = lane; l < len; l += 64) mxs = fmaxf(mxs, a.scores[(int64_t)b * M + l]);
-    mxs = wave_max(mxs);
-    for (int l = lane; l < len; l += 64) sum += expf(a.tau * (a.scores[(int64_t)b * M + l] - mxs));
-    sum = wave_sum(sum);
-  }
-  for (int l = lane; l < len; l += 64) {
-    const float s = a.scores[(int64_t)b * M + l];
-    unsigned k;
-    if (a.mode == ULTR_ONLINE_STOCHASTIC) {
-      const float lw = a.tau * (s - mxs);
-      uint32_t r[4] = {(uint32_t)b, 0u, (uint32_t)(l >> 2), ONLINE_RACE_TAG};
-      rng(r);
-      const float e = -logf(1.0f - u01(r[l & 3]));  // Exp(1); 1 - u is exact for u = k 2^-24
-      // fp32 probability 0: exp(lw) / sum rounds to 0 below 2^-150, judged in the log domain (exp in the subnormal range is not
-      // reproducible across implementations; log p = lw - log sum is)
-      k = (lw - logf(sum) < ONLINE_LN_ZERO_PROB) ? 0u : online_key(lw - logf(e));
-    } else {
-      k = online_key(s);
-    }
-    key[l] = k;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  for (int i = lane; i < len; i += 64) {
-    const unsigned ki = key[i];
-    int r = 0;
-    for (int j = 0; j < len; ++j) {
-      const unsigned kj = key[j];
-      r += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
-    }
-    perm[r] = i;
-  }
+  // keys of the first list_len positions, then the order (ultr_rank.h)
+  wave_rank_keys(a.scores + (int64_t)b * M, len, a.mode == ULTR_ONLINE_STOCHASTIC, a.tau, rng, (uint32_t)b, 0u, ONLINE_RACE_TAG, key,
+                 lane);
+  wave_rank_by_count(key, len, perm, lane);
   for (int i = len + lane; i < M; i += 64) perm[i] = i;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  wave_lds_sync();
 
   for (int l = lane; l < M; l += 64) {
     const int src = perm[l];

@@ -119,7 +119,7 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
                                             const uint32_t* __restrict__ h3flag = nullptr) {
   const int64_t P = u.n_params;
   const int L = u.list_size;
-  const float loss_sum = tail[0], D = u.algo == ULTR_ALGO_PDGD ? 1.0f : tail[1], loss2 = tail[2], D2 = tail[3];
+  const float loss_sum = tail[0], D = (u.algo == ULTR_ALGO_PDGD || u.algo == ULTR_ALGO_DBGD) ? 1.0f : tail[1], loss2 = tail[2], D2 = tail[3];
   float gs = 1.0f, loss = loss_sum, rank_loss = 0.f, exam_loss = 0.f;
   switch (u.algo) {
     case ULTR_ALGO_SOFTMAX:  // loss = sum_b loss_b / sum w   (base_algorithm.py:330)
@@ -149,6 +149,7 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
       loss = loss_sum / D;
       break;
     case ULTR_ALGO_PDGD:  // the weighted pair terms are summed (pdgd.py:197-205)
+    case ULTR_ALGO_DBGD:  // grads already hold the step's direction; the loss is 1 - NDCG of the current model (dbgd.py:140)
       gs = 1.0f;
       loss = loss_sum;
       break;
@@ -450,12 +451,13 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
   if (wt != nullptr) {
     if (!ultr_make_dnn_plan(d, 0, &dp) || dp.P != u->n_params) return ULTR_E_BADARG;
   }
-  if (u->algo < 0 || u->algo > ULTR_ALGO_PDGD || (u->optimizer != ULTR_OPT_ADAGRAD && u->optimizer != ULTR_OPT_SGD))
+  if (u->algo < 0 || u->algo > ULTR_ALGO_DBGD || (u->optimizer != ULTR_OPT_ADAGRAD && u->optimizer != ULTR_OPT_SGD))
     return ULTR_E_BADARG;
-  if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && u->algo != ULTR_ALGO_PDGD && !aux) return ULTR_E_BADARG;
+  if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && u->algo != ULTR_ALGO_PDGD && u->algo != ULTR_ALGO_DBGD && !aux)
+    return ULTR_E_BADARG;
   if (u->optimizer == ULTR_OPT_ADAGRAD && u->algo != ULTR_ALGO_DLA && !state) return ULTR_E_BADARG;
   if (u->l2_loss < 0.f || (u->l2_loss > 0.f && !scalars_out) ||
-      (u->l2_loss > 0.f && (u->algo == ULTR_ALGO_LAMBDARANK || u->algo == ULTR_ALGO_PRS)))
+      (u->l2_loss > 0.f && (u->algo == ULTR_ALGO_LAMBDARANK || u->algo == ULTR_ALGO_PRS || u->algo == ULTR_ALGO_DBGD)))
     return ULTR_E_BADARG;  // LambdaRank and PRSrank have no l2_loss hyper-parameter (lambda_rank.py:42-49, prs_rank.py:43-50)
   const int tail = (int)ultr_tail_len(u->list_size);
   const int nsq = (int)ultr_red_blocks(u->n_params, tail);

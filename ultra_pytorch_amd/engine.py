@@ -22,7 +22,7 @@ from . import _lib, hip_ops
 
 ALGOS = {"softmax": _lib.ALGO_SOFTMAX, "dla": _lib.ALGO_DLA, "pairdebias": _lib.ALGO_PAIRDEBIAS,
          "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM, "prs": _lib.ALGO_PRS,
-         "pdgd": _lib.ALGO_PDGD}
+         "pdgd": _lib.ALGO_PDGD, "dbgd": _lib.ALGO_DBGD}
 
 
 def _f32(n, device, zero=False):
@@ -471,3 +471,134 @@ class SetRankEvalEngine(EvalEngine):
             hip_ops.setrank_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.saved)
         self._ndcg(labels, docids, n_docs)
         return self.scores, self.ndcg
+
+
+class DbgdEngine:
+    """One DBGD / MGD step (learning_algorithm.DBGD) on one GPU, every launch on the current stream (csrc/ultr_dbgd.hip):
+
+        ultr_dbgd_noise_args -> R + 1 x ultr_dnn_forward (validation path; ultr_dnn_build_wt before each candidate's)
+        -> [need_interleave: ultr_dbgd_interleave_args] -> ultr_ndcg (R + 1 of them without interleaving) -> ultr_dbgd_grad_args
+        -> ultr_apply_update (ULTR_ALGO_DBGD)
+
+    The buffers are this engine's (one per (batch, max_candidates) shape, cached by the algorithm).  The loss is read from the update's
+    host-mapped step report (read_loss, as StepEngine): no other host synchronisation."""
+
+    def __init__(self, shape, batch, max_candidates, rank_list_size, n_rankers, device, need_interleave=True, stochastic=True, tau=1.0,
+                 noise_rate=0.5, learning_rate=0.5, max_gradient_norm=5.0, optimizer="sgd", click_model=0, exam=None, n_exam=0,
+                 cprob=None, seed=0, max_redraws=100):
+        if not torch.cuda.is_available():
+            raise RuntimeError("ultra_pytorch_amd needs an MI355X/ROCm GPU: there is no CPU fallback")
+        B, M, rls, R = int(batch), int(max_candidates), int(rank_list_size), int(n_rankers)
+        if not 0 < M <= _lib.DBGD_MAX_M:
+            raise ValueError("DBGD / MGD support max_candidate_num up to %d (got %d)" % (_lib.DBGD_MAX_M, M))
+        if not 1 <= R < _lib.DBGD_MAX_RANKERS:
+            raise ValueError("DBGD / MGD support 1 .. %d candidate rankers (got %d)" % (_lib.DBGD_MAX_RANKERS - 1, R))
+        if not 0 < rls <= M:
+            raise ValueError("rank_list_size must be in 1 .. max_candidate_num (got %d, %d)" % (rls, M))
+        self.shape, self.lib, self.device = shape, shape.lib, device
+        shape.lib.ultr_config_reload()
+        self.B, self.M, self.rls, self.R = B, M, rls, R
+        self.need_interleave = bool(need_interleave)
+        self.L = M if self.need_interleave else rls  # the forwards' list length
+        P, tail = shape.n_params, hip_ops.tail_floats(M)
+        self.P, self.pg, self.comm = P, None, None
+        self.noise = _f32(R * P, device, zero=True).view(R, P)
+        # candidate vectors on a 64-float stride: each starts 16-byte aligned, as the fast forward path needs
+        self.cand_stride = (P + 63) // 64 * 64
+        self.cand = _f32(R * self.cand_stride, device, zero=True).view(R, self.cand_stride)[:, :P]
+        nwt = int(shape.lib.ultr_dnn_wt_floats(ctypes.byref(shape.desc)))
+        self.cand_wt = [_f32(nwt, device, zero=True) for _ in range(R)]  # (alignment gaps stay zero, as WeightCopy's)
+        self.scores = _f32((R + 1) * B * self.L, device, zero=True).view(R + 1, B, self.L)
+        self.winners = _f32(B * (R + 1), device, zero=True).view(B, R + 1)
+        self.loss_scores = _f32(B * rls, device, zero=True).view(B, rls)
+        self.ndcg = _f32(R + 1, device, zero=True)
+        self.ndcg_ws = _f32(B, device)
+        self.grads = _f32(P + tail, device, zero=True)
+        self.bwd_ws = _f32((P + tail + 63) // 64 + 16, device, zero=True)
+        self.scalars = _f32(16, device, zero=True)
+        self._hs = torch.zeros(16, dtype=torch.float32).pin_memory()
+        self._hs_f = self._hs.numpy()
+        self._hs_u = self._hs_f.view(np.uint32)
+        self._seq, self._host_report = 0, True
+        self._topn = (ctypes.c_int32 * 1)(rls)
+        u = _lib.UpdateDesc()
+        u.algo = _lib.ALGO_DBGD
+        u.optimizer = _lib.OPT_SGD if optimizer == "sgd" else _lib.OPT_ADAGRAD
+        u.list_size = M
+        u.n_params = P
+        u.learning_rate = float(learning_rate)
+        u.max_gradient_norm = float(max_gradient_norm)
+        u.adagrad_eps = 1e-10
+        u.host_scalars = self._hs.data_ptr()
+        self.udesc = u
+        self._exam, self._cprob = exam, cprob  # (kept alive: the argument block points at them)
+        a = self.args = _lib.DbgdArgs()
+        a.desc = ctypes.pointer(shape.desc)
+        a.n_params, a.n_rankers, a.batch, a.max_candidates, a.rank_list_size = P, R, B, M, rls
+        a.need_interleave = 1 if self.need_interleave else 0
+        a.mode = _lib.ONLINE_STOCHASTIC if stochastic else _lib.ONLINE_DETERMINISTIC
+        a.max_redraws, a.click_model = int(max_redraws), int(click_model)
+        a.n_exam, a.n_rel = int(n_exam), int(cprob.numel()) if cprob is not None else 0
+        a.exam_prob = exam.data_ptr() if exam is not None else None
+        a.click_prob = cprob.data_ptr() if cprob is not None else None
+        a.noise_rate, a.tau = float(noise_rate), float(tau)
+        a.seed, a.step = int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+        a.noise, a.cand_params, a.cand_stride = self.noise.data_ptr(), self.cand.data_ptr(), self.cand_stride
+        a.scores, a.winners, a.loss_scores = self.scores.data_ptr(), self.winners.data_ptr(), self.loss_scores.data_ptr()
+        a.ndcg, a.grads, a.bwd_ws = self.ndcg.data_ptr(), self.grads.data_ptr(), self.bwd_ws.data_ptr()
+        self._aref = ctypes.byref(a)
+        self.rng_step = 0
+
+    read_scalars = StepEngine.read_scalars
+    read_loss = StepEngine.read_loss
+    _raise_on_status = StepEngine._raise_on_status
+    H3_RANGE, H3_NEAR = StepEngine.H3_RANGE, StepEngine.H3_NEAR
+
+    def close(self):
+        pass
+
+    def train_step(self, params, state, features, n_docs, docids, labels, noise_in=None, shuffles_in=None, clicks_in=None,
+                   interleaved=None, teams=None, clicks=None, step=None):
+        """One step on the batch docids / labels [max_candidates, B] (device).  The draws are Philox(seed, step), step = this engine's
+        step counter unless given; noise_in [R, P] / shuffles_in [B, M, R + 1] / clicks_in [M, B] replace them (tests).  Optional
+        [M, B] outputs: interleaved, teams, clicks.  Returns the device scalars of the update ([0] loss)."""
+        lib, shape, a, st = self.lib, self.shape, self.args, hip_ops.raw_stream()
+        B, L, R = self.B, self.L, self.R
+        a.step = self.rng_step if step is None else int(step)
+        self.rng_step += 1
+        a.params = params.data_ptr()
+        a.noise_in = noise_in.data_ptr() if noise_in is not None else None
+        a.shuffles_in = shuffles_in.data_ptr() if shuffles_in is not None else None
+        a.clicks_in = clicks_in.data_ptr() if clicks_in is not None else None
+        a.interleaved = interleaved.data_ptr() if interleaved is not None else None
+        a.teams = teams.data_ptr() if teams is not None else None
+        a.clicks = clicks.data_ptr() if clicks is not None else None
+        a.docids, a.labels, a.n_docs = docids.data_ptr(), labels.data_ptr(), int(n_docs)
+        _lib.check(lib.ultr_dbgd_noise_args(self._aref, st), "ultr_dbgd_noise_args")
+        fp = features.data_ptr() if n_docs > 0 else None
+        ids = docids.data_ptr()
+        desc = ctypes.byref(shape.desc)
+        wt0 = hip_ops.weight_copy(shape).get(params)
+        _lib.check(lib.ultr_dnn_forward(desc, params.data_ptr(), wt0.data_ptr(), fp, int(n_docs), ids, B, L, self.scores[0].data_ptr(),
+                                        None, st), "ultr_dnn_forward")
+        for r in range(R):
+            cp, cw = self.cand[r].data_ptr(), self.cand_wt[r].data_ptr()
+            _lib.check(lib.ultr_dnn_build_wt(desc, cp, cw, st), "ultr_dnn_build_wt")
+            _lib.check(lib.ultr_dnn_forward(desc, cp, cw, fp, int(n_docs), ids, B, L, self.scores[r + 1].data_ptr(), None, st),
+                       "ultr_dnn_forward")
+        ndcg = lib.ultr_ndcg
+        if self.need_interleave:
+            _lib.check(lib.ultr_dbgd_interleave_args(self._aref, st), "ultr_dbgd_interleave_args")
+            _lib.check(ndcg(self.loss_scores.data_ptr(), labels.data_ptr(), None, int(n_docs), B, self.rls, self._topn, 1,
+                            self.ndcg.data_ptr(), None, None, self.ndcg_ws.data_ptr(), st), "ultr_ndcg")
+        else:
+            for r in range(R + 1):
+                _lib.check(ndcg(self.scores[r].data_ptr(), labels.data_ptr(), None, int(n_docs), B, self.rls, self._topn, 1,
+                                self.ndcg.data_ptr() + 4 * r, None, None, self.ndcg_ws.data_ptr(), st), "ultr_ndcg")
+        _lib.check(lib.ultr_dbgd_grad_args(self._aref, st), "ultr_dbgd_grad_args")
+        self._seq = (self._seq % 0xFFFFFFFF) + 1
+        self.udesc.seq = self._seq
+        _lib.check(lib.ultr_apply_update(ctypes.byref(self.udesc), desc, params.data_ptr(), wt0.data_ptr(),
+                                         state.data_ptr() if state is not None else None, self.grads.data_ptr(), None,
+                                         self.bwd_ws.data_ptr(), self.scalars.data_ptr(), st), "ultr_apply_update")
+        return self.scalars

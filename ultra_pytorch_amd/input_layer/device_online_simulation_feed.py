@@ -41,8 +41,11 @@ class DeviceOnlineSimulationFeed(object):
         self.hparams = HParams(**defaults)
         self.hparams.parse(hparam_str)
         self.need_interleave = bool(getattr(model.hparams, "need_interleave", False))
-        if self.need_interleave:
-            raise NotImplementedError("result interleaving (TeamDraftInterleaving) belongs to DBGD, which is not implemented")
+        # result interleaving happens inside train() of the algorithms that declare it (DBGD, MGD: INTERLEAVES_IN_TRAIN); the
+        # feed itself serves the same batches either way, as the reference's does
+        if self.need_interleave and not getattr(model, "INTERLEAVES_IN_TRAIN", False):
+            raise NotImplementedError("result interleaving (TeamDraftInterleaving) is done by DBGD / MGD inside train(); %s does "
+                                      "not interleave" % type(model).__name__)
         path = self.hparams.click_model_json
         if not os.path.exists(path):
             alt = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", os.path.basename(path))

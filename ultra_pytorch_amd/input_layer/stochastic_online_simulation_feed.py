@@ -46,8 +46,11 @@ class OnlineSimulationFeed(BaseInputFeed):
         self.batch_size, self.model = batch_size, model
         self.global_batch_count = 0
         self.need_interleave = bool(getattr(model.hparams, "need_interleave", False))
-        if self.need_interleave:
-            raise NotImplementedError("result interleaving (TeamDraftInterleaving) belongs to DBGD, which is not implemented")
+        # result interleaving happens inside train() of the algorithms that declare it (DBGD, MGD: INTERLEAVES_IN_TRAIN); the
+        # feed itself serves the same batches either way, as the reference's does
+        if self.need_interleave and not getattr(model, "INTERLEAVES_IN_TRAIN", False):
+            raise NotImplementedError("result interleaving (TeamDraftInterleaving) is done by DBGD / MGD inside train(); %s does "
+                                      "not interleave" % type(model).__name__)
 
     def prepare_true_labels_with_index(self, data_set, index, docid_inputs, letor_features, labels, check_validation=False):
         """stochastic_online_simulation_feed.py:78-94: the relevance labels of all max_candidate_num positions; a list without

@@ -10,3 +10,4 @@ from .lambda_rank import LambdaRank  # noqa: F401
 from .regression_EM import RegressionEM  # noqa: F401
 from .prs_rank import PRSrank  # noqa: F401
 from .pdgd import PDGD  # noqa: F401
+from .dbgd import DBGD, MGD  # noqa: F401
