@@ -25,11 +25,18 @@ reference's `loss.item()`, here a spin on the update kernel's report in host-map
 per-step read is `queries_per_sec_no_host_sync`.
 
 Prints ONE JSON line on rank 0 (see the contract in the task statement); extra keys: `roofline` (dominant kernel,
-timed inside the timed region from its own dispatch packets), `cpu_baseline` (the oracle = a torch-CPU port of the
-reference's step, timed on this box's host cores on the same workload), `torch_rocm_baseline` (the same step in stock
-PyTorch-ROCm ops on this GPU: context), `kernel_us` (per-kernel average, calibration pass), `plugin_*` (the same step through
-the reference-shaped plugin API), and for N > 1 `dp_exchanges` (BOTH gradient exchanges timed in this run: the one-kernel hipIpc
-exchange and the RCCL all-reduce), `dp_exchange` (the one `value` was measured with), `rccl_ranks`, `dp_checks`.
+timed inside the timed region from its own dispatch packets), `kernel_us` (per-kernel average, calibration pass), and for N > 1
+`dp_exchange` (the exchange `value` was measured with), `rccl_ranks`, `dp_checks`.
+
+A plain run does only what that line needs: set-up, spin-up, warm-up, the calibration pass that picks the dominant kernel (whose
+timer runs inside the timed region), the K timed steps, the --dump-outputs arrays and the line.  `--full` adds every secondary
+figure, each measured after the timed region as before: `cpu_baseline` (the oracle = a torch-CPU port of the reference's step,
+timed on this box's host cores on the same workload), `torch_rocm_baseline` (the same step in stock PyTorch-ROCm ops on this GPU:
+context), `queries_per_sec_no_host_sync`, `fp32_mfma_products`, `plugin_*` (the same step through the reference-shaped plugin API),
+the device-feed rate, `eval` and `other_configs` (config 2), and for N > 1 `dp_selftest` (in front of the timed region),
+`dp_exchanges` (BOTH gradient exchanges timed in this run: the one-kernel hipIpc exchange and the RCCL all-reduce),
+`single_gpu_in_run`, `weak_scaling_efficiency`, `exchange_exposed_us`, `allreduce_us`.  `--no-cpu-baseline`, `--no-extras`,
+`--no-other-configs` and `--no-dp-selftest` leave parts of that out again.
 """
 import argparse
 import ctypes
@@ -759,10 +766,13 @@ def main():
     ap.add_argument("--attention-dtype", default="fp32", choices=["fp32", "fp16"],
                     help="config 5 only: operand type of SetRank's self-attention (fp16 = BASELINE config 5's fp16 MFMA attention, "
                          "ordering-level parity; fp32 = the 1e-5 parity path, default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary figures (plugin API, device feed)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of configs 3 / 4pair / 4lambda / 5 and the eval leg")
-    ap.add_argument("--no-dp-selftest", action="store_true", help="--gpus N > 1: skip the exchange self-test (delayed publishes) in front of the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary figure (CPU and stock-torch baselines, the loop without host reads, strict fp32, "
+                         "plugin API, device feed, eval leg, other configs; N > 1: exchange self-test, both exchanges, single-GPU step)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU and stock-torch baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary figures (plugin API, device feed)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short runs of configs 3 / 4pair / 4lambda / 5 and the eval leg")
+    ap.add_argument("--no-dp-selftest", action="store_true", help="with --full, --gpus N > 1: skip the exchange self-test (delayed publishes) in front of the timed region")
     ap.add_argument("--dp-selftest-steps", type=int, default=1000)
     ap.add_argument("--spinup-ms", type=float, default=None,
                     help="untimed steps for this many ms in front of the W warm-up steps (shader clocks settle; default 300 for config 2)")
@@ -914,7 +924,7 @@ def main():
     # publish of this rank's vector and its flags arrive that much later than its peers'), then: replicas bit-identical, every
     # status word zero.  The first run on real peers yields a verdict on the protocol, not just a throughput number.
     dp_selftest = None
-    if pg is not None and not args.no_dp_selftest:
+    if pg is not None and args.full and not args.no_dp_selftest:
         n_self = args.dp_selftest_steps
         sp, ss = params.clone(), None if state is None else state.clone()
         sa = None if aux is None else aux.clone()
@@ -1039,13 +1049,14 @@ def main():
 
     # the same loop without the per-step read of the loss (the host runs ahead of the GPU)
     dom_stream_us = None
-    if dnn and (not args.no_extras or world > 1):
+    extras_loop = args.full and (not args.no_extras or world > 1)
+    if dnn and extras_loop:
         # the dominant kernel's dispatch timestamps in THIS loop too: back-to-back launches (what a rocprofv3 average over the
         # whole process is dominated by) - the figure inside the timed region is higher because every step there starts on a
         # GPU that idled while the host read the previous loss
         _lib.check(lib.ultr_prof_set_stride(stride), "ultr_prof_set_stride")
         _lib.check(lib.ultr_prof_enable(1 << dom, 4 * (max(100, min(args.steps, 2000)) // stride + 4)), "ultr_prof_enable")
-    nosync = timed_loop(eng, max(100, min(args.steps, 2000)), False) if not args.no_extras or world > 1 else None
+    nosync = timed_loop(eng, max(100, min(args.steps, 2000)), False) if extras_loop else None
     if dnn and nosync is not None:
         tot2, cnt2 = (ctypes.c_double * 8)(), (ctypes.c_int64 * 8)()
         _lib.check(lib.ultr_prof_collect(tot2, cnt2), "ultr_prof_collect")
@@ -1057,7 +1068,7 @@ def main():
     # the same synced loop with the wide layers' products on the fp32 matrix cores (round 2's arithmetic, bit for bit): the
     # split-half fp16 products are fp32-accurate, this line is for a reader who wants the all-fp32-MFMA figure
     fp32_mfma = None
-    if dnn and world == 1 and not args.no_extras and h3_products_on():
+    if args.full and dnn and world == 1 and not args.no_extras and h3_products_on():
         keep = {k: os.environ.get(k) for k in ("ULTR_FB_H3", "ULTR_FWD_H3", "ULTR_BWD_H3", "ULTR_WG_H3")}
         try:
             for k in keep:
@@ -1098,37 +1109,41 @@ def main():
                 torch.distributed.broadcast(params, src=0, group=pg)
                 if state is not None:
                     torch.distributed.broadcast(state, src=0, group=pg)
-        # BOTH exchanges in this run: `value` above was measured with the default one; the other is timed here the same way
+        # BOTH exchanges in this run (--full): `value` above was measured with the default one; the other is timed here the same way
         main_is_peer = eng.comm is not None
-        ms_main = (t1 - t0) / args.steps
-        dp_exchanges = {}
+        rccl_ranks = torch.distributed.get_world_size(pg)  # a communicator that all-reduced `grads` in this run
         n_alt = max(100, min(args.steps, 1000))
-        rec_main = {"ms_per_step": 1e3 * elapsed / args.steps, "queries_per_sec": world * B * args.steps / elapsed,
-                    "ms_per_step_no_host_sync": None if nosync is None else 1e3 * nosync,
-                    "exchange_alone_us": exchange_alone(eng), "measured_as": "value (the timed region)"}
-        dp_exchanges[NAME_PEER if main_is_peer else NAME_RCCL] = rec_main
-        allreduce_us = rec_main["exchange_alone_us"]
-        if main_is_peer:
+        if args.full:
+            dp_exchanges = {}
+            rec_main = {"ms_per_step": 1e3 * elapsed / args.steps, "queries_per_sec": world * B * args.steps / elapsed,
+                        "ms_per_step_no_host_sync": None if nosync is None else 1e3 * nosync,
+                        "exchange_alone_us": exchange_alone(eng), "measured_as": "value (the timed region)"}
+            dp_exchanges[NAME_PEER if main_is_peer else NAME_RCCL] = rec_main
+            allreduce_us = rec_main["exchange_alone_us"]
+        if main_is_peer and (args.full or not main_ok):  # a plain run times the RCCL loop only when it has to carry `value`
             alt = engs["rccl"] = eng_cls(shape, B, L, device, algo=cfg["algo"], learning_rate=LR, max_gradient_norm=CLIP,
                                          process_group=pg, no_peer_comm=True)
             t_alt = timed_loop(alt, n_alt, True)
-            t_alt_ns = timed_loop(alt, n_alt, False)
-            dp_exchanges[NAME_RCCL] = {"ms_per_step": 1e3 * t_alt, "queries_per_sec": world * B / t_alt,
-                                       "ms_per_step_no_host_sync": 1e3 * t_alt_ns, "exchange_alone_us": exchange_alone(alt),
-                                       "measured_as": "%d steps, same loop as the timed region, right after it" % n_alt}
-            rccl_ranks = torch.distributed.get_world_size(pg)  # a communicator that all-reduced `grads` in this run
+            if args.full:
+                t_alt_ns = timed_loop(alt, n_alt, False)
+                dp_exchanges[NAME_RCCL] = {"ms_per_step": 1e3 * t_alt, "queries_per_sec": world * B / t_alt,
+                                           "ms_per_step_no_host_sync": 1e3 * t_alt_ns, "exchange_alone_us": exchange_alone(alt),
+                                           "measured_as": "%d steps, same loop as the timed region, right after it" % n_alt}
             if not main_ok:  # the peer path is broken here: the line's headline figures come from the RCCL loop
-                rec_main["measured_as"] = "the timed region - REPLICAS DIVERGED, not used for `value`"
-                dp_exchanges[NAME_RCCL]["measured_as"] += " - used for `value` (the peer exchange diverged)"
-                elapsed, nosync = t_alt * args.steps, t_alt_ns
+                if args.full:
+                    rec_main["measured_as"] = "the timed region - REPLICAS DIVERGED, not used for `value`"
+                    dp_exchanges[NAME_RCCL]["measured_as"] += " - used for `value` (the peer exchange diverged)"
+                    nosync = t_alt_ns
+                dp_checks["value_measured_with_rccl_after_divergence"] = True
+                elapsed = t_alt * args.steps
                 eng = alt
-        else:
-            rccl_ranks = torch.distributed.get_world_size(pg)
+        elif args.full and not main_is_peer:
             if not peer_ok or os.environ.get("ULTR_DP_COMM", "peer") != "peer":
                 dp_exchanges[NAME_PEER] = {"skipped": "not available / failed verification on this node"
                                            if os.environ.get("ULTR_DP_COMM", "peer") == "peer" else "ULTR_DP_COMM=pg"}
         dp_checks["replicas_bit_identical_after_run"] = replicas_identical()
         assert dp_checks["replicas_bit_identical_after_run"] or not main_ok, "data-parallel replicas diverged"
+    if pg is not None and args.full:
         # the SAME step without the exchange, in this run, on every rank at once (its own copies of the parameters: the replicas are
         # not disturbed): what one GPU does alone on this node right now - the denominator of the weak-scaling efficiency
         solo_params, solo_state = params.clone(), None if state is None else state.clone()
@@ -1152,7 +1167,7 @@ def main():
         solo_ms = 1e3 * float(tsolo.item())
 
     e2e, plugin = None, None
-    if world == 1 and not args.no_extras and light:
+    if args.full and world == 1 and not args.no_extras and light:
         # end-to-end variant (the reference's own step_time definition, main.py:153-156: get_batch + train): the
         # dataset is resident in HBM and clicks are simulated on the device (ultr_click_batch)
         nq = 20000
@@ -1186,14 +1201,14 @@ def main():
         e2e = B * n3 / (time.perf_counter() - t4)
         plugin = plugin_rates(cfg, pool, device, args.steps)
     trb = None
-    if world == 1 and not args.no_extras and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_extras and not args.no_cpu_baseline:
         try:
             trb = torch_rocm_baseline(cfg, pool, params0, device)
         except Exception as ex:  # a baseline must never take the headline down
             trb = {"value": None, "error": repr(ex)}
 
     other, evalleg = None, None
-    if world == 1 and light and not args.no_other_configs:
+    if args.full and world == 1 and light and not args.no_other_configs:
         # the other BASELINE configs and the validation path on the SAME line: short synced runs
         evalleg = eval_leg(cfg, device, lib, params0)
         other = {}
@@ -1262,10 +1277,11 @@ def main():
         dp_head = {}
         if pg is not None:  # in front of the long strings: a record that keeps only the head of the line still shows what exchanged
             dp_head = {"dp_exchange": NAME_PEER if eng.comm is not None else NAME_RCCL,  # the one `value` was measured with
-                       "rccl_ranks": rccl_ranks,  # world size of the RCCL communicator that all-reduced `grads` in THIS run
-                       "weak_scaling_efficiency": (world * B * args.steps / elapsed) / (world * B / (1e-3 * solo_ms)),
-                       "exchange_exposed_us": 1e3 * (1e3 * elapsed / args.steps - solo_ms),
-                       "dp_selftest": dp_selftest}
+                       "rccl_ranks": rccl_ranks}  # world size of the RCCL communicator that all-reduced `grads` in THIS run
+            if args.full:
+                dp_head.update({"weak_scaling_efficiency": (world * B * args.steps / elapsed) / (world * B / (1e-3 * solo_ms)),
+                                "exchange_exposed_us": 1e3 * (1e3 * elapsed / args.steps - solo_ms),
+                                "dp_selftest": dp_selftest})
         out = {
             "metric": "queries/sec (training step)", "value": world * B * args.steps / elapsed, "unit": "queries/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
@@ -1317,9 +1333,10 @@ def main():
             out["queries_per_sec_no_host_sync"] = B * world / nosync
             out["ms_per_step_no_host_sync"] = 1e3 * nosync
         if pg is not None:
+            out["dp_checks"] = dp_checks
+        if pg is not None and args.full:
             out["dp_exchanges"] = dp_exchanges
             out["allreduce_us"] = allreduce_us
-            out["dp_checks"] = dp_checks
             out["single_gpu_in_run"] = {"ms_per_step": solo_ms, "queries_per_sec": B / (1e-3 * solo_ms),
                                         "what": "the same synced step WITHOUT the exchange on every rank at once, in this run (slowest rank)"}
         if trb is not None:
@@ -1329,7 +1346,7 @@ def main():
         if plugin is not None:
             out["plugin_queries_per_sec"] = plugin[0]  # IPWrank.train(host numpy feed): marshal + PCIe + .item() + print
             out["plugin_device_feed_queries_per_sec"] = plugin[1]  # IPWrank.train(DeviceClickFeed batch)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, pool, params0)
         if outputs is not None:
             out["dump_outputs"] = write_outputs(args.dump_outputs, outputs)

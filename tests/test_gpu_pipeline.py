@@ -144,8 +144,31 @@ def test_driver_matches_the_reference_run(tmp_path, monkeypatch):
             np.testing.assert_allclose(sd[k], d["save%d_%s" % (i, k)], rtol=5e-3, atol=5e-4, err_msg=k)
 
 
+def test_bench_plain_run_prints_only_the_headline():
+    """A plain `python bench.py --gpus 1 --steps N --warmup W` times the N steps and prints the headline line without measuring any
+    secondary figure: those (baselines, other precisions and configs, the eval leg, the plugin API) are `--full`'s."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    env.pop("RANK", None), env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "queries/sec (training step)" and d["unit"] == "queries/sec" and d["higher_is_better"] is True
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 256 / (1e-3 * d["ms_per_step"])) <= 1e-6 * d["value"] and np.isfinite(d["final_loss"])
+    assert d["dtype"].startswith("f32") and d["roofline"]["launches_timed"] >= 1
+    for key in ("cpu_baseline", "torch_rocm_baseline", "queries_per_sec_no_host_sync", "fp32_mfma_products", "other_configs", "eval",
+                "plugin_queries_per_sec", "end_to_end_queries_per_sec_device_feed"):
+        assert key not in d, key
+
+
 def test_bench_multi_rank_logic_on_one_gpu():
-    """`python bench.py --gpus 2` launches its own ranks and prints ONE JSON line carrying both gradient exchanges and the
+    """`python bench.py --gpus 2 --full` launches its own ranks and prints ONE JSON line carrying both gradient exchanges and the
     checks - exercised here with both ranks on cuda:0 over gloo (ULTR_BENCH_SHARE_GPU=1: a test of bench.py's N > 1 logic, the
     same code the driver's scaling run takes; not a measurement)."""
     import json
@@ -153,8 +176,8 @@ def test_bench_multi_rank_logic_on_one_gpu():
     import sys
     env = dict(os.environ, ULTR_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5", "--no-cpu-baseline",
-                        "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5", "--full",
+                        "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
