@@ -540,6 +540,39 @@ int ultr_dbgd_noise_args(const ultr_dbgd_args* a, void* stream);
 int ultr_dbgd_interleave_args(const ultr_dbgd_args* a, void* stream);
 int ultr_dbgd_grad_args(const ultr_dbgd_args* a, void* stream);
 
+/* ---- NSGD: DBGD / MGD with null-space exploration (ultr_nsgd.hip; additive within ABI 8) ----------------------------------
+ * Counterpart of NSGD.train (nsgd.py): MGD's step with its noise launch replaced and one launch added.  `dbgd` points at the
+ * step's ultr_dbgd_args (desc, n_params, n_rankers R, seed, step, params, noise, cand_params, cand_stride, noise_rate,
+ * need_interleave, batch, winners, ndcg); memory [R, n_params] holds the last losing directions (0 outside the Linear entries).
+ * A Linear tensor t is a weight [out, in] or a bias [out] of the flat DNN vector.  A step, on one stream:
+ *   ultr_nsgd_noise_args   noise [R, P]: per Linear tensor t and ranker r, u_{t,r} = z / sqrt(max(sum z^2, 1e-12)) with
+ *                          z = P_t z_{t,r}, z_{t,r} Philox normals (Box-Muller, own tag) and P_t the orthogonal projection onto the
+ *                          complement of memory's rows restricted to t (exactly-zero rows are empty slots; rows the fp64 pivoted
+ *                          Cholesky of their Gram matrix finds dependent are dropped); u = 0 when the kept rows span t; a bias of
+ *                          one entry skips the projection (+-1).  0 on the LayerNorm entries.  cand_params [R, cand_stride] =
+ *                          params + noise_rate * noise.  Four launches (partial dot products; their fixed-order reduction and the
+ *                          solve, one workgroup per tensor; projection and partial sums of squares; normalization and the
+ *                          candidates): a step is a pure function of (seed, step, params, memory), independent of the launch
+ *                          geometry.  Optional: normals_in [R, P] replaces the Philox draw; unit_noise_in [R, P] replaces the whole
+ *                          law (noise = unit_noise_in on the Linear entries; one launch).
+ *   then DBGD's forwards, ultr_dbgd_interleave_args / ultr_ndcg, ultr_dbgd_grad_args and ultr_apply_update, unchanged.
+ *   ultr_nsgd_memory_args  after the winners (need_interleave) or the R + 1 NDCGs (without): memory row r = noise_r on the Linear
+ *                          entries if ranker r + 1 lost, else 0.  Lost: with interleaving, winners[b, r + 1] = 0 for every list b;
+ *                          without, the reference's batch-level winners w = ceil(ndcg_a - ndcg_0) / (sum + 1e-9) sum to 0 (then
+ *                          every row stores its noise, else every row is zeroed).
+ * ws: ultr_nsgd_workspace_bytes(desc, n_rankers) bytes, 8-byte aligned.  No atomics.
+ * ULTR_E_BADARG: as ultr_dbgd_noise_args, or a missing memory / ws. */
+typedef struct ultr_nsgd_args {
+  const ultr_dbgd_args* dbgd;
+  float* memory;
+  const float* normals_in;
+  const float* unit_noise_in;
+  void* ws;
+} ultr_nsgd_args;
+int64_t ultr_nsgd_workspace_bytes(const ultr_dnn_desc* desc, int32_t n_rankers);
+int ultr_nsgd_noise_args(const ultr_nsgd_args* a, void* stream);
+int ultr_nsgd_memory_args(const ultr_nsgd_args* a, void* stream);
+
 /* ---- e: data-parallel gradient exchange over xGMI -----------------------------
  * No reference counterpart: the reference is single-process.  One process per GPU; queries shard across ranks,
  * parameters / optimizer / EM state are replicated, and ONE sum per step of the flat vector

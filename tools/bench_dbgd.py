@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Training-step time of DBGD (one candidate) and MGD (four candidates) against PDGD's step, at BASELINE config 2's shape (136-d,
+"""Training-step time of DBGD (one candidate), MGD and NSGD (four candidates each) against PDGD's step, at BASELINE config 2's shape (136-d,
 DNN[256,256], B 256, M 10) and the reference's online example's model (136-d, DNN[512,256,128], B 256, M 10), with the default
 'Stochastic' multileave and PBM clicks.
 
-The three engines of one shape live in one process and are timed in alternating blocks of --block steps (device events around each
+The four engines of one shape live in one process and are timed in alternating blocks of --block steps (device events around each
 block, steps queued back to back), so clock and thermal drift hit all alike.  Then the device online loop
-(input_layer.DeviceStochasticOnlineSimulationFeed get_batch + DBGD.train / MGD.train) per batch: device events around --online batches,
+(input_layer.DeviceStochasticOnlineSimulationFeed get_batch + DBGD.train / MGD.train / NSGD.train) per batch: device events around --online batches,
 one synchronise at the end.  Prints one JSON line.
 
     python tools/bench_dbgd.py [--blocks 20] [--block 50] [--warmup 100] [--online 200] [--out profiles/dbgd_bench.json]
@@ -47,7 +47,7 @@ def time_shape(F, hidden, B, L, args):
     p0 = O.init_params(F, hidden, seed=2)
     exam, n_exam, cprob = _click_tables(dev)
     runs = {}
-    for name, R in (("pdgd", None), ("dbgd", 1), ("mgd", 4)):
+    for name, R in (("pdgd", None), ("dbgd", 1), ("mgd", 4), ("nsgd", 4)):
         p, st = torch.tensor(p0, device=dev), torch.zeros(p0.shape[0], device=dev)
         if R is None:
             eng = engine.StepEngine(shape, B, L, dev, algo="pdgd", l2_loss=0.005, max_gradient_norm=1.0, cutoff=L)
@@ -56,8 +56,9 @@ def time_shape(F, hidden, B, L, args):
                 eng.train_step(p, st, f, feats.shape[0], i, yy)
         else:
             # a small learning rate keeps the weights where the timed kernels run at any step count
-            eng = engine.DbgdEngine(shape, B, L, L, R, dev, noise_rate=0.01, learning_rate=0.01, click_model=0, exam=exam,
-                                    n_exam=n_exam, cprob=cprob, seed=1)
+            cls = engine.NsgdEngine if name == "nsgd" else engine.DbgdEngine
+            eng = cls(shape, B, L, L, R, dev, noise_rate=0.01, learning_rate=0.01, click_model=0, exam=exam, n_exam=n_exam,
+                      cprob=cprob, seed=1)
 
             def step(eng=eng, p=p, st=st):
                 eng.train_step(p, st, f, feats.shape[0], i, yy)
@@ -82,6 +83,7 @@ def time_shape(F, hidden, B, L, args):
         res[a + "_step_us"] = dict(median=float(np.median(t)), min=float(np.min(t)), max=float(np.max(t)))
     res["dbgd_over_pdgd"] = res["dbgd_step_us"]["median"] / res["pdgd_step_us"]["median"]
     res["mgd_over_pdgd"] = res["mgd_step_us"]["median"] / res["pdgd_step_us"]["median"]
+    res["nsgd_minus_mgd_us"] = res["nsgd_step_us"]["median"] - res["mgd_step_us"]["median"]
     return res
 
 
@@ -137,7 +139,7 @@ def main():
         res[name] = time_shape(*SHAPES[name], args)
     if args.online > 0:
         for name in args.shapes.split(","):
-            for algo_name in ("PDGD", "DBGD", "MGD"):
+            for algo_name in ("PDGD", "DBGD", "MGD", "NSGD"):
                 res["device_online_%s_%s" % (name, algo_name.lower())] = time_device_online(name, algo_name, args.online)
     line = json.dumps(res)
     print(line)

@@ -69,6 +69,10 @@ class DbgdArgs(ctypes.Structure):  # ultr_dbgd_args (ultr_dbgd_noise_args / ultr
 DBGD_MAX_M, DBGD_MAX_RANKERS = 256, 16  # include/ultr_hip.h: ULTR_DBGD_MAX_M, ULTR_DBGD_MAX_RANKERS (R + 1)
 
 
+class NsgdArgs(ctypes.Structure):  # ultr_nsgd_args (ultr_nsgd_noise_args / ultr_nsgd_memory_args)
+    _fields_ = [("dbgd", ctypes.POINTER(DbgdArgs)), ("memory", c_vp), ("normals_in", c_vp), ("unit_noise_in", c_vp), ("ws", c_vp)]
+
+
 class SetRankDesc(ctypes.Structure):
     _fields_ = [("feature_size", c_i32), ("d_model", c_i32), ("num_heads", c_i32), ("num_layers", c_i32), ("dff", c_i32),
                 ("attention_dtype", c_i32), ("flags", c_i32)]
@@ -131,6 +135,9 @@ SIGNATURES = {
     "ultr_dbgd_noise_args": (c_i32, [c_vp, c_vp]),
     "ultr_dbgd_interleave_args": (c_i32, [c_vp, c_vp]),
     "ultr_dbgd_grad_args": (c_i32, [c_vp, c_vp]),
+    "ultr_nsgd_workspace_bytes": (c_i64, [ctypes.POINTER(DnnDesc), c_i32]),
+    "ultr_nsgd_noise_args": (c_i32, [c_vp, c_vp]),
+    "ultr_nsgd_memory_args": (c_i32, [c_vp, c_vp]),
     "ultr_comm_create": (c_i32, [c_i32, c_i32, c_i64, ctypes.POINTER(c_vp)]),
     "ultr_comm_export": (c_i32, [c_vp, c_vp]),
     "ultr_comm_import": (c_i32, [c_vp, c_i32, c_vp]),

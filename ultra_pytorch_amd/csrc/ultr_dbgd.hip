@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "../../include/ultr_hip.h"
+#include "ultr_dbgd.h"
 #include "ultr_device.h"
 #include "ultr_feed.h"
 #include "ultr_plan.h"
@@ -31,28 +32,11 @@
 #define DBGD_SHUFFLE_TAG 0x0DB6D003u
 #define DBGD_CLICK_TAG 0x0DB6D004u
 #define DBGD_NORM_EPS 1e-12f  // F.normalize's eps
-#define DBGD_TILE_COLS 16     // weight columns per workgroup of dbgd_noise_kernel
 
-struct DbgdLayout {
-  int nl;
-  int K[ULTR_MAXL], M[ULTR_MAXL];
-  int64_t off_ln[ULTR_MAXL], off_w[ULTR_MAXL], off_b[ULTR_MAXL];
-  int tiles[ULTR_MAXL];  // workgroups of layer j: ceil(K_j / 16) column tiles + one for the bias and the LayerNorm entries
-  int64_t P;
-};
-
-__device__ __forceinline__ Philox dbgd_rng(uint64_t seed, uint64_t step) {
-  return Philox{(uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step};
-}
-
-// the standard normal of element e of ranker r: Box-Muller on two uniforms of one Philox draw (u1 in (0, 1], u2 in [0, 1))
+// the standard normal of element e of ranker r (ultr_dbgd.h)
 __device__ __forceinline__ float dbgd_normal(const ultr_dbgd_args& a, const Philox& rng, int r, int64_t e) {
   if (a.noise_in != nullptr) return a.noise_in[(int64_t)r * a.n_params + e];
-  uint32_t c[4] = {(uint32_t)e, (uint32_t)r, 0u, DBGD_NOISE_TAG};
-  rng(c);
-  const float u1 = (float)((c[0] >> 8) + 1u) * (1.0f / 16777216.0f);
-  const float u2 = u01(c[1]);
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+  return philox_normal(rng, r, e, DBGD_NOISE_TAG);
 }
 
 // grid (sum_j tiles[j], R), 1024 threads.  A column tile of W_j [M_j, K_j]: 16 columns (lane & 15), 64 row phases (4 per wave), rows
@@ -312,30 +296,6 @@ __global__ __launch_bounds__(256) void dbgd_grad_kernel(ultr_dbgd_args a, int64_
   const float sq = wave_sum(gg);
   const int64_t part = (int64_t)blockIdx.x * 4 + w;
   if (lane == 0 && part < (total + 63) / 64) static_cast<float*>(a.bwd_ws)[part] = sq;
-}
-
-static bool dbgd_layout(const ultr_dbgd_args* a, DbgdLayout* ly) {
-  DnnPlan p;
-  if (!a->desc || !ultr_make_dnn_plan(a->desc, 0, &p)) return false;
-  memset(ly, 0, sizeof(*ly));
-  ly->nl = p.nl;
-  ly->P = p.P;
-  for (int j = 0; j < p.nl; ++j) {
-    ly->K[j] = p.K[j];
-    ly->M[j] = p.M[j];
-    ly->off_ln[j] = p.off_lnw[j];
-    ly->off_w[j] = p.off_w[j];
-    ly->off_b[j] = p.off_b[j];
-    ly->tiles[j] = (p.K[j] + DBGD_TILE_COLS - 1) / DBGD_TILE_COLS + 1;
-    if (p.off_lnb[j] != p.off_lnw[j] + p.K[j]) return false;  // gamma | beta adjacent (ranking_model/dnn.py)
-  }
-  return ly->P == a->n_params;
-}
-
-static bool dbgd_shape_ok(const ultr_dbgd_args* a) {
-  return a && a->n_rankers >= 1 && a->n_rankers + 1 <= ULTR_DBGD_MAX_RANKERS && a->batch > 0 && a->max_candidates > 0 &&
-         a->max_candidates <= ULTR_DBGD_MAX_M && a->rank_list_size > 0 && a->rank_list_size <= a->max_candidates &&
-         a->n_params > 0;
 }
 
 extern "C" int ultr_dbgd_noise_args(const ultr_dbgd_args* a, void* stream) {

@@ -574,7 +574,7 @@ class DbgdEngine:
         a.teams = teams.data_ptr() if teams is not None else None
         a.clicks = clicks.data_ptr() if clicks is not None else None
         a.docids, a.labels, a.n_docs = docids.data_ptr(), labels.data_ptr(), int(n_docs)
-        _lib.check(lib.ultr_dbgd_noise_args(self._aref, st), "ultr_dbgd_noise_args")
+        self._launch_noise(st)
         fp = features.data_ptr() if n_docs > 0 else None
         ids = docids.data_ptr()
         desc = ctypes.byref(shape.desc)
@@ -595,6 +595,7 @@ class DbgdEngine:
             for r in range(R + 1):
                 _lib.check(ndcg(self.scores[r].data_ptr(), labels.data_ptr(), None, int(n_docs), B, self.rls, self._topn, 1,
                                 self.ndcg.data_ptr() + 4 * r, None, None, self.ndcg_ws.data_ptr(), st), "ultr_ndcg")
+        self._after_winners(st)
         _lib.check(lib.ultr_dbgd_grad_args(self._aref, st), "ultr_dbgd_grad_args")
         self._seq = (self._seq % 0xFFFFFFFF) + 1
         self.udesc.seq = self._seq
@@ -602,3 +603,57 @@ class DbgdEngine:
                                          state.data_ptr() if state is not None else None, self.grads.data_ptr(), None,
                                          self.bwd_ws.data_ptr(), self.scalars.data_ptr(), st), "ultr_apply_update")
         return self.scalars
+
+    def _launch_noise(self, st):
+        """noise [R, P] and the candidate vectors (args.noise_in: the injected normals, or NULL)."""
+        _lib.check(self.lib.ultr_dbgd_noise_args(self._aref, st), "ultr_dbgd_noise_args")
+
+    def _after_winners(self, st):
+        """Runs once the winners (or the R + 1 NDCGs) are on the stream, before the gradient: nothing for DBGD / MGD."""
+
+
+class NsgdEngine(DbgdEngine):
+    """One NSGD step (learning_algorithm.NSGD): DbgdEngine's step with the noise drawn from the null space of `memory` and the memory
+    rewritten after the winners (csrc/ultr_nsgd.hip):
+
+        ultr_nsgd_noise_args -> R + 1 x ultr_dnn_forward -> [ultr_dbgd_interleave_args] -> ultr_ndcg -> ultr_nsgd_memory_args
+        -> ultr_dbgd_grad_args -> ultr_apply_update (ULTR_ALGO_DBGD)
+
+    memory [R, P] (device, fp32) belongs to the caller (the algorithm: it outlives this per-shape engine) and every step reads and
+    rewrites it in place."""
+
+    def __init__(self, shape, batch, max_candidates, rank_list_size, n_rankers, device, memory=None, **kw):
+        super().__init__(shape, batch, max_candidates, rank_list_size, n_rankers, device, **kw)
+        R, P = self.R, self.P
+        if memory is None:
+            memory = _f32(R * P, device, zero=True).view(R, P)
+        if (tuple(memory.shape) != (R, P) or memory.dtype != torch.float32 or not memory.is_contiguous()
+                or memory.device != self.noise.device):
+            raise ValueError("NSGD memory must be a contiguous float32 [%d, %d] tensor on %s" % (R, P, self.noise.device))
+        self.memory = memory
+        nb = int(shape.lib.ultr_nsgd_workspace_bytes(ctypes.byref(shape.desc), R))
+        if nb < 0:
+            raise ValueError("ultr_nsgd_workspace_bytes refused the model (%d candidate rankers)" % R)
+        self.nsgd_ws = torch.zeros(max((nb + 7) // 8, 1), dtype=torch.float64, device=device)
+        n = self.nargs = _lib.NsgdArgs()
+        n.dbgd = ctypes.pointer(self.args)
+        n.memory, n.ws = memory.data_ptr(), self.nsgd_ws.data_ptr()
+        self._nref = ctypes.byref(n)
+        self._unit_noise_in = None
+
+    def train_step(self, params, state, features, n_docs, docids, labels, noise_in=None, unit_noise_in=None, **kw):
+        """DbgdEngine.train_step; noise_in [R, P] replaces the Philox normals, unit_noise_in [R, P] the whole noise law (tests)."""
+        self._unit_noise_in = unit_noise_in
+        try:
+            return super().train_step(params, state, features, n_docs, docids, labels, noise_in=noise_in, **kw)
+        finally:
+            self._unit_noise_in = None
+
+    def _launch_noise(self, st):
+        n, a = self.nargs, self.args
+        n.normals_in, a.noise_in = a.noise_in, None
+        n.unit_noise_in = self._unit_noise_in.data_ptr() if self._unit_noise_in is not None else None
+        _lib.check(self.lib.ultr_nsgd_noise_args(self._nref, st), "ultr_nsgd_noise_args")
+
+    def _after_winners(self, st):
+        _lib.check(self.lib.ultr_nsgd_memory_args(self._nref, st), "ultr_nsgd_memory_args")

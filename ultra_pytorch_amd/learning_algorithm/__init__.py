@@ -11,3 +11,4 @@ from .regression_EM import RegressionEM  # noqa: F401
 from .prs_rank import PRSrank  # noqa: F401
 from .pdgd import PDGD  # noqa: F401
 from .dbgd import DBGD, MGD  # noqa: F401
+from .nsgd import NSGD  # noqa: F401

@@ -76,7 +76,7 @@ class DBGD(BaseAlgorithm):
         key = (B, M)
         eng = self._train_engines.get(key)
         if eng is None:
-            eng = self._train_engines[key] = engine.DbgdEngine(
+            eng = self._train_engines[key] = self._make_engine(
                 self.model.shape, B, M, min(int(self.rank_list_size), M), self.n_rankers, self.cuda,
                 need_interleave=bool(self.hparams.need_interleave), stochastic=self.interleaving_strategy == "Stochastic",
                 tau=float(self.hparams.tau), noise_rate=float(self.hparams.learning_rate), learning_rate=self.learning_rate,
@@ -88,6 +88,9 @@ class DBGD(BaseAlgorithm):
         else:
             self._train_engines.move_to_end(key)
         return eng
+
+    def _make_engine(self, *args, **kw):
+        return engine.DbgdEngine(*args, **kw)
 
     def train(self, input_feed):
         """dbgd.py:125-187: every list of max_candidate_num positions (a device feed: its own length); the loss is
