@@ -573,6 +573,40 @@ int64_t ultr_nsgd_workspace_bytes(const ultr_dnn_desc* desc, int32_t n_rankers);
 int ultr_nsgd_noise_args(const ultr_nsgd_args* a, void* stream);
 int ultr_nsgd_memory_args(const ultr_nsgd_args* a, void* stream);
 
+/* ---- propensity estimation from randomized click sessions (ultr_propensity.hip; additive within ABI 8) ------------------------
+ * Counterpart of the session loop of RandomizedPropensityEstimator.estimateParametersFromModel (propensity_estimator.py:95-118):
+ * n_sessions times, pick a label list uniformly, shuffle it uniformly, sample clicks on the shuffled list with the click model
+ * (no redraw of click-less lists), and add every click to click_count[len - 1][position].  The table is ADDED to, never cleared:
+ * the caller zeroes it once and may split the sessions over any number of calls.
+ *   labels  [n_queries][lmax] relevance, row q valid in [0, lengths[q]);  lengths [n_queries], 0 .. lmax
+ *   exam_prob / n_exam / click_prob / n_rel / click_model: as ultr_click_args (ULTR_CLICK_UBM: dense [n_exam][n_exam] image)
+ *   click_count [lmax][lmax] 64-bit counters, row = list length - 1, column = position
+ * Session s (first_session <= s < first_session + n_sessions) is a pure function of (seed, s): Philox under ultr_click_batch's key
+ * with step = 0, counters (lo32(s), hi32(s), g, tag).  Query: q = min((int64)((double)u01(word 0 of (.., 0xFFFFFFFF, query tag)) *
+ * n_queries), n_queries - 1), n = lengths[q].  Shuffle: position l < n gets the 32-bit word l & 3 of (.., l >> 2, shuffle tag) as its
+ * key; the label at rank r is the one whose key is the r-th largest (ties by index).  Clicks: the uniform of rank r is u01(word
+ * r & 3 of (.., r >> 2, click tag)), the decision ultr_click_batch's for a list of n positions.  A session with n == 0 counts nothing.
+ * Persistent workgroups accumulate in a 32-bit LDS histogram and flush once with 64-bit integer atomic adds: the table is
+ * independent of the launch geometry and of the order of the adds (bit-reproducible).  The parity with the reference's Python
+ * random stream is distributional.
+ * ULTR_E_BADARG: a missing pointer, n_queries / lmax / n_exam / n_rel <= 0, n_sessions < 0, an unknown click model, ULTR_CLICK_UBM
+ * with n_exam < 2.  ULTR_E_UNSUPPORTED: lmax > ULTR_PROPENSITY_MAX_L.  Neither launches anything; n_sessions == 0 is a no-op. */
+#define ULTR_PROPENSITY_MAX_L 128
+typedef struct ultr_propensity_args {
+  const float* labels;
+  const int32_t* lengths;
+  int64_t n_queries;
+  int32_t lmax;
+  const float* exam_prob;
+  int32_t n_exam;
+  const float* click_prob;
+  int32_t n_rel, click_model;
+  uint64_t seed, first_session;
+  int64_t n_sessions;
+  unsigned long long* click_count;
+} ultr_propensity_args;
+int ultr_propensity_count(const ultr_propensity_args* a, void* stream);
+
 /* ---- e: data-parallel gradient exchange over xGMI -----------------------------
  * No reference counterpart: the reference is single-process.  One process per GPU; queries shard across ranks,
  * parameters / optimizer / EM state are replicated, and ONE sum per step of the flat vector

@@ -73,6 +73,15 @@ class NsgdArgs(ctypes.Structure):  # ultr_nsgd_args (ultr_nsgd_noise_args / ultr
     _fields_ = [("dbgd", ctypes.POINTER(DbgdArgs)), ("memory", c_vp), ("normals_in", c_vp), ("unit_noise_in", c_vp), ("ws", c_vp)]
 
 
+class PropensityArgs(ctypes.Structure):  # ultr_propensity_args (ultr_propensity_count)
+    _fields_ = [("labels", c_vp), ("lengths", c_vp), ("n_queries", c_i64), ("lmax", c_i32), ("exam_prob", c_vp), ("n_exam", c_i32),
+                ("click_prob", c_vp), ("n_rel", c_i32), ("click_model", c_i32), ("seed", ctypes.c_uint64),
+                ("first_session", ctypes.c_uint64), ("n_sessions", c_i64), ("click_count", c_vp)]
+
+
+PROPENSITY_MAX_L = 128  # include/ultr_hip.h: ULTR_PROPENSITY_MAX_L
+
+
 class SetRankDesc(ctypes.Structure):
     _fields_ = [("feature_size", c_i32), ("d_model", c_i32), ("num_heads", c_i32), ("num_layers", c_i32), ("dff", c_i32),
                 ("attention_dtype", c_i32), ("flags", c_i32)]
@@ -138,6 +147,7 @@ SIGNATURES = {
     "ultr_nsgd_workspace_bytes": (c_i64, [ctypes.POINTER(DnnDesc), c_i32]),
     "ultr_nsgd_noise_args": (c_i32, [c_vp, c_vp]),
     "ultr_nsgd_memory_args": (c_i32, [c_vp, c_vp]),
+    "ultr_propensity_count": (c_i32, [c_vp, c_vp]),
     "ultr_comm_create": (c_i32, [c_i32, c_i32, c_i64, ctypes.POINTER(c_vp)]),
     "ultr_comm_export": (c_i32, [c_vp, c_vp]),
     "ultr_comm_import": (c_i32, [c_vp, c_i32, c_vp]),

@@ -1,12 +1,34 @@
 // ultr_feed.h - the click draw of ultr_feed.hip as a device function: its own launch (click_batch_kernel) or a rider on the update
 // launch of the step in front of it (update_tiled_kernel: extra workgroups behind the update's own - ultr_feed_train_step).
-// click_decide, its per-position PBM / cascade / UBM decisions, is shared with the online re-rank (online_rerank_kernel, ultr_online.hip).
+// click_decide, its per-position PBM / cascade / UBM decisions, is shared with the online re-rank (online_rerank_kernel, ultr_online.hip)
+// and the propensity estimator's session loop (propensity_count_kernel, ultr_propensity.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ultr_hip.h"
 #include "ultr_device.h"
+
+// Philox counter word 3 of the draws that share click_draw's key: the query pick, the click uniforms, and the per-session shuffle keys
+// of the propensity estimator (ultr_propensity.hip)
+#define ULTR_QUERY_TAG 0x51ED270Bu
+#define ULTR_CLICK_TAG 0x2545F491u
+#define ULTR_SHUFFLE_TAG 0x53485546u
+
+// click probability of a relevance label: click_prob[min(max((int)y, 0), n_rel - 1)]
+__device__ __forceinline__ float click_prob_of(const float* __restrict__ cprob, int n_rel, float y) {
+  const int lab = y > 0.f ? (int)y : 0;
+  return cprob[lab < n_rel ? lab : n_rel - 1];
+}
+// user-browsing examination probability of `rank` at distance dist = rank - last click (last click -1 before the first one) in the dense
+// [n_exam][n_exam] image of the triangular table (row = rank, column = distance - 1); getExamProb, click_models.py:175-186: beyond the
+// table the LAST row serves - the last entry when no click precedes the position, else column distance - 1 saturating at the
+// second-to-last
+__device__ __forceinline__ float ubm_exam_prob(const float* __restrict__ exam, int n_exam, int rank, int dist) {
+  if (rank < n_exam) return exam[rank * n_exam + dist - 1];
+  if (dist > rank) return exam[(n_exam - 1) * n_exam + n_exam - 1];
+  return exam[(n_exam - 1) * n_exam + (dist < n_exam - 1 ? dist - 1 : (n_exam >= 2 ? n_exam - 2 : 0))];
+}
 
 // The click decision of position l = l0 + lane (in: l < L) of one chunk of 64 positions of an L-position list, from its label y and its
 // uniform u: PBM, cascade or UBM as ultr_click_batch draws them.  clicked_before (cascade: a click in an earlier chunk) and last_click
@@ -17,8 +39,7 @@ __device__ __forceinline__ float click_decide(int model, const float* __restrict
   const int l = l0 + lane;
   float ck = 0.f;
   if (in) {
-    const int lab = y > 0.f ? (int)y : 0;
-    const float cp = cprob[lab < n_rel ? lab : n_rel - 1];
+    const float cp = click_prob_of(cprob, n_rel, y);
     if (model == ULTR_CLICK_UBM) {
       // click iff u < exam x cp: the walk below compares u / cp with the examination probability; cp == 0 (a relevance level that
       // is never clicked) gives +inf or NaN, and both compare false against every probability - no click, as intended
@@ -28,18 +49,12 @@ __device__ __forceinline__ float click_decide(int model, const float* __restrict
     }
   }
   if (model == ULTR_CLICK_UBM) {
-    // exam = dense [n_exam][n_exam] image of the triangular table (row = rank, column = distance - 1); getExamProb,
-    // click_models.py:175-186: beyond the table the LAST row serves - the last entry when no click precedes the position,
-    // else column distance - 1 saturating at the second-to-last
     const float ratio = ck;
     ck = 0.f;
     const int hi = (L - l0) < 64 ? (L - l0) : 64;
     for (int k = 0; k < hi; ++k) {
-      const int rank = l0 + k, dist = rank - last_click;
-      float ex;
-      if (rank < n_exam) ex = exam[rank * n_exam + dist - 1];
-      else if (dist > rank) ex = exam[(n_exam - 1) * n_exam + n_exam - 1];
-      else ex = exam[(n_exam - 1) * n_exam + (dist < n_exam - 1 ? dist - 1 : (n_exam >= 2 ? n_exam - 2 : 0))];
+      const int rank = l0 + k;
+      const float ex = ubm_exam_prob(exam, n_exam, rank, rank - last_click);
       const float rk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ratio), k));
       const bool hit = rk < ex;
       if (hit) last_click = rank;
@@ -73,7 +88,7 @@ __device__ __forceinline__ void click_draw(const ultr_click_args& ca, int block)
   Philox rng{(uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step};
   int64_t q = 0;
   for (int attempt = 0; attempt < max_tries; ++attempt) {
-    uint32_t c[4] = {(uint32_t)b, (uint32_t)attempt, 0xFFFFFFFFu, 0x51ED270Bu};
+    uint32_t c[4] = {(uint32_t)b, (uint32_t)attempt, 0xFFFFFFFFu, ULTR_QUERY_TAG};
     rng(c);
     q = (int64_t)((double)u01(c[0]) * (double)n_queries);  // uniform query pick (click_simulation_feed.py:126)
     if (q >= n_queries) q = n_queries - 1;
@@ -92,7 +107,7 @@ __device__ __forceinline__ void click_draw(const ultr_click_args& ca, int block)
           id = d;
           y = rel[q * Lmax + l];
         }
-        uint32_t r[4] = {(uint32_t)b, (uint32_t)attempt, (uint32_t)(l >> 2), 0x2545F491u};
+        uint32_t r[4] = {(uint32_t)b, (uint32_t)attempt, (uint32_t)(l >> 2), ULTR_CLICK_TAG};
         rng(r);
         u = u01(r[l & 3]);
       }

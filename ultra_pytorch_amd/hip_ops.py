@@ -333,3 +333,19 @@ def ndcg(scores, labels, docids, n_docs, B, L, topn, ndcg_out, ndcg_ws, order_ou
     arr = (ctypes.c_int32 * len(topn))(*[int(t) for t in topn])
     check(_lib.load().ultr_ndcg(_p(scores), _p(labels), _p(docids), int(n_docs), int(B), int(L), arr, len(topn),
                                 _p(ndcg_out), _p(order_out), _p(masked_out), _p(ndcg_ws), _stream()), "ultr_ndcg")
+
+
+def propensity_count(labels, lengths, exam, n_exam, cprob, click_model, seed, first_session, n_sessions, click_count):
+    """n_sessions randomized click sessions (ultr_propensity_count) ADDED to click_count [lmax, lmax] int64: labels [n_queries, lmax]
+    float32 with row q valid in [0, lengths[q]), lengths [n_queries] int32, exam / cprob as the device feeds upload them."""
+    _req(labels, torch.float32, "labels"), _req(lengths, torch.int32, "lengths"), _req(exam, torch.float32, "exam")
+    _req(cprob, torch.float32, "cprob"), _req(click_count, torch.int64, "click_count")
+    n_queries, lmax = labels.shape
+    if lengths.numel() != n_queries or tuple(click_count.shape) != (lmax, lmax):
+        raise ValueError("propensity_count: labels [n_queries, lmax] needs lengths [n_queries] and click_count [lmax, lmax]")
+    a = _lib.PropensityArgs()
+    a.labels, a.lengths, a.n_queries, a.lmax = labels.data_ptr(), lengths.data_ptr(), int(n_queries), int(lmax)
+    a.exam_prob, a.n_exam, a.click_prob, a.n_rel = exam.data_ptr(), int(n_exam), cprob.data_ptr(), int(cprob.numel())
+    a.click_model, a.seed, a.first_session, a.n_sessions = int(click_model), int(seed), int(first_session), int(n_sessions)
+    a.click_count = click_count.data_ptr()
+    check(_lib.load().ultr_propensity_count(ctypes.byref(a), _stream()), "ultr_propensity_count")

@@ -1,5 +1,19 @@
-"""Inverse-propensity tables (reference ultra/utils/propensity_estimator.py:10-56): a JSON file with "IPW_list"."""
+"""Inverse-propensity tables (reference ultra/utils/propensity_estimator.py): a JSON file with "IPW_list", loaded by IPWrank and
+PRSrank, and the estimators that make one: RandomizedPropensityEstimator runs the reference's randomized click experiment
+(:95-132) on the GPU (ultr_propensity_count: the session loop, the shuffle and the click histogram are one HIP kernel), the
+OraclePropensityEstimator (:149-180) answers from the click model itself.
+
+    python -m ultra_pytorch_amd.utils.propensity_estimator <click_model.json> <data_dir> <output_dir> [--sessions N] [--seed S]
+
+writes <output_dir>/randomized_<click model file stem>.json, as the reference's main() does."""
+import argparse
 import json
+import os
+
+from . import click_models as CM
+
+CLICK_MODEL_IDS = {"position_biased_model": 0, "cascade_model": 1, "user_browsing_model": 2}  # ULTR_CLICK_PBM / _CASCADE / _UBM
+SESSIONS_PER_CALL = 1 << 24  # sessions per ultr_propensity_count call: the counter is (seed, session), the split changes nothing
 
 
 class BasicPropensityEstimator(object):
@@ -22,5 +36,116 @@ class BasicPropensityEstimator(object):
             f.write(json.dumps({"IPW_list": self.IPW_list}, indent=4, sort_keys=True))
 
 
+def ipw_from_click_count(click_count):
+    """The reference's table from its counts (:119-131): click_count[y][x] = clicks on position x of lists of length y + 1;
+    first[x] = sum_{y >= x} click_count[y][0], agg[x] = sum_{y >= x} click_count[y][x],
+    IPW_list[x] = min(first[x] / (agg[x] + 10e-6), first[x]) in Python floats from the integer counts."""
+    n = len(click_count)
+    first, agg = [0] * n, [0] * n
+    for x in range(n):
+        for y in range(x, n):
+            first[x] += int(click_count[y][0])
+            agg[x] += int(click_count[y][x])
+    return [min(first[x] / (agg[x] + 10e-6), first[x]) for x in range(n)]
+
+
 class RandomizedPropensityEstimator(BasicPropensityEstimator):
-    """Loads a pre-estimated table; re-estimating one from 10^7 simulated sessions (:95-132) is offline tooling."""
+    """The table estimated from randomized click sessions (:69-146), or loaded from a file that holds one."""
+
+    def __init__(self, file_name=None):
+        self.click_model = None
+        BasicPropensityEstimator.__init__(self, file_name)
+
+    def loadEstimatorFromFile(self, file_name):
+        with open(file_name) as f:
+            data = json.load(f)
+        self.click_model = CM.loadModelFromJson(data["click_model"]) if "click_model" in data else None
+        self.IPW_list = data["IPW_list"]
+
+    def estimateParametersFromModel(self, click_model, data_set, session_num=10_000_000, seed=0, device=None):
+        """session_num times on the GPU: pick a label list of data_set uniformly, shuffle it, sample clicks with click_model, count
+        them by (list length, position); then IPW_list[x] = clicks on position 0 / clicks on position x over the lists that have a
+        position x.  Sets click_model, IPW_list (length data_set.rank_list_size) and click_count (int64 [L, L] numpy)."""
+        import numpy as np
+        import torch
+        from .. import hip_ops
+        if getattr(click_model, "model_name", None) not in CLICK_MODEL_IDS:
+            raise NotImplementedError("RandomizedPropensityEstimator simulates the position-biased, the cascade and the user-browsing model")
+        L, label_lists = int(data_set.rank_list_size), data_set.labels
+        if any(len(x) > L for x in label_lists):
+            raise ValueError("a label list is longer than rank_list_size = %d" % L)
+        if not label_lists or L <= 0 or session_num < 0:
+            raise ValueError("estimateParametersFromModel needs at least one label list, rank_list_size > 0 and session_num >= 0")
+        if not torch.cuda.is_available():
+            raise RuntimeError("RandomizedPropensityEstimator.estimateParametersFromModel needs a GPU; there is no CPU fallback")
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        labels = np.zeros((len(label_lists), L), np.float32)
+        for q, lab in enumerate(label_lists):
+            labels[q, :len(lab)] = lab
+        model_id = CLICK_MODEL_IDS[click_model.model_name]
+        ep = click_model.exam_prob
+        if model_id == 2:  # dense [n][n] image of the triangular rank x distance table, as the device feeds upload it
+            ep = [[(row[c] if c < len(row) else 0.0) for c in range(len(ep))] for row in ep]
+        with torch.cuda.device(device):
+            d_labels = torch.tensor(labels, device=device)
+            d_lengths = torch.tensor([len(x) for x in label_lists], dtype=torch.int32, device=device)
+            d_exam = torch.tensor(ep, dtype=torch.float32, device=device).contiguous()
+            d_cprob = torch.tensor(click_model.click_prob, dtype=torch.float32, device=device)
+            d_count = torch.zeros(L, L, dtype=torch.int64, device=device)
+            for first in range(0, int(session_num), SESSIONS_PER_CALL):
+                hip_ops.propensity_count(d_labels, d_lengths, d_exam, len(click_model.exam_prob), d_cprob, model_id, seed, first,
+                                         min(SESSIONS_PER_CALL, int(session_num) - first), d_count)
+            self.click_count = d_count.cpu().numpy()
+        self.click_model = click_model
+        self.IPW_list = ipw_from_click_count(self.click_count)
+
+    def outputEstimatorToFile(self, file_name):
+        with open(file_name, "w") as f:
+            f.write(json.dumps({"click_model": self.click_model.getModelJson(), "IPW_list": self.IPW_list}, indent=4, sort_keys=True))
+
+
+class OraclePropensityEstimator(BasicPropensityEstimator):
+    """The click model's own weights (:149-180): no table, no estimation."""
+
+    def __init__(self, click_model):
+        self.click_model = click_model
+
+    def loadEstimatorFromFile(self, file_name):
+        with open(file_name) as f:
+            self.click_model = CM.loadModelFromJson(json.load(f)["click_model"])
+
+    def getPropensityForOneList(self, click_list, use_non_clicked_data=False):
+        return self.click_model.estimatePropensityWeightsForOneList(click_list, use_non_clicked_data)
+
+    def outputEstimatorToFile(self, file_name):
+        with open(file_name, "w") as f:
+            f.write(json.dumps({"click_model": self.click_model.getModelJson()}, indent=4, sort_keys=True))
+
+
+def main(argv=None):
+    from . import data_utils
+    ap = argparse.ArgumentParser(prog="python -m ultra_pytorch_amd.utils.propensity_estimator",
+                                 description="Estimate an inverse-propensity table from randomized click sessions on the GPU.")
+    ap.add_argument("click_model_json")
+    ap.add_argument("data_dir")
+    ap.add_argument("output_dir")
+    ap.add_argument("--sessions", type=int, default=10_000_000)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    os.makedirs(args.output_dir, exist_ok=True)  # before the run, not after 10^7 sessions
+    print("Load data from " + args.data_dir)
+    train_set = data_utils.read_data(args.data_dir, "train")
+    with open(args.click_model_json) as fin:
+        click_model = CM.loadModelFromJson(json.load(fin))
+    print("Estimating...")
+    estimator = RandomizedPropensityEstimator()
+    estimator.estimateParametersFromModel(click_model, train_set, session_num=args.sessions, seed=args.seed)
+    print("Output results...")
+    stem = os.path.splitext(os.path.basename(args.click_model_json))[0]
+    output_file = os.path.join(args.output_dir, "randomized_" + stem + ".json")
+    estimator.outputEstimatorToFile(output_file)
+    print(output_file)
+
+
+if __name__ == "__main__":
+    main()
