@@ -388,6 +388,40 @@ int ultr_dnn_forward_ndcg(const ultr_dnn_desc* d, const float* params, const flo
                           const int32_t* docids, const float* labels, int32_t batch, int32_t list_size, float* scores,
                           const int32_t* topn, int32_t n_topn, float* ndcg_out, int32_t* order_out, float* masked_out,
                           float* ndcg_ws, uint32_t* counter, float* host_report, uint32_t seq, void* stream);
+/* ABI 8 (additive): every metric of the reference's factory table (metrics.py:36-153, weights = None) in that ONE launch.  The list is
+ * masked, validated and ranked exactly as for ultr_ndcg_report; with sl[r] the validated label at predicted rank r, n = min(topn[k], L):
+ *   NDCG       as ultr_ndcg_report (the same arithmetic in the same order: the same bits)      DCG   its numerator
+ *   MRR        1 / (1 + first r with sl >= 1), 0 without one                                   MAP   mean over r with sl >= 1 of hits(r) / (r + 1)
+ *   ERR        sum_{r<n} rel_r prod_{q<r} (1 - rel_q) / (r + 1), rel = (2^sl - 1) / 2^max_label (the exclusive product formed directly: the
+ *              reference's cumprod / (1 - rel) is NaN where rel == 1)                          ARP   sum (r + 1) sl / sum sl (0 for 0 / 0)
+ *   PRECISION  count(sl >= 1) / L over the WHOLE list, as the reference's
+ *   OPA        ordered_pair_accuracy: pairs (i, j) of documents with VALID labels, label_i > label_j and masked score_i > score_j
+ *              (a NaN compares false), over L * L
+ * Only NDCG, DCG and ERR have a cutoff; the others repeat their value per cutoff (what validation() zips with metrics_topn).
+ * metric_ids [n_metrics] (1 .. ULTR_MAX_METRICS distinct ULTR_METRIC_* ids) picks the rows and their order: out [n_metrics][n_topn] batch
+ * means, ws [batch][n_metrics][n_topn] per-list values.  host_report (may be NULL): a pinned, device-mapped page of >= 8 * 16 + 1 floats -
+ * the n_metrics * n_topn means, then the word host_report[128] = seq.  counter as for ultr_ndcg_report (the two may share one).
+ * ULTR_E_BADARG: a missing pointer, n_metrics outside 1 .. 8, an unknown or repeated id, max_label not finite, topn[k] <= 0, n_topn
+ * outside 1 .. 16.  ULTR_E_UNSUPPORTED: list_size beyond 64 KiB of LDS with one more array per list (every list_size <= 800 fits). */
+#define ULTR_METRIC_NDCG 0
+#define ULTR_METRIC_DCG 1
+#define ULTR_METRIC_MRR 2
+#define ULTR_METRIC_ERR 3
+#define ULTR_METRIC_MAP 4
+#define ULTR_METRIC_ARP 5
+#define ULTR_METRIC_PRECISION 6
+#define ULTR_METRIC_OPA 7
+#define ULTR_MAX_METRICS 8
+int ultr_metrics_report(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,
+                        int32_t list_size, const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics,
+                        float max_label, float* out /*[n_metrics][n_topn]*/, int32_t* order_out, float* masked_out,
+                        float* ws /*[batch][n_metrics][n_topn]*/, uint32_t* counter, float* host_report, uint32_t seq, void* stream);
+/* validation() with those metrics as ONE host call: ultr_dnn_forward (saved = NULL), then ultr_metrics_report of its scores. */
+int ultr_dnn_forward_metrics(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features, int64_t n_docs,
+                             const int32_t* docids, const float* labels, int32_t batch, int32_t list_size, float* scores,
+                             const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics, float max_label,
+                             float* out, int32_t* order_out, float* masked_out, float* ws, uint32_t* counter, float* host_report,
+                             uint32_t seq, void* stream);
 
 /* ---- next row: device-side click simulation + batch assembly -------------------
  * Counterpart of ClickSimulationFeed.get_batch (click_simulation_feed.py:70-174) + PositionBiasedModel

@@ -722,6 +722,19 @@ extern "C" int ultr_dnn_forward_ndcg(const ultr_dnn_desc* d, const float* params
                           host_report, seq, stream);
 }
 
+// the same with ultr_metrics_report: any of the eight validation metrics behind the forward
+extern "C" int ultr_dnn_forward_metrics(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features, int64_t n_docs,
+                                        const int32_t* docids, const float* labels, int32_t batch, int32_t list_size, float* scores,
+                                        const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics, float max_label,
+                                        float* out, int32_t* order_out, float* masked_out, float* ws, uint32_t* counter, float* host_report,
+                                        uint32_t seq, void* stream) {
+  if (!labels || !topn || !metric_ids || !out || !ws || !counter || n_topn <= 0 || n_metrics <= 0) return ULTR_E_BADARG;
+  const int rc = ultr_dnn_forward(d, params, wt, features, n_docs, docids, batch, list_size, scores, nullptr, stream);
+  if (rc != 0) return rc;
+  return ultr_metrics_report(scores, labels, docids, n_docs, batch, list_size, topn, n_topn, metric_ids, n_metrics, max_label, out, order_out,
+                             masked_out, ws, counter, host_report, seq, stream);
+}
+
 extern "C" int32_t ultr_dnn_forward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows, int32_t training) {
   DnnPlan p;
   if (n_rows <= 0 || !ultr_make_dnn_plan(d, n_rows, &p)) return -1;

@@ -1,4 +1,5 @@
-// ultr_metrics.hip — validation-side kernels: padding mask + NDCG@topn.
+// ultr_metrics.hip — validation-side kernels: padding mask + NDCG@topn, and (ultr_metrics_report) the other seven metrics of the
+// reference's factory table from the same ranked list in the same launch.
 //
 // Replaces BaseAlgorithm.remove_padding_for_metric_eval (reference base_algorithm.py:88-116) and
 // ultra.utils.metrics.normalized_discounted_cumulative_gain with weights=None (metrics.py:191-265, 456-495).
@@ -38,20 +39,41 @@ struct NdcgTail {
   uint32_t seq;
 };
 
+// ultr_metrics_report (ALL): which metrics, in which order, go into a list's [n][topn.n] block of per_list and of the report
+struct MetricSel {
+  int n;
+  int id[ULTR_MAX_METRICS];
+  float pow_max;  // 2^max_label (expected_reciprocal_rank's relevance scale, metrics.py:300-336)
+};
+#define METRICS_SEQ_WORD (ULTR_MAX_METRICS * NDCG_MAX_TOPN)  // the report's sequence word follows the largest [metrics][topn] block
+
+// LDS bytes of a workgroup: 4 (ALL: 5) [LPW][L] float arrays, ALL: one validity bit per document, the arrival word
+static size_t ndcg_lds_bytes(int L, bool all) {
+  return all ? ((size_t)NDCG_LPW * 5 * L + (size_t)NDCG_LPW * 2 * ((L + 63) / 64) + 4) * sizeof(float)
+             : ((size_t)NDCG_LPW * 4 * L + 4) * sizeof(float);
+}
+
+// ALL = false: NDCG@topn (ultr_ndcg, ultr_ndcg_report).  ALL = true: the same ranking, the same NDCG arithmetic, and the other metrics
+// of utils/metrics.py (weights = None) from the labels by predicted rank; sel picks the rows that are written.
+template <bool ALL>
 __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* __restrict__ scores,
                                                                  const float* __restrict__ labels,
                                                                  const int32_t* __restrict__ docids, int64_t n_docs,
                                                                  int B, int L, TopN topn, float* __restrict__ per_list,
                                                                  int32_t* __restrict__ order_out,
-                                                                 float* __restrict__ masked_out, NdcgTail tail) {
+                                                                 float* __restrict__ masked_out, NdcgTail tail, MetricSel sel) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sm_s = smem;                 // [LPW][L] masked + validated predictions (then their order keys)
+  float* sm_s = smem;                 // [LPW][L] masked + validated predictions (then their order keys; ALL: then the ERR terms by rank)
   float* sm_y = sm_s + NDCG_LPW * L;  // [LPW][L] validated labels
   float* sm_d = sm_y + NDCG_LPW * L;  // [LPW][L] discounted gains by predicted rank
   float* sm_i = sm_d + NDCG_LPW * L;  // [LPW][L] discounted gains by ideal rank
+  float* sm_l = sm_i + NDCG_LPW * L;  // ALL: [LPW][L] validated labels by predicted rank
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x * NDCG_LPW + wave;
-  unsigned* arrived = reinterpret_cast<unsigned*>(sm_i + NDCG_LPW * L);  // waves of this workgroup that finished their list (ultr_ndcg_report)
+  const int nch = (L + 63) >> 6;  // 64-document chunks of a list
+  // ALL: [LPW][nch] 64-bit masks of the documents whose label was valid (ordered_pair_accuracy counts pairs of those only)
+  unsigned long long* sm_v = reinterpret_cast<unsigned long long*>(sm_l + (ALL ? NDCG_LPW * L : 0));
+  unsigned* arrived = reinterpret_cast<unsigned*>(sm_v + (ALL ? NDCG_LPW * nch : 0));  // waves of this workgroup that finished their list (ultr_ndcg_report)
   if (tail.counter != nullptr) {
     if (threadIdx.x == 0) *arrived = 0u;
     __syncthreads();  // (before the waves without a list leave)
@@ -61,6 +83,8 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
   float* my = sm_y + wave * L;
   float* md = sm_d + wave * L;
   float* mi = sm_i + wave * L;
+  float* ml = sm_l + wave * L;
+  unsigned long long* mv = sm_v + wave * nch;
   // pad mask, then metrics.py:251-264: invalid labels (< 0) -> label 0, prediction rowmin - 1e-6
   // (score, doc id and label of a position are requested together: the kernel is a chain of dependent round trips, not bytes)
   float mn = INFINITY;
@@ -78,24 +102,44 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
   mn = -wave_max(-mn);
   if (__ballot(nan_seen) != 0) mn = __builtin_nanf("");  // torch.min propagates a NaN (fminf drops it)
   unsigned* mk = reinterpret_cast<unsigned*>(ms);  // the validated predictions, from here on as order keys (score_key)
-  for (int l = lane; l < L; l += 64) {
-    const float y = my[l];
-    const bool ok = y >= 0.f;
-    my[l] = ok ? y : 0.f;
-    mk[l] = score_key(ok ? ms[l] : -1e-6f + mn);
+  for (int l0 = 0; l0 < L; l0 += 64) {
+    const int l = l0 + lane;
+    bool ok = false;
+    if (l < L) {
+      const float y = my[l];
+      ok = y >= 0.f;
+      my[l] = ok ? y : 0.f;
+      mk[l] = score_key(ok ? ms[l] : -1e-6f + mn);
+    }
+    if constexpr (ALL) {
+      const unsigned long long okm = __ballot(ok);
+      if (lane == 0) mv[l0 >> 6] = okm;
+    }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  int opa = 0;  // ALL: this lane's correctly ordered pairs
   for (int i = lane; i < L; i += 64) {
     const unsigned ki = mk[i];
     const float yi = my[i];
-    int rs = 0, ry = 0;
+    int rs = 0, ry = 0, pairs = 0;
+    unsigned long long vj = 0;
     for (int j = 0; j < L; ++j) {
       const unsigned kj = mk[j];
       const float yj = my[j];
       rs += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
       ry += (yj > yi || (yj == yi && j < i)) ? 1 : 0;
+      if constexpr (ALL) {
+        // ordered_pair_accuracy (metrics.py:531-568): label_i > label_j and score_i > score_j, j valid (i: below).  Between valid
+        // documents the keys order as the masked scores compare, but for NaN, which compares false
+        if ((j & 63) == 0) vj = mv[j >> 6];
+        pairs += (yi > yj && ki > kj && ((vj >> (j & 63)) & 1ull)) ? 1 : 0;
+      }
+    }
+    if constexpr (ALL) {
+      if (((mv[i >> 6] >> (i & 63)) & 1ull) && ki != 0xFFFFFFFFu) opa += pairs;
+      ml[rs] = yi;
     }
     const float gain = exp2f(yi) - 1.0f;  // weights = 1: gains = 2^label - 1 (metrics.py:213)
     md[rs] = gain * (1.0f / log2f((float)rs + 2.0f));
@@ -105,18 +149,75 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  // ALL: the metrics without a cutoff, and the ERR terms by rank (over the order keys, which nothing reads any more)
+  float whole[ULTR_MAX_METRICS] = {};  // by ULTR_METRIC_* id (the NDCG, DCG and ERR entries are filled per cutoff)
+  float* me = ms;
+  if constexpr (ALL) {
+    float carry = 1.f, ap = 0.f, pos_sum = 0.f, lab_sum = 0.f;  // prod(1 - rel) of the chunks before, sum of precision-at-hit, ARP's sums
+    int hits = 0, first = L;                                    // relevant documents so far, the first one's rank
+    for (int r0 = 0; r0 < L; r0 += 64) {
+      const int r = r0 + lane;
+      const float y = r < L ? ml[r] : 0.f;
+      const bool hit = r < L && y >= 1.f;
+      const float rel = (exp2f(y) - 1.0f) / sel.pow_max;  // metrics.py:320 (0 behind the list's end)
+      // the exclusive product of 1 - rel along the rank, formed directly (the reference's cumprod / (1 - rel) is NaN at rel == 1):
+      // an inclusive scan over the wave, shifted by one lane, times the carry of the chunks before
+      float p = 1.0f - rel;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const float t = __shfl_up(p, d);
+        if (lane >= d) p *= t;
+      }
+      float excl = __shfl_up(p, 1);
+      if (lane == 0) excl = 1.f;
+      excl *= carry;
+      carry *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), 63));
+      if (r < L) me[r] = rel * excl * (1.0f / (float)(r + 1));
+      // mean_average_precision (metrics.py:408-453): hits up to and including this rank / (rank + 1) at every hit
+      const unsigned long long hm = __ballot(hit);
+      if (hit) ap += (float)(hits + __popcll(hm & ((2ull << lane) - 1ull))) / (float)(r + 1);
+      if (first == L && hm != 0) first = r0 + __ffsll((long long)hm) - 1;
+      hits += __popcll(hm);
+      pos_sum += (float)(r + 1) * y;
+      lab_sum += y;
+    }
+    float sums[4] = {ap, pos_sum, lab_sum, (float)opa};  // (the pair count is below 2^24: exact)
+    wave_sum_n<4>(sums);
+    whole[ULTR_METRIC_MRR] = first < L ? 1.0f / (float)(first + 1) : 0.f;
+    whole[ULTR_METRIC_MAP] = hits > 0 ? sums[0] / (float)hits : 0.f;
+    whole[ULTR_METRIC_ARP] = sums[2] == 0.f ? 0.f : sums[1] / sums[2];  // _safe_div
+    whole[ULTR_METRIC_PRECISION] = (float)hits / (float)L;
+    whole[ULTR_METRIC_OPA] = sums[3] / ((float)L * (float)L);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  const int width = ALL ? sel.n * topn.n : topn.n;  // floats of a list in per_list, and of the batch means
   for (int k = 0; k < topn.n; ++k) {
     const int n = topn.v[k] < L ? topn.v[k] : L;  // topn clipped to the list size (metrics.py:249)
-    float d = 0.f, id = 0.f;
+    float d = 0.f, id = 0.f, e = 0.f;
     for (int r = lane; r < n; r += 64) {
       d += md[r];
       id += mi[r];
+      if constexpr (ALL) e += me[r];
     }
     d = wave_sum(d);
     id = wave_sum(id);
+    if constexpr (ALL) e = wave_sum(e);
     if (lane == 0) {
       const float v = (id == 0.f) ? 0.f : d / id;  // _safe_div
-      if (tail.counter != nullptr) coh_st1(make_src(per_list, (int64_t)B * topn.n), (unsigned)(((int64_t)b * topn.n + k) * 4), v);  // written through
+      if constexpr (ALL) {
+        whole[ULTR_METRIC_NDCG] = v;
+        whole[ULTR_METRIC_DCG] = d;
+        whole[ULTR_METRIC_ERR] = e;
+        const Src pl = make_src(per_list, (int64_t)B * width);
+        for (int m = 0; m < sel.n; ++m) {
+          float x = 0.f;
+#pragma unroll
+          for (int q = 0; q < ULTR_MAX_METRICS; ++q) x = sel.id[m] == q ? whole[q] : x;  // (registers: no indexed private array)
+          coh_st1(pl, (unsigned)(((int64_t)b * width + m * topn.n + k) * 4), x);
+        }
+      } else if (tail.counter != nullptr) coh_st1(make_src(per_list, (int64_t)B * topn.n), (unsigned)(((int64_t)b * topn.n + k) * 4), v);  // written through
       else per_list[(int64_t)b * topn.n + k] = v;
     }
   }
@@ -135,6 +236,26 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
   if (lane == 0) old = __hip_atomic_fetch_add(tail.counter, (unsigned)lists_here, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
   if (old + (unsigned)lists_here != (unsigned)B) return;
+  if constexpr (ALL) {
+    const Src pl = make_src(per_list, (int64_t)B * width);
+    for (int w = 0; w < width; ++w) {
+      float s = 0.f;
+      for (int bb = lane; bb < B; bb += 64) s += coh_ld1(pl, (unsigned)(((int64_t)bb * width + w) * 4));  // served from the coherence point
+      s = wave_sum(s) / (float)B;
+      if (lane == 0) {
+        tail.out[w] = s;
+        if (tail.host != nullptr) __hip_atomic_store(tail.host + w, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+    if (lane == 0) {
+      __hip_atomic_store(tail.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch on this stream
+      if (tail.host != nullptr) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(reinterpret_cast<uint32_t*>(tail.host) + METRICS_SEQ_WORD, tail.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+    return;
+  }
   const Src pl = make_src(per_list, (int64_t)B * topn.n);
   float vals[NDCG_MAX_TOPN];
   for (int k = 0; k < topn.n; ++k) {
@@ -175,13 +296,13 @@ extern "C" int ultr_ndcg(const float* scores, const float* labels, const int32_t
     if (topn[k] <= 0) return ULTR_E_BADARG;
     t.v[k] = topn[k];
   }
-  const size_t lds = ((size_t)NDCG_LPW * 4 * list_size + 4) * sizeof(float);
+  const size_t lds = ndcg_lds_bytes(list_size, false);
   if (lds > 64 * 1024) return ULTR_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   {
     UltrProfScope prof(ULTR_K_NDCG, st);
-    ULTR_LAUNCH(prof, ndcg_list_kernel, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
-                n_docs, (int)batch, (int)list_size, t, ndcg_ws, order_out, masked_out, NdcgTail{nullptr, nullptr, nullptr, 0u});
+    ULTR_LAUNCH(prof, ndcg_list_kernel<false>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
+                n_docs, (int)batch, (int)list_size, t, ndcg_ws, order_out, masked_out, NdcgTail{nullptr, nullptr, nullptr, 0u}, MetricSel{});
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
@@ -203,11 +324,45 @@ extern "C" int ultr_ndcg_report(const float* scores, const float* labels, const 
     if (topn[k] <= 0) return ULTR_E_BADARG;
     t.v[k] = topn[k];
   }
-  const size_t lds = ((size_t)NDCG_LPW * 4 * list_size + 4) * sizeof(float);
+  const size_t lds = ndcg_lds_bytes(list_size, false);
   if (lds > 64 * 1024) return ULTR_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   UltrProfScope prof(ULTR_K_NDCG, st);
-  ULTR_LAUNCH(prof, ndcg_list_kernel, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
-              n_docs, (int)batch, (int)list_size, t, ndcg_ws, order_out, masked_out, NdcgTail{counter, ndcg_out, host_report, seq});
+  ULTR_LAUNCH(prof, ndcg_list_kernel<false>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
+              n_docs, (int)batch, (int)list_size, t, ndcg_ws, order_out, masked_out, NdcgTail{counter, ndcg_out, host_report, seq}, MetricSel{});
+  return (int)hipGetLastError();
+}
+
+// ONE launch for any of the eight metrics of utils/metrics.py: out [n_metrics][n_topn] in the order of metric_ids (include/ultr_hip.h)
+extern "C" int ultr_metrics_report(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,
+                                   int32_t list_size, const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics,
+                                   float max_label, float* out, int32_t* order_out, float* masked_out, float* ws, uint32_t* counter,
+                                   float* host_report, uint32_t seq, void* stream) {
+  if (!scores || !labels || !topn || !metric_ids || !out || !ws || !counter || batch <= 0 || list_size <= 0 || n_topn <= 0 ||
+      n_topn > NDCG_MAX_TOPN || n_metrics <= 0 || n_metrics > ULTR_MAX_METRICS || !(fabsf(max_label) < INFINITY))
+    return ULTR_E_BADARG;
+  TopN t;
+  t.n = n_topn;
+  for (int k = 0; k < n_topn; ++k) {
+    if (topn[k] <= 0) return ULTR_E_BADARG;
+    t.v[k] = topn[k];
+  }
+  MetricSel sel{};
+  sel.n = n_metrics;
+  sel.pow_max = exp2f(max_label);
+  unsigned seen = 0;
+  for (int m = 0; m < n_metrics; ++m) {
+    const int id = metric_ids[m];
+    if (id < 0 || id >= ULTR_MAX_METRICS || ((seen >> id) & 1u)) return ULTR_E_BADARG;  // unknown or repeated
+    seen |= 1u << id;
+    sel.id[m] = id;
+  }
+  const size_t lds = ndcg_lds_bytes(list_size, true);
+  // (the per-list block is addressed with 32-bit byte offsets through a buffer descriptor)
+  if (lds > 64 * 1024 || (int64_t)batch * n_metrics * n_topn * 4 > INT32_MAX) return ULTR_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  UltrProfScope prof(ULTR_K_NDCG, st);
+  ULTR_LAUNCH(prof, ndcg_list_kernel<true>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
+              n_docs, (int)batch, (int)list_size, t, ws, order_out, masked_out, NdcgTail{counter, out, host_report, seq}, sel);
   return (int)hipGetLastError();
 }

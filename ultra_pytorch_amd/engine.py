@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, hip_ops
+from .utils import metrics as metrics_mod
 
 ALGOS = {"softmax": _lib.ALGO_SOFTMAX, "dla": _lib.ALGO_DLA, "pairdebias": _lib.ALGO_PAIRDEBIAS,
          "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM, "prs": _lib.ALGO_PRS,
@@ -325,10 +326,22 @@ class StepEngine:
         return self.scalars
 
 
-class EvalEngine:
-    """validation(): forward at max_candidate_num + padding mask + NDCG@topn."""
+# ULTR_METRIC_* (include/ultr_hip.h) by RankingMetricKey
+METRIC_IDS = {"ndcg": 0, "dcg": 1, "mrr": 2, "err": 3, "map": 4, "arp": 5, "precision": 6, "ordered_pair_accuracy": 7}
+_METRICS_SEQ_WORD = 8 * 16  # ultr_metrics_report's sequence word in the host report (ultr_ndcg_report's is 16)
 
-    def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10)):
+
+def metrics_fit(list_size):
+    """Whether ultr_metrics_report takes this list size (csrc/ultr_metrics.hip ndcg_lds_bytes: 64 KiB of LDS for four lists)."""
+    L = int(list_size)
+    return (4 * 5 * L + 4 * 2 * ((L + 63) // 64) + 4) * 4 <= 64 * 1024
+
+
+class EvalEngine:
+    """validation(): forward at max_candidate_num + padding mask + NDCG@topn; with metrics other than ("ndcg",) every requested metric
+    of utils.metrics in the same launch (ultr_metrics_report), read with read_metrics()."""
+
+    def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10), metrics=("ndcg",)):
         if not torch.cuda.is_available():
             raise RuntimeError("ultra_pytorch_amd needs an MI355X/ROCm GPU: there is no CPU fallback")
         self.shape, self.B, self.L, self.device = shape, int(batch), int(list_size), device
@@ -347,9 +360,37 @@ class EvalEngine:
         self._seq = 0
         self._topn_arr = (ctypes.c_int32 * len(self.topn))(*self.topn)
         self._lib = shape.lib
+        self.metrics = tuple(metrics)
+        self._all = self.metrics != ("ndcg",)
+        if self._all:
+            unknown = [m for m in self.metrics if m not in METRIC_IDS]
+            if unknown or len(set(self.metrics)) != len(self.metrics) or not self.metrics:
+                raise ValueError("metrics must be distinct keys of %s, got %r" % (sorted(METRIC_IDS), self.metrics))
+            nm, nt = len(self.metrics), len(self.topn)
+            self._ids_arr = (ctypes.c_int32 * nm)(*[METRIC_IDS[m] for m in self.metrics])
+            self.metric_out = _f32(nm * nt, device).view(nm, nt)  # batch means, a row per metric in the order asked
+            self.metric_ws = _f32(self.B * nm * nt, device).view(self.B, nm, nt)  # per-list values
+            # (self.ndcg / self.ndcg_ws stay allocated; the NDCG row of this path is metric_out's)
+            self.ndcg = self.metric_out[self.metrics.index("ndcg")] if "ndcg" in self.metrics else None
+            self._hs = torch.zeros(_METRICS_SEQ_WORD + 32, dtype=torch.float32).pin_memory()
+            self._hs_f = self._hs.numpy()
+            self._hs_u = self._hs_f.view(np.uint32)
+
+    @staticmethod
+    def _max_label():
+        """RankingMetricKey.MAX_LABEL is set by the data loader, possibly after this engine was built: read at every run()."""
+        ml = metrics_mod.RankingMetricKey.MAX_LABEL
+        return 4.0 if ml is None else float(ml)
 
     def _ndcg(self, labels, docids, n_docs):
         self._seq = (self._seq % 0xFFFFFFFF) + 1
+        if self._all:
+            _lib.check(self._lib.ultr_metrics_report(self.scores.data_ptr(), labels.data_ptr(), docids.data_ptr(), int(n_docs), self.B, self.L,
+                                                     self._topn_arr, len(self.topn), self._ids_arr, len(self.metrics), self._max_label(),
+                                                     self.metric_out.data_ptr(), self.order.data_ptr(), self.masked.data_ptr(),
+                                                     self.metric_ws.data_ptr(), self._counter.data_ptr(), self._hs.data_ptr(), self._seq,
+                                                     hip_ops.raw_stream()), "ultr_metrics_report")
+            return
         _lib.check(self._lib.ultr_ndcg_report(self.scores.data_ptr(), labels.data_ptr(), docids.data_ptr(), int(n_docs), self.B, self.L,
                                               self._topn_arr, len(self.topn), self.ndcg.data_ptr(), self.order.data_ptr(),
                                               self.masked.data_ptr(), self.ndcg_ws.data_ptr(), self._counter.data_ptr(),
@@ -359,6 +400,15 @@ class EvalEngine:
         """ONE host call (ultr_dnn_forward_ndcg): the forward, then the metric launch with its report in host-mapped memory."""
         self._seq = (self._seq % 0xFFFFFFFF) + 1
         wt = hip_ops.weight_copy(self.shape).get(params)
+        if self._all:
+            _lib.check(self._lib.ultr_dnn_forward_metrics(ctypes.byref(self.shape.desc), params.data_ptr(), wt.data_ptr() if wt is not None else None,
+                                                          features.data_ptr() if n_docs > 0 else None, int(n_docs), docids.data_ptr(),
+                                                          labels.data_ptr(), self.B, self.L, self.scores.data_ptr(), self._topn_arr,
+                                                          len(self.topn), self._ids_arr, len(self.metrics), self._max_label(),
+                                                          self.metric_out.data_ptr(), self.order.data_ptr(), self.masked.data_ptr(),
+                                                          self.metric_ws.data_ptr(), self._counter.data_ptr(), self._hs.data_ptr(), self._seq,
+                                                          hip_ops.raw_stream()), "ultr_dnn_forward_metrics")
+            return self.scores, self.ndcg
         _lib.check(self._lib.ultr_dnn_forward_ndcg(ctypes.byref(self.shape.desc), params.data_ptr(), wt.data_ptr() if wt is not None else None,
                                                    features.data_ptr() if n_docs > 0 else None, int(n_docs), docids.data_ptr(),
                                                    labels.data_ptr(), self.B, self.L, self.scores.data_ptr(), self._topn_arr, len(self.topn),
@@ -370,17 +420,33 @@ class EvalEngine:
     def read_ndcg(self, timeout_s=60.0):
         """NDCG@topn of the LAST run() as a numpy array - the reference's `.item()` per metric (ipw_rank.py:204-210) without a stream
         synchronisation: waits for the launch's report in host-mapped memory."""
+        if self._all:
+            if "ndcg" not in self.metrics:
+                raise RuntimeError("read_ndcg() of an engine built without the ndcg metric")
+            return self.read_metrics(timeout_s)["ndcg"]
+        self._wait_report(16, timeout_s)
+        return self._hs_f[:len(self.topn)].copy()
+
+    def _wait_report(self, word, timeout_s):
         seq, u, spins, t0 = self._seq, self._hs_u, 0, None
         if seq == 0:
             raise RuntimeError("read_ndcg() before the first run()")
-        while int(u[16]) != seq:
+        while int(u[word]) != seq:
             spins += 1
             if spins & 0x3FF == 0:
                 now = time.perf_counter()
                 t0 = now if t0 is None else t0
                 if now - t0 > timeout_s:
                     raise _lib.UltrHipError("no NDCG report from the GPU within %.0f s" % timeout_s)
-        return self._hs_f[:len(self.topn)].copy()
+
+    def read_metrics(self, timeout_s=60.0):
+        """{metric: values per cutoff} of the LAST run(), from the launch's report in host-mapped memory (no stream synchronisation)."""
+        if not self._all:
+            return {"ndcg": self.read_ndcg(timeout_s)}
+        self._wait_report(_METRICS_SEQ_WORD, timeout_s)
+        nt = len(self.topn)
+        vals = self._hs_f[:len(self.metrics) * nt].copy()
+        return {m: vals[k * nt:(k + 1) * nt] for k, m in enumerate(self.metrics)}
 
 
 def _setrank_draw(list_size):
@@ -449,8 +515,8 @@ class SetRankStepEngine(StepEngine):
 
 
 class SetRankEvalEngine(EvalEngine):
-    def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10)):
-        super().__init__(shape, batch, list_size, device, topn=topn)
+    def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10), metrics=("ndcg",)):
+        super().__init__(shape, batch, list_size, device, topn=topn, metrics=metrics)
         self.saved = _f32(shape.saved_bytes(self.B * self.L) // 4, device)
         self._flag = self.saved[shape.range_flag_offset(self.B * self.L):][:1].view(torch.int32)
         self._checked = None  # (data_ptr, version) of the parameters whose split-half planes were last looked at

@@ -191,10 +191,17 @@ class BaseAlgorithm(object):
         labels_host = self.create_input_feed(input_feed, L)
         B = self.batch_size
         topn = [int(t) for t in self.exp_settings["metrics_topn"]]
-        key = (B, L, tuple(topn))
+        # every key of utils.metrics' table comes out of the ONE metric launch (ultr_metrics_report).  What that launch does not take -
+        # a list beyond its LDS budget, a key outside the table - keeps the NDCG launch + utils.metrics on the host, as does
+        # ["ndcg"] alone (and online simulation, which reads no metric)
+        wanted = tuple(dict.fromkeys(self.exp_settings["metrics"]))
+        on_device = (not is_online_simulation and wanted != ("ndcg",) and len(wanted) > 0 and engine.metrics_fit(L)
+                     and all(m in engine.METRIC_IDS for m in wanted))
+        names = wanted if on_device else ("ndcg",)
+        key = (B, L, tuple(topn), names)
         if key not in self._eval_engines:
             cls = getattr(self.model, "eval_engine_cls", engine.EvalEngine)
-            self._eval_engines[key] = cls(self.model.shape, B, L, self.cuda, topn=topn)
+            self._eval_engines[key] = cls(self.model.shape, B, L, self.cuda, topn=topn, metrics=names)
             while len(self._eval_engines) > self.MAX_ENGINES:
                 self._eval_engines.popitem(last=False)
         else:
@@ -202,7 +209,12 @@ class BaseAlgorithm(object):
         ev = self._eval_engines[key]
         scores, ndcg = ev.run(self.model.flat_params, self.letor_features, self.n_docs, self.docid_inputs, self.labels_LB)
         self.output = scores.clone()  # the UNMASKED scores are what callers get (base_algorithm.py / main.py:266)
-        if not is_online_simulation:
+        if on_device:
+            # host-mapped report of the metric launch (no stream synchronisation, no copy of scores or labels)
+            for metric, values in ev.read_metrics().items():
+                for n, v in zip(topn, values):
+                    self.eval_summary["%s_%d" % (metric, n)] = float(v)
+        elif not is_online_simulation:
             masked = None
             for metric in self.exp_settings["metrics"]:
                 if metric == metrics_mod.RankingMetricKey.NDCG:

@@ -1,9 +1,9 @@
 """Host-side ranking metrics with the reference's factory interface (ultra/utils/metrics.py:36-153).
 
-NDCG on the validation path runs as a HIP kernel (ultr_ndcg); the other metrics that appear in the example
-settings (mrr, err) and the rest of the reference's factory table (arp, precision, map, ordered_pair_accuracy, dcg) are
-evaluated here on host tensors — SURVEY.md §8 a13 marks them "host restatement suffices".  weights=None semantics only
-(what every validation() call passes).  Pinned to the reference's own outputs: tests/golden/metrics_host.npz.
+validation() computes every metric of this table on the GPU, in its one metric launch (ultr_metrics_report, csrc/ultr_metrics.hip).
+This module is the reference's factory interface for callers that hold host tensors, and validation()'s path for a list longer than
+that launch takes (engine.metrics_fit).  weights=None semantics only (what every validation() call passes).  Pinned to the
+reference's own outputs: tests/golden/metrics_host.npz.
 Two places where this module is usable and the reference is not: `dcg` (the reference's raises: it gathers a `weights` of None,
 metrics.py:519-523 -> :191-221) and `precision` (the reference returns ONE scalar whatever topn is, metrics.py:373-405, which
 validation()'s zip over metrics_topn cannot iterate; here the same value is repeated per cut-off).
