@@ -641,6 +641,48 @@ typedef struct ultr_propensity_args {
 } ultr_propensity_args;
 int ultr_propensity_count(const ultr_propensity_args* a, void* stream);
 
+/* ---- a whole validation / test set from a RESIDENT dataset (ultr_eval.hip; additive within ABI 8) -----------------------------------
+ * Counterpart of the driver's evaluation loop (main.py:85-227 validate, :230-292 test): DirectLabelFeed.get_next_batch per batch
+ * (direct_label_feed.py:36-47), validation() per batch, utils.merge_Summary at the end (data_utils.py:501-514) - for a dataset
+ * RESIDENT in HBM (lists / labels as for ultr_click_batch).
+ *   ultr_eval_pick        the sequential sibling of ultr_online_pick_args: queries start .. start + batch - 1 and positions
+ *                         l < list_size: docids_out [L, B] = the list entry, or n_docs (PAD) where the entry is < 0 or l >= lmax;
+ *                         labels_out [L, B] = the label, 0 at a PAD (prepare_true_labels_with_index, direct_label_feed.py:19-23);
+ *                         query_idx_out [B] (may be NULL) = start + b.  One wavefront per slot, four slots per workgroup; ANY
+ *                         list_size >= 1 (no 256 cap: validation lists can be long).
+ *                         ULTR_E_BADARG: a missing pointer (query_idx_out excepted), n_queries / lmax <= 0, n_docs outside 0 .. 2^31 - 1,
+ *                         start < 0, batch <= 0, start + batch > n_queries, list_size <= 0.  Launches nothing then.
+ *   ultr_eval_accumulate  merge_Summary operation for operation in double: acc[i] += (double)batch_means[i] * (double)batch for
+ *                         i < n_values, acc[n_values] += batch; acc [n_values + 1] doubles on the device.  flags: ULTR_EVAL_RESET - the
+ *                         accumulator counts as zero before the add (it need not be cleared); ULTR_EVAL_FINISH - after the add,
+ *                         host_report[i] = acc[i] / max(1e-7, acc[n_values]) (IEEE round-to-nearest), host_report[128] = acc[n_values],
+ *                         then the 32-bit word behind 129 doubles (byte offset ULTR_EVAL_SEQ_BYTE) = seq, ordered behind the values as
+ *                         ultr_metrics_report orders its report.  host_report: pinned, device-mapped, >= ULTR_EVAL_SEQ_BYTE + 4 bytes
+ *                         (required with ULTR_EVAL_FINISH).  One workgroup, one thread per value: no reduction, no atomics.
+ *                         ULTR_E_BADARG: a missing pointer, n_values outside 1 .. 128, batch <= 0, unknown flag bits.
+ *   ultr_dnn_eval_set     the whole set from ONE host call: per chunk of `batch` queries (the last one short) ultr_eval_pick into
+ *                         docids_ws / labels_ws [L, batch], ultr_dnn_forward_metrics of the chunk (host report NULL; topn, metric_ids,
+ *                         max_label, out, order_out, masked_out, ws, counter as there, sized for `batch` lists) and
+ *                         ultr_eval_accumulate of `out` (n_values = n_metrics * n_topn) - ULTR_EVAL_RESET on the first chunk,
+ *                         ULTR_EVAL_FINISH on the last.  scores_all [n_queries, L] / per_query [n_queries, n_metrics, n_topn] (either
+ *                         may be NULL): every chunk's scores / per-list metric values written straight to their offset; otherwise
+ *                         they go to scores_ws [batch, L] / ws and only the last chunk's remain.  The launches of a chunk are exactly
+ *                         the ones validation() issues for that batch: the merged figures are the per-batch loop's, bit for bit.
+ *                         Does not synchronise, does not allocate, stops at the first non-zero return. */
+#define ULTR_EVAL_RESET 1
+#define ULTR_EVAL_FINISH 2
+#define ULTR_EVAL_SEQ_BYTE (129 * 8)
+int ultr_eval_pick(const int32_t* lists, const float* labels, int64_t n_queries, int32_t lmax, int64_t n_docs, int64_t start,
+                   int32_t batch, int32_t list_size, int32_t* docids_out, float* labels_out, int32_t* query_idx_out, void* stream);
+int ultr_eval_accumulate(const float* batch_means, int32_t n_values, int32_t batch, double* acc, int32_t flags, double* host_report,
+                         uint32_t seq, void* stream);
+int ultr_dnn_eval_set(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features, int64_t n_docs,
+                      const int32_t* lists, const float* labels, int64_t n_queries, int32_t lmax, int32_t batch, int32_t list_size,
+                      const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics, float max_label,
+                      int32_t* docids_ws, float* labels_ws, float* scores_ws, float* out, int32_t* order_out, float* masked_out, float* ws,
+                      uint32_t* counter, float* scores_all, float* per_query, double* acc, double* host_report, uint32_t seq,
+                      void* stream);
+
 /* ---- e: data-parallel gradient exchange over xGMI -----------------------------
  * No reference counterpart: the reference is single-process.  One process per GPU; queries shard across ranks,
  * parameters / optimizer / EM state are replicated, and ONE sum per step of the flat vector

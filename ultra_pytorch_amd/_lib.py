@@ -80,6 +80,7 @@ class PropensityArgs(ctypes.Structure):  # ultr_propensity_args (ultr_propensity
 
 
 PROPENSITY_MAX_L = 128  # include/ultr_hip.h: ULTR_PROPENSITY_MAX_L
+EVAL_RESET, EVAL_FINISH, EVAL_SEQ_BYTE = 1, 2, 129 * 8  # include/ultr_hip.h: ULTR_EVAL_*
 
 
 class SetRankDesc(ctypes.Structure):
@@ -168,6 +169,11 @@ SIGNATURES = {
     "ultr_dnn_forward_metrics": (c_i32, [ctypes.POINTER(DnnDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp,
                                          ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_i32), c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp,
                                          c_vp, c_vp, ctypes.c_uint32, c_vp]),
+    "ultr_eval_pick": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "ultr_eval_accumulate": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, ctypes.c_uint32, c_vp]),
+    "ultr_dnn_eval_set": (c_i32, [ctypes.POINTER(DnnDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
+                                  ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_i32), c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint32, c_vp]),
 }
 
 _LIB = None

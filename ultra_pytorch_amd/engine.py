@@ -449,6 +449,117 @@ class EvalEngine:
         return {m: vals[k * nt:(k + 1) * nt] for k, m in enumerate(self.metrics)}
 
 
+class EvalSetEngine:
+    """A whole validation / test set from a ResidentDataset without returning to the host between batches (csrc/ultr_eval.hip): per
+    chunk of `batch` queries (the last one short) the sequential pick, the launches validation() issues for that batch and the
+    accumulate in double - utils.merge_Summary operation for operation - then ONE host read of the merged report.
+
+    A DNN / Linear model runs the chunks from one C call (ultr_dnn_eval_set).  A model with another eval engine (SetRank) runs the same
+    three stages per chunk from Python: ultr_eval_pick, that engine's run() without reading its report, ultr_eval_accumulate."""
+
+    def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10), metrics=("ndcg",), eval_engine_cls=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("ultra_pytorch_amd needs an MI355X/ROCm GPU: there is no CPU fallback")
+        self.shape, self.B, self.L, self.device = shape, int(batch), int(list_size), device
+        self.topn, self.metrics = [int(t) for t in topn], tuple(metrics)
+        unknown = [m for m in self.metrics if m not in METRIC_IDS]
+        if unknown or len(set(self.metrics)) != len(self.metrics) or not self.metrics:
+            raise ValueError("metrics must be distinct keys of %s, got %r" % (sorted(METRIC_IDS), self.metrics))
+        if not metrics_fit(self.L):
+            raise ValueError("list size %d is beyond the metric launch's LDS budget (engine.metrics_fit)" % self.L)
+        self._lib = shape.lib
+        B, L, nm, nt = self.B, self.L, len(self.metrics), len(self.topn)
+        self.n_values = nm * nt
+        self._cls = eval_engine_cls if eval_engine_cls not in (None, EvalEngine) else None
+        self.acc = torch.zeros(self.n_values + 1, dtype=torch.float64, device=device)
+        # the merged report in HOST-mapped pinned memory: 128 values, the summed weights, the sequence word (ULTR_EVAL_SEQ_BYTE)
+        self._hs = torch.zeros(_lib.EVAL_SEQ_BYTE // 8 + 1, dtype=torch.float64).pin_memory()
+        self._hs_d = self._hs.numpy()
+        self._hs_u = self._hs_d.view(np.uint32)
+        self._seq = 0
+        self.docids = torch.empty(L, B, dtype=torch.int32, device=device)
+        self.labels = torch.empty(L, B, dtype=torch.float32, device=device)
+        self.scores_all = self.per_query = None
+        self.n_queries = 0
+        if self._cls is None:
+            self._topn_arr = (ctypes.c_int32 * nt)(*self.topn)
+            self._ids_arr = (ctypes.c_int32 * nm)(*[METRIC_IDS[m] for m in self.metrics])
+            self.scores = _f32(B * L, device).view(B, L)
+            self.masked = _f32(B * L, device).view(B, L)
+            self.order = torch.empty(B, L, dtype=torch.int32, device=device)
+            self.metric_out = _f32(nm * nt, device).view(nm, nt)
+            self.metric_ws = _f32(B * nm * nt, device).view(B, nm, nt)
+            self._counter = torch.zeros(1, dtype=torch.int32, device=device)
+        else:
+            self._engines = {}  # chunk size -> the model's own eval engine (the full chunk and the short last one)
+
+    def _chunk_engine(self, b):
+        ev = self._engines.get(b)
+        if ev is None:
+            ev = self._engines[b] = self._cls(self.shape, b, self.L, self.device, topn=self.topn, metrics=self.metrics)
+        return ev
+
+    def _outputs(self, n_queries, want_scores, per_query):
+        nm, nt = len(self.metrics), len(self.topn)
+        if want_scores and (self.scores_all is None or self.scores_all.shape[0] != n_queries):
+            self.scores_all = _f32(n_queries * self.L, self.device).view(n_queries, self.L)
+        if per_query and (self.per_query is None or self.per_query.shape[0] != n_queries):
+            self.per_query = _f32(n_queries * nm * nt, self.device).view(n_queries, nm, nt)
+        return (self.scores_all if want_scores else None), (self.per_query if per_query else None)
+
+    def run(self, params, resident, want_scores=False, per_query=False):
+        """Queue the whole set on the current stream; read() waits for the report.  want_scores / per_query: keep every query's scores
+        [n_queries, L] / per-list metric values [n_queries, n_metrics, n_topn] on the device (self.scores_all / self.per_query)."""
+        rd, st = resident, hip_ops.raw_stream()
+        nq = self.n_queries = int(rd.n_queries)
+        sa, pq = self._outputs(nq, want_scores, per_query)
+        self._seq = (self._seq % 0xFFFFFFFF) + 1
+        feats = rd.features.data_ptr() if rd.n_docs > 0 else None
+        if self._cls is None:
+            wt = hip_ops.weight_copy(self.shape).get(params)
+            _lib.check(self._lib.ultr_dnn_eval_set(
+                ctypes.byref(self.shape.desc), params.data_ptr(), wt.data_ptr() if wt is not None else None, feats, rd.n_docs,
+                rd.lists.data_ptr(), rd.labels.data_ptr(), nq, rd.lmax, self.B, self.L, self._topn_arr, len(self.topn), self._ids_arr,
+                len(self.metrics), EvalEngine._max_label(), self.docids.data_ptr(), self.labels.data_ptr(), self.scores.data_ptr(),
+                self.metric_out.data_ptr(), self.order.data_ptr(), self.masked.data_ptr(), self.metric_ws.data_ptr(),
+                self._counter.data_ptr(), sa.data_ptr() if sa is not None else None, pq.data_ptr() if pq is not None else None,
+                self.acc.data_ptr(), self._hs.data_ptr(), self._seq, st), "ultr_dnn_eval_set")
+            return
+        nm, nt = len(self.metrics), len(self.topn)
+        for start in range(0, nq, self.B):
+            b = min(self.B, nq - start)
+            ids, lab = self.docids.view(-1)[:self.L * b].view(self.L, b), self.labels.view(-1)[:self.L * b].view(self.L, b)
+            _lib.check(self._lib.ultr_eval_pick(rd.lists.data_ptr(), rd.labels.data_ptr(), nq, rd.lmax, rd.n_docs, start, b, self.L,
+                                                ids.data_ptr(), lab.data_ptr(), None, st), "ultr_eval_pick")
+            ev = self._chunk_engine(b)
+            scores, _ = ev.run(params, rd.features, rd.n_docs, ids, lab)
+            means = ev.metric_out if ev._all else ev.ndcg
+            if sa is not None:
+                sa[start:start + b].copy_(scores)
+            if pq is not None:
+                pq[start:start + b].copy_((ev.metric_ws if ev._all else ev.ndcg_ws).view(b, nm, nt))
+            flags = (_lib.EVAL_RESET if start == 0 else 0) | (_lib.EVAL_FINISH if start + b >= nq else 0)
+            _lib.check(self._lib.ultr_eval_accumulate(means.data_ptr(), self.n_values, b, self.acc.data_ptr(), flags, self._hs.data_ptr(),
+                                                      self._seq, st), "ultr_eval_accumulate")
+
+    def read(self, timeout_s=60.0):
+        """{metric: float64 [n_topn]} of the LAST run(), merged over the set - from the report in host-mapped memory."""
+        seq, u, spins, t0 = self._seq, self._hs_u, 0, None
+        if seq == 0:
+            raise RuntimeError("read() before the first run()")
+        word = _lib.EVAL_SEQ_BYTE // 4
+        while int(u[word]) != seq:
+            spins += 1
+            if spins & 0x3FF == 0:
+                now = time.perf_counter()
+                t0 = now if t0 is None else t0
+                if now - t0 > timeout_s:
+                    raise _lib.UltrHipError("no evaluation report from the GPU within %.0f s" % timeout_s)
+        nt = len(self.topn)
+        vals = self._hs_d[:self.n_values].copy()
+        return {m: vals[k * nt:(k + 1) * nt] for k, m in enumerate(self.metrics)}
+
+
 def _setrank_draw(list_size):
     """The reference's SetRank.build shuffles an index list on EVERY forward and never uses it (SetRank.py:245-246), but the
     call advances Python's global `random` stream - the one ClickSimulationFeed draws queries and clicks from.  Consuming

@@ -8,3 +8,4 @@ from .stochastic_online_simulation_feed import StochasticOnlineSimulationFeed  #
 from .deterministic_online_simulation_feed import DeterministicOnlineSimulationFeed  # noqa: F401
 from .device_online_simulation_feed import (DeviceOnlineSimulationFeed, DeviceStochasticOnlineSimulationFeed,  # noqa: F401
                                             DeviceDeterministicOnlineSimulationFeed)
+from .device_direct_label_feed import DeviceDirectLabelFeed  # noqa: F401

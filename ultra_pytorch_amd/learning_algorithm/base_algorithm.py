@@ -12,12 +12,13 @@ The hot path — gather + DNN forward, the loss, DNN backward, clip, optimizer, 
 reference's bookkeeping.  There is no CPU path: constructing an algorithm without a GPU raises.
 """
 import collections
+import copy
 
 import numpy as np
 import torch
 
 from .. import engine
-from ..utils import find_class
+from ..utils import find_class, merge_Summary
 from ..utils import metrics as metrics_mod
 
 
@@ -230,3 +231,51 @@ class BaseAlgorithm(object):
                 for n, v in zip(topn, values):
                     self.eval_summary["%s_%d" % (metric, n)] = float(v)
         return None, self.output, self.eval_summary
+
+    # ---- a whole validation / test set (main.py:85-227 validate loop, :230-292 test loop) -----------------------------------
+    def validation_set(self, feed, data_set, want_scores=False, per_query=False, data_format="ULTRA"):
+        """The driver's evaluation of a whole set: (summary, scores or None, per_query or None).  summary has validation()'s
+        eval_summary keys, merged over the set as utils.merge_Summary merges the per-batch dicts (batch-size weighted); scores
+        [n_queries, max_candidate_num] (device, unmasked) with want_scores; per_query [n_queries, n_metrics, n_topn] (device, the
+        per-list metric values in the order of exp_settings["metrics"]) with per_query.
+
+        With a feed that keeps the dataset in HBM (input_layer.DeviceDirectLabelFeed) the set is queued from one call
+        (engine.EvalSetEngine): per batch the launches validation() issues, the merge in double on the device, ONE host read - the same
+        figures, bit for bit.  A list beyond the metric launch's LDS budget (engine.metrics_fit), a metric key outside
+        engine.METRIC_IDS or any other feed keep the per-batch loop over feed.get_next_batch + validation() (per_query is None there)."""
+        if self.model.training:
+            self.model.eval()
+        L = self.max_candidate_num
+        topn = [int(t) for t in self.exp_settings["metrics_topn"]]
+        wanted = tuple(dict.fromkeys(self.exp_settings["metrics"]))
+        on_device = (hasattr(feed, "resident") and int(getattr(feed, "rank_list_size", -1)) == L and len(wanted) > 0
+                     and len(topn) > 0 and engine.metrics_fit(L) and all(m in engine.METRIC_IDS for m in wanted))
+        if not on_device:
+            it, summaries, sizes, rows = 0, [], [], []
+            while it < len(data_set.initial_list):
+                input_feed, info_map = feed.get_next_batch(it, data_set, check_validation=False, data_format=data_format)
+                _, output, summary = self.validation(input_feed)
+                summaries.append(copy.deepcopy(summary))
+                sizes.append(len(info_map["input_list"]))
+                if want_scores:
+                    rows.append(output[:sizes[-1]])
+                it += sizes[-1]
+            return merge_Summary(summaries, sizes), (torch.cat(rows, dim=0) if want_scores else None), None
+        feed._check(data_set)
+        rd = feed.resident(data_set)
+        key = ("set", int(feed.batch_size), L, tuple(topn), wanted)
+        es = self._eval_engines.get(key)
+        if es is None:
+            es = self._eval_engines[key] = engine.EvalSetEngine(self.model.shape, feed.batch_size, L, self.cuda, topn=topn, metrics=wanted,
+                                                                eval_engine_cls=getattr(self.model, "eval_engine_cls", None))
+            while len(self._eval_engines) > self.MAX_ENGINES:
+                self._eval_engines.popitem(last=False)
+        else:
+            self._eval_engines.move_to_end(key)
+        es.run(self.model.flat_params, rd, want_scores=want_scores, per_query=per_query)
+        summary = {}
+        for metric, values in es.read().items():
+            for n, v in zip(topn, values):
+                summary["%s_%d" % (metric, n)] = float(v)
+        self.eval_summary.update(summary)
+        return summary, (es.scores_all if want_scores else None), (es.per_query if per_query else None)

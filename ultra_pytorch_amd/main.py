@@ -72,7 +72,14 @@ def _set_cutoffs(args, exp_settings):
     print("Users can only see the top %d documents for each query in training." % exp_settings["selection_bias_cutoff"])
 
 
+def _device_label_feed(feed):
+    from .input_layer import DeviceDirectLabelFeed
+    return isinstance(feed, DeviceDirectLabelFeed)
+
+
 def validate_model(model, data_set, feed, data_format):
+    if _device_label_feed(feed):  # the whole set from one call, one host read (BaseAlgorithm.validation_set)
+        return model.validation_set(feed, data_set, data_format=data_format)[0]
     it, summaries, sizes = 0, [], []
     while it < len(data_set.initial_list):
         input_feed, info_map = feed.get_next_batch(it, data_set, check_validation=False, data_format=data_format)
@@ -160,16 +167,20 @@ def test(args, exp_settings):
     test_set.pad(exp_settings["max_candidate_num"])
     model = create_model(args, exp_settings, test_set)
     feed = utils.find_class(exp_settings["test_input_feed"])(model, args.batch_size, exp_settings["test_input_hparams"])
-    it, rerank_scores, summaries, sizes = 0, [], [], []
-    while it < len(test_set.initial_list):
-        input_feed, info_map = feed.get_next_batch(it, test_set, check_validation=False)
-        _, output_logits, summary = model.validation(input_feed)
-        summaries.append(copy.deepcopy(summary))
-        sizes.append(len(info_map["input_list"]))
-        rows = output_logits.detach().cpu().tolist()
-        rerank_scores.extend(rows[: sizes[-1]])
-        it += sizes[-1]
-    test_summary = utils.merge_Summary(summaries, sizes)
+    if _device_label_feed(feed):  # the whole set from one call; the scores come back in ONE device-to-host copy
+        test_summary, scores, _ = model.validation_set(feed, test_set, want_scores=True)
+        rerank_scores = scores.cpu().tolist()
+    else:
+        it, rerank_scores, summaries, sizes = 0, [], [], []
+        while it < len(test_set.initial_list):
+            input_feed, info_map = feed.get_next_batch(it, test_set, check_validation=False)
+            _, output_logits, summary = model.validation(input_feed)
+            summaries.append(copy.deepcopy(summary))
+            sizes.append(len(info_map["input_list"]))
+            rows = output_logits.detach().cpu().tolist()
+            rerank_scores.extend(rows[: sizes[-1]])
+            it += sizes[-1]
+        test_summary = utils.merge_Summary(summaries, sizes)
     print("  eval: %s" % " ".join("%s:%.3f" % kv for kv in test_summary.items()))
     os.makedirs(args.output_dir, exist_ok=True)
     utils.output_ranklist(test_set, rerank_scores, args.output_dir, args.test_data_prefix)
