@@ -209,6 +209,12 @@ int ultr_regem_loss(const float* scores, const float* labels, const float* prope
  * including its explosion where x rounds to 1 and its NaN where exp overflows in the lower triangle. */
 int ultr_prs_loss(const float* scores, const float* labels, const float* ipw_table, int32_t n_ipw, float sigma,
                   int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
+/* The same with a weight per list entry (additive within ABI 8): ipw_bl [B, L], indexed by PRESENTATION position, replaces
+ * ipw_table[min(l, n_ipw-1)] - the weights of an estimator that looks at the list's clicks (ultr_history_pw, all_positions = 1).
+ * Everything else, pw = 1/ipw (0 where ipw == 0) included, is ultr_prs_loss.  ultr_train_step with ULTR_ALGO_PRS takes this path
+ * when ultr_step_args::pw is set.  ULTR_E_BADARG: a missing pointer, batch <= 0, list_size <= 0. */
+int ultr_prs_loss_pw(const float* scores, const float* labels, const float* ipw_bl, float sigma, int32_t batch, int32_t list_size,
+                     float* dscores, void* loss_ws, void* stream);
 
 /* ---- PDGD: Pairwise Differentiable Gradient Descent (online) ---------------------------
  * Replaces PDGD.train's pair construction and loss (pdgd.py:107-205) over the list_size positions the forward scored
@@ -323,7 +329,8 @@ int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* 
  * call (what `model.train(input_feed)` does between marshalling the feed and `loss.item()`).  A data-parallel
  * caller sets skip_update, all-reduces `grads`, then calls ultr_grad_sumsq + ultr_apply_update itself.
  * aux: prop_params (DLA) or [t_plus | t_minus] (PairDebias / LambdaRank) or propensity [L] (RegressionEM) or NULL.
- * ipw_table / n_ipw: the IPW_list of IPW (SOFTMAX) and PRS.  sigma: LambdaRank and PRS.
+ * ipw_table / n_ipw: the IPW_list of IPW (SOFTMAX) and PRS; pw: explicit [B, L] weights instead (SOFTMAX: ultr_softmax_ce's pw;
+ * PRS: ultr_prs_loss_pw's ipw_bl).  sigma: LambdaRank and PRS.
  * PDGD (no IPW table, no sigma): sigma carries tau and n_ipw the cutoff (selection_bias_cutoff); docids / n_docs mark
  * the PADs. */
 typedef struct ultr_step_args {
@@ -640,6 +647,26 @@ typedef struct ultr_propensity_args {
   unsigned long long* click_count;
 } ultr_propensity_args;
 int ultr_propensity_count(const ultr_propensity_args* a, void* stream);
+
+/* ---- per-click weights of a click model with a click history (ultr_history_pw.hip; additive within ABI 8) ---------------------
+ * Counterpart of OraclePropensityEstimator.getPropensityForOneList on a user-browsing model (propensity_estimator.py:149-180,
+ * click_models.py:151-162), whose weight at a position depends on where the previous click of the same list was.
+ *   labels [L, B] clicks (> 0 = clicked);  table [L][L] row-major: row = position, column = position of the last click before it + 1
+ *   (column 0: no click so far; entries beyond the diagonal are never read);  pw_out [B, L].
+ * With last(b, l) = the largest l' < l with labels[l', b] > 0, or -1:
+ *   pw_out[b, l] = (all_positions || labels[l, b] > 0) ? table[l * L + last(b, l) + 1] : 0
+ * all_positions = 0: IPWrank (getPropensityForOneList(click_list)); 1: PRSrank (use_non_clicked_data=True).  The table is the
+ * host's (OraclePropensityEstimator.weight_table: the model's own expression per entry, rounded to float32 once), the launch only
+ * looks up: the weights are the reference's bit for bit.  Lists of up to 32 positions are packed 8 / 4 / 2 to a wavefront.  No
+ * atomics, no dependence on the launch geometry, any list_size >= 1.
+ * ULTR_E_BADARG: a NULL argument block or pointer, batch <= 0, list_size <= 0, all_positions outside {0, 1}.  Launches nothing then. */
+typedef struct ultr_history_pw_args {
+  const float* labels;
+  const float* table;
+  float* pw_out;
+  int32_t batch, list_size, all_positions, pad_;
+} ultr_history_pw_args;
+int ultr_history_pw(const ultr_history_pw_args* a, void* stream);
 
 /* ---- a whole validation / test set from a RESIDENT dataset (ultr_eval.hip; additive within ABI 8) -----------------------------------
  * Counterpart of the driver's evaluation loop (main.py:85-227 validate, :230-292 test): DirectLabelFeed.get_next_batch per batch

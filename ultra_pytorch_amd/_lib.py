@@ -79,6 +79,11 @@ class PropensityArgs(ctypes.Structure):  # ultr_propensity_args (ultr_propensity
                 ("first_session", ctypes.c_uint64), ("n_sessions", c_i64), ("click_count", c_vp)]
 
 
+class HistoryPwArgs(ctypes.Structure):  # ultr_history_pw_args (ultr_history_pw)
+    _fields_ = [("labels", c_vp), ("table", c_vp), ("pw_out", c_vp), ("batch", c_i32), ("list_size", c_i32), ("all_positions", c_i32),
+                ("pad_", c_i32)]
+
+
 PROPENSITY_MAX_L = 128  # include/ultr_hip.h: ULTR_PROPENSITY_MAX_L
 EVAL_RESET, EVAL_FINISH, EVAL_SEQ_BYTE = 1, 2, 129 * 8  # include/ultr_hip.h: ULTR_EVAL_*
 
@@ -124,6 +129,7 @@ SIGNATURES = {
     "ultr_pairdebias_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_lambdarank_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_prs_loss": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ultr_prs_loss_pw": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_pdgd_loss": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_regem_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "ultr_setrank_param_count": (c_i64, [ctypes.POINTER(SetRankDesc)]),
@@ -149,6 +155,7 @@ SIGNATURES = {
     "ultr_nsgd_noise_args": (c_i32, [c_vp, c_vp]),
     "ultr_nsgd_memory_args": (c_i32, [c_vp, c_vp]),
     "ultr_propensity_count": (c_i32, [c_vp, c_vp]),
+    "ultr_history_pw": (c_i32, [c_vp, c_vp]),
     "ultr_comm_create": (c_i32, [c_i32, c_i32, c_i64, ctypes.POINTER(c_vp)]),
     "ultr_comm_export": (c_i32, [c_vp, c_vp]),
     "ultr_comm_import": (c_i32, [c_vp, c_i32, c_vp]),

@@ -4,7 +4,8 @@
 // counting (ties broken by original index), then PRS_JW waves each walk a slice of the partner positions c for every sorted
 // position r; the two partial sums per position (d loss / d sorted score, loss) are combined in fixed order through LDS.
 // Only the pairs i < j of the sorted order carry loss (triu(., 1)); the weights are indexed by PRESENTATION position and
-// gathered into score order:  prs_ij = ipw_i * pw_j,  pw = ipw == 0 ? 0 : 1 / ipw  (use_non_clicked_data=True).
+// gathered into score order:  prs_ij = ipw_i * pw_j,  pw = ipw == 0 ? 0 : 1 / ipw  (use_non_clicked_data=True).  The ipw of a
+// position is the table's, or - ultr_prs_loss_pw - this list's own entry of a [B, L] array (an estimator that reads the clicks).
 //
 // Numerics follow autograd through the reference's composition, quirks included:
 //   x = 1 / (exp(-sigma s_ij) + 1) with the reciprocal-of-exp chain (no logistic shortcut), F.binary_cross_entropy with each
@@ -33,7 +34,7 @@
 __global__ __launch_bounds__(LPW * PRS_JW * 64) void prs_loss_kernel(const float* __restrict__ scores,
                                                                     const float* __restrict__ labels,
                                                                     const float* __restrict__ ipw_table, int n_ipw,
-                                                                    float sigma, int B, int L, float* __restrict__ dscores,
+                                                                    const float* __restrict__ ipw_bl, float sigma, int B, int L, float* __restrict__ dscores,
                                                                     float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tail = (int)ultr_tail_len(L);
@@ -81,7 +82,8 @@ __global__ __launch_bounds__(LPW * PRS_JW * 64) void prs_loss_kernel(const float
         ry += (yj > yi || (yj == yi && j < i)) ? 1 : 0;
       }
       // getPropensityForOneList(..., use_non_clicked_data=True): IPW_list[min(l, len - 1)] for every position (prs_rank.py:114)
-      const float ipw = ipw_table[i < n_ipw ? i : n_ipw - 1];
+      // ipw_bl: the estimator looked at this list's clicks (ultr_history_pw), a weight per entry [B, L]
+      const float ipw = ipw_bl != nullptr ? ipw_bl[(int64_t)b * L + i] : ipw_table[i < n_ipw ? i : n_ipw - 1];
       pos[i] = rs;
       ps[rs] = si;
       ls[rs] = yi;
@@ -164,10 +166,8 @@ static size_t prs_lds_bytes(int32_t list_size) {
   return ((size_t)LPW * (tail + 8 * (size_t)list_size) + list_size + (size_t)LPW * PRS_JW * list_size * 2) * sizeof(float);
 }
 
-extern "C" int ultr_prs_loss(const float* scores, const float* labels, const float* ipw_table, int32_t n_ipw, float sigma,
-                             int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream) {
-  if (!scores || !labels || !ipw_table || n_ipw <= 0 || !dscores || !loss_ws || batch <= 0 || list_size <= 0)
-    return ULTR_E_BADARG;
+static int prs_launch(const float* scores, const float* labels, const float* ipw_table, int32_t n_ipw, const float* ipw_bl,
+                      float sigma, int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream) {
   const size_t lds = prs_lds_bytes(list_size);
   if (lds > 160 * 1024) return ULTR_E_UNSUPPORTED;
   if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(prs_loss_kernel),
@@ -175,6 +175,19 @@ extern "C" int ultr_prs_loss(const float* scores, const float* labels, const flo
     return ULTR_E_UNSUPPORTED;
   UltrProfScope prof(ULTR_K_LOSS, (hipStream_t)stream);
   ULTR_LAUNCH(prof, prs_loss_kernel, dim3((unsigned)ultr_loss_parts(batch)), dim3(LPW * PRS_JW * 64), lds, (hipStream_t)stream,
-              scores, labels, ipw_table, (int)n_ipw, sigma, (int)batch, (int)list_size, dscores, (float*)loss_ws);
+              scores, labels, ipw_table, (int)n_ipw, ipw_bl, sigma, (int)batch, (int)list_size, dscores, (float*)loss_ws);
   return (int)hipGetLastError();
+}
+
+extern "C" int ultr_prs_loss(const float* scores, const float* labels, const float* ipw_table, int32_t n_ipw, float sigma,
+                             int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream) {
+  if (!scores || !labels || !ipw_table || n_ipw <= 0 || !dscores || !loss_ws || batch <= 0 || list_size <= 0)
+    return ULTR_E_BADARG;
+  return prs_launch(scores, labels, ipw_table, n_ipw, nullptr, sigma, batch, list_size, dscores, loss_ws, stream);
+}
+
+extern "C" int ultr_prs_loss_pw(const float* scores, const float* labels, const float* ipw_bl, float sigma, int32_t batch,
+                                int32_t list_size, float* dscores, void* loss_ws, void* stream) {
+  if (!scores || !labels || !ipw_bl || !dscores || !loss_ws || batch <= 0 || list_size <= 0) return ULTR_E_BADARG;
+  return prs_launch(scores, labels, nullptr, 0, ipw_bl, sigma, batch, list_size, dscores, loss_ws, stream);
 }

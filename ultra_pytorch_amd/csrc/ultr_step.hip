@@ -102,8 +102,11 @@ extern "C" int ultr_train_step(const ultr_step_args* a, void* stream) {
                                 a->list_size, a->dscores, a->loss_ws, stream);
       break;
     case ULTR_ALGO_PRS:
-      rc = ultr_prs_loss(a->scores, a->labels, a->ipw_table, a->n_ipw, a->sigma, a->batch, a->list_size, a->dscores,
-                         a->loss_ws, stream);
+      // pw: a weight per list entry (an estimator that reads the list's clicks) instead of the position table
+      rc = a->pw != nullptr
+               ? ultr_prs_loss_pw(a->scores, a->labels, a->pw, a->sigma, a->batch, a->list_size, a->dscores, a->loss_ws, stream)
+               : ultr_prs_loss(a->scores, a->labels, a->ipw_table, a->n_ipw, a->sigma, a->batch, a->list_size, a->dscores,
+                               a->loss_ws, stream);
       break;
     case ULTR_ALGO_PDGD:
       rc = ultr_pdgd_loss(a->scores, a->labels, a->docids, a->n_docs, a->sigma, a->n_ipw, a->batch, a->list_size, a->dscores,

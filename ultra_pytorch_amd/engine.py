@@ -134,9 +134,12 @@ class StepEngine:
         elif self.algo == "lambdarank":
             hip_ops.lambdarank_loss(self.scores, labels, aux[:L], aux[L:], self.sigma, B, L, self.dscores, self.loss_ws)
         elif self.algo == "prs":
-            if ipw_table is None:
-                raise ValueError("PRSrank's loss needs the IPW table (ipw_table=)")
-            hip_ops.prs_loss(self.scores, labels, ipw_table, self.sigma, B, L, self.dscores, self.loss_ws)
+            if pw is not None:  # a weight per list entry [B, L] (hip_ops.history_pw) instead of the position table
+                hip_ops.prs_loss_pw(self.scores, labels, pw, self.sigma, B, L, self.dscores, self.loss_ws)
+            elif ipw_table is None:
+                raise ValueError("PRSrank's loss needs the IPW table (ipw_table=) or per-entry weights (pw=)")
+            else:
+                hip_ops.prs_loss(self.scores, labels, ipw_table, self.sigma, B, L, self.dscores, self.loss_ws)
         elif self.algo == "pdgd":
             if docids is None or n_docs is None:
                 raise ValueError("PDGD's loss needs the docids and n_docs (its PADs)")

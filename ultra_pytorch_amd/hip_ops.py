@@ -310,6 +310,12 @@ def prs_loss(scores, labels, ipw_table, sigma, B, L, dscores, loss_ws):
                                     _p(dscores), _p(loss_ws), _stream()), "ultr_prs_loss")
 
 
+def prs_loss_pw(scores, labels, ipw_bl, sigma, B, L, dscores, loss_ws):
+    """PRSrank with a weight per list entry: ipw_bl [B, L] (presentation order) instead of the position table (history_pw)."""
+    check(_lib.load().ultr_prs_loss_pw(_p(scores), _p(labels), _p(ipw_bl), float(sigma), int(B), int(L), _p(dscores), _p(loss_ws),
+                                       _stream()), "ultr_prs_loss_pw")
+
+
 def pdgd_loss(scores, labels, docids, n_docs, tau, cutoff, B, L, dscores, loss_ws):
     """PDGD: the pairs of clicked documents with lower-labelled ones above them (or just below), each weighted by the
     Plackett-Luce probability ratio of the swapped ranking; docids [L, B] int32 mark the PADs (== n_docs)."""
@@ -349,3 +355,17 @@ def propensity_count(labels, lengths, exam, n_exam, cprob, click_model, seed, fi
     a.click_model, a.seed, a.first_session, a.n_sessions = int(click_model), int(seed), int(first_session), int(n_sessions)
     a.click_count = click_count.data_ptr()
     check(_lib.load().ultr_propensity_count(ctypes.byref(a), _stream()), "ultr_propensity_count")
+
+
+def history_pw(labels, table, pw_out, all_positions, args=None):
+    """pw_out [B, L] = the weights of a click model with a click history (ultr_history_pw): labels [L, B] clicks, table [L, L] from
+    OraclePropensityEstimator.weight_table; all_positions False: clicked positions only (IPWrank), True: every position (PRSrank).
+    Queued on the current stream.  args: a _lib.HistoryPwArgs the caller keeps between calls (a step loop: no struct per step)."""
+    _req(labels, torch.float32, "labels"), _req(table, torch.float32, "table"), _req(pw_out, torch.float32, "pw_out")
+    L, B = labels.shape
+    if tuple(table.shape) != (L, L) or tuple(pw_out.shape) != (B, L):
+        raise ValueError("history_pw: labels [L, B] needs table [L, L] and pw_out [B, L]")
+    a = _lib.HistoryPwArgs() if args is None else args
+    a.labels, a.table, a.pw_out = labels.data_ptr(), table.data_ptr(), pw_out.data_ptr()
+    a.batch, a.list_size, a.all_positions = int(B), int(L), 1 if all_positions else 0
+    check(_lib.load().ultr_history_pw(ctypes.byref(a), _stream()), "ultr_history_pw")

@@ -1,7 +1,7 @@
 """Inverse-propensity tables (reference ultra/utils/propensity_estimator.py): a JSON file with "IPW_list", loaded by IPWrank and
 PRSrank, and the estimators that make one: RandomizedPropensityEstimator runs the reference's randomized click experiment
 (:95-132) on the GPU (ultr_propensity_count: the session loop, the shuffle and the click histogram are one HIP kernel), the
-OraclePropensityEstimator (:149-180) answers from the click model itself.
+OraclePropensityEstimator (:149-180) answers from the click model itself (weight_table: what IPWrank / PRSrank upload).
 
     python -m ultra_pytorch_amd.utils.propensity_estimator <click_model.json> <data_dir> <output_dir> [--sessions N] [--seed S]
 
@@ -105,14 +105,56 @@ class RandomizedPropensityEstimator(BasicPropensityEstimator):
 
 
 class OraclePropensityEstimator(BasicPropensityEstimator):
-    """The click model's own weights (:149-180): no table, no estimation."""
+    """The click model's own weights (:149-180): no table to estimate.  Built from a click-model object or from the path of a JSON
+    file with a "click_model" entry - what outputEstimatorToFile writes, and what a randomized_*.json carries next to its table.
+    (Changed: the reference's find_class(type)(json_path) hands the file NAME to the constructor as its click model)
+
+    An examination probability of 0 at an entry a list can reach raises ValueError here: the step would divide by it."""
 
     def __init__(self, click_model):
-        self.click_model = click_model
+        if isinstance(click_model, (str, bytes, os.PathLike)):
+            self.loadEstimatorFromFile(os.fspath(click_model))
+        else:
+            self.click_model = click_model
+            if click_model is not None:  # (None: an empty estimator for loadEstimatorFromFile, as the base class allows)
+                self._check()
 
     def loadEstimatorFromFile(self, file_name):
         with open(file_name) as f:
-            self.click_model = CM.loadModelFromJson(json.load(f)["click_model"])
+            data = json.load(f)
+        if "click_model" not in data:
+            raise KeyError("%s has no \"click_model\" entry: OraclePropensityEstimator needs the click model itself" % file_name)
+        self.click_model = CM.loadModelFromJson(data["click_model"])
+        self._check()
+
+    def _check(self):
+        name = getattr(self.click_model, "model_name", None)
+        if name not in CLICK_MODEL_IDS:
+            raise NotImplementedError("OraclePropensityEstimator answers for the position-biased, the cascade and the user-browsing "
+                                      "model (got %r)" % name)
+        ep = self.click_model.exam_prob
+        used = [x for row in ep for x in row] if name == "user_browsing_model" else list(ep)
+        if any(float(x) == 0.0 for x in used):
+            raise ValueError("the click model has an examination probability of 0: its inverse propensity weight is undefined")
+
+    def weight_table(self, list_size):
+        """The weights of every list of `list_size` positions as float32 numpy, each entry the reference's own expression in Python
+        floats rounded to float32 once (what torch.as_tensor(list of floats) does, ipw_rank.py:138, prs_rank.py:116):
+          position-biased / cascade: ("position", w[list_size]),            w[r] = 1.0 / getExamProb(r) * getExamProb(0)
+          user-browsing:             ("history", w[list_size, list_size]),  w[r][c] = 1.0 / getExamProb(r, c - 1) for c <= r, else 0
+        (row = rank, column = rank of the last click before it + 1, column 0 = no click so far).  getExamProb fills the table, so
+        its rules for ranks beyond the model's rows (click_models.py:174-185) are expanded here and the GPU only looks up."""
+        import numpy as np
+        cm, L = self.click_model, int(list_size)
+        if L <= 0:
+            raise ValueError("list_size must be positive")
+        if cm.model_name == "user_browsing_model":
+            w = np.zeros((L, L), np.float32)
+            for r in range(L):
+                for c in range(r + 1):
+                    w[r, c] = np.float32(1.0 / cm.getExamProb(r, c - 1))
+            return "history", w
+        return "position", np.asarray([1.0 / cm.getExamProb(r) * cm.getExamProb(0) for r in range(L)], np.float32)
 
     def getPropensityForOneList(self, click_list, use_non_clicked_data=False):
         return self.click_model.estimatePropensityWeightsForOneList(click_list, use_non_clicked_data)
