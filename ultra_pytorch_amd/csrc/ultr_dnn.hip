@@ -775,12 +775,13 @@ bool ultr_wgrad_h3_geometry(int64_t T, int M, int K, int* nsplit, int* rows_per_
 static int backward_impl(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs,
                          const int32_t* docids, int32_t batch, int32_t list_size, const void* saved, const float* dscores,
                          const void* loss_ws, void* bwd_ws, float* grads, void* stream, FusedSoftmax fl,
-                         int fused_rb = 0 /* > 0: the fused forward+backward kernel ran with this many rows per block;
+                         StepCtx* ctx /* the step in flight (ultr_plan.h); nullptr: a stand-alone call */, int fused_rb = 0 /* > 0: the fused forward+backward kernel ran with this many rows per block;
                                              only the weight gradients and the reduction remain */) {
   if (!params || !docids || !saved || (!dscores && !fl.scores) || !bwd_ws || !grads || batch <= 0 || list_size <= 0 ||
       n_docs < 0 || (n_docs > 0 && !features))
     return ULTR_E_BADARG;
   const int64_t N = (int64_t)batch * list_size;
+  const float* wt = ctx ? ctx->wt : nullptr;  // the weight copies of the step: the public ultr_dnn_backward has no such argument
   DnnPlan p;
   BwdPlan bp;
   if (!ultr_make_dnn_plan(d, N, &p) || !ultr_make_bwd_plan(p, N, &bp)) return ULTR_E_BADARG;
@@ -807,7 +808,7 @@ static int backward_impl(const ultr_dnn_desc* d, const float* params, const floa
   bp.wg_prenorm = (fused_rb > 0) ? 1 : 0;  // the fused kernel left the ready-made wgrad operands in `saved`
   WideBwd wb;
   size_t wblds = 0;
-  const bool wide = fused_rb == 0 && dscores != nullptr && av && l0g_ok && g_ultr_step_wt != nullptr && ((uintptr_t)g_ultr_step_wt & 15) == 0 &&
+  const bool wide = fused_rb == 0 && dscores != nullptr && av && l0g_ok && wt != nullptr && ((uintptr_t)wt & 15) == 0 &&
                     bwd_wide_plan(p, N, &wb, &wblds);
   if (fused_rb > 0) {
     // the row-local half already ran inside dnn_fb_kernel
@@ -815,18 +816,18 @@ static int backward_impl(const ultr_dnn_desc* d, const float* params, const floa
     UltrProfScope prof(ULTR_K_BWD, st);
     bp.rblk = wb.R;
     bp.nrb = (int)((N + wb.R - 1) / wb.R);  // one vector slab per workgroup
-    const int rcw = ultr_launch_dnn_bwdw(prof, p, bp, wb, wblds, st, (const float*)saved, dscores, ws, g_ultr_step_wt);
+    const int rcw = ultr_launch_dnn_bwdw(prof, p, bp, wb, wblds, st, (const float*)saved, dscores, ws, wt);
     if (rcw) return rcw;
   } else if (big) {
     UltrProfScope prof(ULTR_K_BWD, st);
     bp.nrb = (int)((N + ULTR_BIG_ROWS - 1) / ULTR_BIG_ROWS);  // one vector slab per row block of the row kernels
     const int rc = ultr_dnn_big_backward(p, bp, params, (const float*)saved, dscores, ws, st, prof.on ? prof.a : nullptr,
-                                         prof.on ? prof.b : nullptr, knobs().bwd_h3 != 0 && !p.no_h3 && g_ultr_step_wt != nullptr);
+                                         prof.on ? prof.b : nullptr, knobs().bwd_h3 != 0 && !p.no_h3 && wt != nullptr);
     if (rc) return rc;
   } else if (v2) {
     UltrProfScope prof(ULTR_K_BWD, st);
     const int rc2 = ultr_launch_dnn_bwd2(prof, p, bp, lds2, st, params, features, n_docs, docids, (int)batch, (int)list_size, (const float*)saved,
-                                         dscores, ws, fl, g_ultr_step_wt);
+                                         dscores, ws, fl, wt);
     if (rc2) return rc2;
   } else {
     UltrProfScope prof(ULTR_K_BWD, st);
@@ -844,44 +845,30 @@ static int backward_impl(const ultr_dnn_desc* d, const float* params, const floa
     bp.lf_len = len;
     bp.lf_chunks = (nlp + len - 1) / len;
   }
-  if (bp.wg_h3) {
+  {
     UltrProfScope prof(ULTR_K_WGRAD, st);
-    const dim3 wgrid(bp.wgrad_blocks + bp.vred_blocks + (bp.lf_chunks > 0 ? bp.lf_chunks : 1));
-    EarlyReport er = g_ultr_early;
-    CommDev cd;
-    memset(&cd, 0, sizeof(cd));
-    if (g_ultr_step_xchg.comm != nullptr && g_ultr_step_xchg.er.host != nullptr && bp.lf_chunks == 0 &&
-        ultr_comm_dev(g_ultr_step_xchg.comm, g_ultr_step_xchg.step, p.P + tail, &cd)) {
-      er = g_ultr_step_xchg.er;  // (see the register kernel's launch below)
-      g_ultr_step_xchg.er.host = nullptr;
-    } else {
-      cd.world = 0;
+    size_t wlds = 0;  // (the split-half kernel's LDS is static)
+    if (!bp.wg_h3) {
+      int maxrps = 0;
+      for (int j = 0; j < p.nl - 1; ++j) maxrps = bp.wl[j].rows_per_split > maxrps ? bp.wl[j].rows_per_split : maxrps;
+      wlds = (size_t)(4 * 64 * 64 + 4 * 64 + maxrps) * sizeof(float);
     }
-    if (bp.lf_chunks > 0) er.host = nullptr;
-    const int rcg = ultr_launch_dnn_wgrad(prof, p, bp, av, true, 0, wgrid, st, params, features, n_docs, docids, (int)batch, (int)list_size,
-                                          (const float*)saved, ws, 0, grads, lp, nlp, tail, er, cd);
-    if (rcg) return rcg;
-  } else {
-    UltrProfScope prof(ULTR_K_WGRAD, st);
-    int maxrps = 0;
-    for (int j = 0; j < p.nl - 1; ++j) maxrps = bp.wl[j].rows_per_split > maxrps ? bp.wl[j].rows_per_split : maxrps;
-    const size_t wlds = (size_t)(4 * 64 * 64 + 4 * 64 + maxrps) * sizeof(float);
     const dim3 wgrid(bp.wgrad_blocks + bp.vred_blocks + (bp.lf_chunks > 0 ? bp.lf_chunks : 1));
-    EarlyReport er = g_ultr_early;
+    EarlyReport er = ctx ? ctx->early : EarlyReport{nullptr, 0u, 0, 1.0f};
     CommDev cd;
     memset(&cd, 0, sizeof(cd));  // world 0: not a data-parallel step
-    if (g_ultr_step_xchg.comm != nullptr && g_ultr_step_xchg.er.host != nullptr && bp.lf_chunks == 0 &&
-        ultr_comm_dev(g_ultr_step_xchg.comm, g_ultr_step_xchg.step, p.P + tail, &cd)) {
+    if (ctx && ctx->comm != nullptr && ctx->early_dp.host != nullptr && bp.lf_chunks == 0 &&
+        ultr_comm_dev(ctx->comm, ctx->comm_step, p.P + tail, &cd)) {
       // data-parallel step: the workgroup that folds the loss partials exchanges the head of the tail with the peers and reports
       // the loss NOW; the gradient exchange behind this launch then has nothing to report
-      er = g_ultr_step_xchg.er;
-      g_ultr_step_xchg.er.host = nullptr;
+      er = ctx->early_dp;
+      ctx->early_dp.host = nullptr;
     } else {
       cd.world = 0;
     }
     if (bp.lf_chunks > 0) er.host = nullptr;  // two-level fold of > 1024 partials: the loss is only final in the reduction launch
-    const int rcg = ultr_launch_dnn_wgrad(prof, p, bp, av, false, wlds, wgrid, st, params, features, n_docs, docids, (int)batch, (int)list_size,
-                                          (const float*)saved, ws, (vm >> 31) & 1, grads, lp, nlp, tail, er, cd);
+    const int rcg = ultr_launch_dnn_wgrad(prof, p, bp, av, bp.wg_h3 != 0, wlds, wgrid, st, params, features, n_docs, docids, (int)batch,
+                                          (int)list_size, (const float*)saved, ws, bp.wg_h3 ? 0 : (vm >> 31) & 1, grads, lp, nlp, tail, er, cd);
     if (rcg) return rcg;
   }
   RedPlan rp;
@@ -896,30 +883,33 @@ static int backward_impl(const ultr_dnn_desc* d, const float* params, const floa
     const int np = rp.seg[k].len > 4096 ? rp.seg[k].nparts : (rp.seg[k].nparts + 3) / 4;
     maxparts = np > maxparts ? np : maxparts;
   }
-  if (g_ultr_step_xchg.comm != nullptr && maxparts <= 32 && bp.lf_chunks == 0) {
+  if (ctx && ctx->comm != nullptr && maxparts <= 32 && bp.lf_chunks == 0) {
     // data-parallel step: this launch exchanges its own output (grad_reduce_xchg_kernel); ultr_train_step then skips the exchange kernel
     CommDev cd;
-    if (ultr_comm_dev(g_ultr_step_xchg.comm, g_ultr_step_xchg.step, p.P + tail, &cd)) {
-      int nx = 0;
-      const int rcx = ultr_launch_grad_reduce_xchg(prof, rp, p, bp, tail, nblk, cd, g_ultr_step_xchg.er, st, ws, grads, &nx);
+    if (ultr_comm_dev(ctx->comm, ctx->comm_step, p.P + tail, &cd)) {
+      const int rcx = ultr_launch_grad_reduce_xchg(prof, rp, p, bp, tail, nblk, cd, ctx->early_dp, st, ws, grads, &ctx->nsq2);
       if (rcx) return rcx;
-      g_ultr_step_xchg.done = true;
-      g_ultr_step_nsq2 = nx;
+      ctx->xchg_done = true;
       return 0;
     }
   }
   int nsq2 = 0;
   const int rcr = ultr_launch_grad_reduce(prof, rp, p, bp, tail, nblk, maxparts, st, ws, grads, &nsq2);
   if (rcr) return rcr;
-  if (nsq2 > 0) g_ultr_step_nsq2 = nsq2;
+  if (ctx) ctx->nsq2 = nsq2;
   return (int)hipGetLastError();
 }
 
 extern "C" int ultr_dnn_backward(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs,
                                  const int32_t* docids, int32_t batch, int32_t list_size, const void* saved,
                                  const float* dscores, const void* loss_ws, void* bwd_ws, float* grads, void* stream) {
+  return ultr_dnn_backward_ctx(d, params, features, n_docs, docids, batch, list_size, saved, dscores, loss_ws, bwd_ws, grads, stream, nullptr);
+}
+int ultr_dnn_backward_ctx(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs, const int32_t* docids,
+                          int32_t batch, int32_t list_size, const void* saved, const float* dscores, const void* loss_ws, void* bwd_ws,
+                          float* grads, void* stream, StepCtx* ctx) {
   FusedSoftmax fl = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, dscores, loss_ws, bwd_ws, grads, stream, fl);
+  return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, dscores, loss_ws, bwd_ws, grads, stream, fl, ctx);
 }
 
 extern "C" int ultr_dnn_backward_softmax(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs,
@@ -927,6 +917,13 @@ extern "C" int ultr_dnn_backward_softmax(const ultr_dnn_desc* d, const float* pa
                                          const float* scores, const float* labels, const float* pw, const float* ipw_table,
                                          int32_t n_ipw, float* dscores_out, void* loss_ws, void* bwd_ws, float* grads,
                                          void* stream) {
+  return ultr_dnn_backward_softmax_ctx(d, params, features, n_docs, docids, batch, list_size, saved, scores, labels, pw, ipw_table, n_ipw,
+                                       dscores_out, loss_ws, bwd_ws, grads, stream, nullptr);
+}
+int ultr_dnn_backward_softmax_ctx(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs,
+                                  const int32_t* docids, int32_t batch, int32_t list_size, const void* saved, const float* scores,
+                                  const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw, float* dscores_out,
+                                  void* loss_ws, void* bwd_ws, float* grads, void* stream, StepCtx* ctx) {
   if (!scores || !labels || !loss_ws || (ipw_table && n_ipw <= 0)) return ULTR_E_BADARG;
   {
     // big batches take the per-layer backward, which wants the loss as its own stage
@@ -939,17 +936,17 @@ extern "C" int ultr_dnn_backward_softmax(const ultr_dnn_desc* d, const float* pa
     // ... and the wide-tile backward of ultr_train_step (dnn_bwdw_kernel), which takes dscores too
     WideBwd wb0;
     size_t wl0 = 0;
-    const bool wide = planned && g_ultr_step_wt != nullptr && knobs().no_vec == 0 && bwd_wide_plan(p, N, &wb0, &wl0);
+    const bool wide = planned && ctx && ctx->wt != nullptr && knobs().no_vec == 0 && bwd_wide_plan(p, N, &wb0, &wl0);
     if (planned && (wide || ((big_bwd_wanted(p, N) || bwd_lds_bytes(p, bp0.rblk) > 160 * 1024) && knobs().big_bwd != 0 &&
         knobs().no_vec == 0 && ultr_dnn_big_ok(p, N, n_docs)))) {
       const int rc = ultr_softmax_ce(scores, labels, pw, ipw_table, n_ipw, batch, list_size, dscores_out, loss_ws, stream);
       if (rc) return rc;
       FusedSoftmax none = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-      return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, dscores_out, loss_ws, bwd_ws, grads, stream, none);
+      return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, dscores_out, loss_ws, bwd_ws, grads, stream, none, ctx);
     }
   }
   FusedSoftmax fl = {scores, labels, pw, ipw_table, (int)n_ipw, dscores_out, (float*)loss_ws};
-  return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, nullptr, loss_ws, bwd_ws, grads, stream, fl);
+  return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, nullptr, loss_ws, bwd_ws, grads, stream, fl, ctx);
 }
 
 // internal (ultr_train_step): forward + NA/IPW loss + backward for a small batch through dnn_fb_kernel, then the weight
@@ -958,7 +955,7 @@ extern "C" int ultr_dnn_backward_softmax(const ultr_dnn_desc* d, const float* pa
 int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features, int64_t n_docs,
                             const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
                             const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw, float* dscores_out,
-                            void* loss_ws, void* bwd_ws, float* grads, void* stream) {
+                            void* loss_ws, void* bwd_ws, float* grads, void* stream, StepCtx* ctx) {
   if (!params || !wt || !docids || !scores || !saved || !labels || !loss_ws || !bwd_ws || !grads || batch <= 0 ||
       list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features) || (ipw_table && n_ipw <= 0))
     return ULTR_E_BADARG;
@@ -1017,6 +1014,6 @@ int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const f
   if (e != hipSuccess) return (int)e;
   fl.scores = scores;  // marks "loss partials come one per row block" for the reduction
   return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, nullptr, loss_ws, bwd_ws, grads, stream, fl,
-                       rb);
+                       ctx, rb);
 }
 

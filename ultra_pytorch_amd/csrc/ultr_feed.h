@@ -123,10 +123,6 @@ __device__ __forceinline__ void click_draw(const ultr_click_args& ca, int block)
   if (lane == 0 && qidx != nullptr) qidx[b] = (int32_t)q;
 }
 
-
-// the draw that rides on the next update launch of this thread (set by ultr_feed_train_step around ultr_train_step; the update launch
-// that takes it clears the pointer)
-extern thread_local const ultr_click_args* g_ultr_click_rider;
 inline bool ultr_click_args_ok(const ultr_click_args* c) {
   return c && c->lists && c->labels && c->exam_prob && c->click_prob && c->docids && c->clicks && c->n_queries > 0 && c->lmax > 0 && c->batch > 0 &&
          c->list_size > 0 && c->n_exam > 0 && c->n_rel > 0 && c->max_tries > 0 &&

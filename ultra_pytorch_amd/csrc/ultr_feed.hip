@@ -21,10 +21,9 @@
 #include "../../include/ultr_hip.h"
 #include "ultr_device.h"
 #include "ultr_feed.h"
+#include "ultr_plan.h"
 
 __global__ __launch_bounds__(256) void click_batch_kernel(ultr_click_args ca) { click_draw(ca, (int)blockIdx.x); }
-
-thread_local const ultr_click_args* g_ultr_click_rider = nullptr;
 
 extern "C" int ultr_click_batch(const int32_t* lists, const float* labels, int64_t n_queries, int32_t lmax, int64_t n_docs,
                                 const float* exam_prob, int32_t n_exam, const float* click_prob, int32_t n_rel, int32_t click_model,
@@ -48,10 +47,9 @@ extern "C" int ultr_click_batch_args(const ultr_click_args* c, void* stream) {
 // a launch of its own behind the step when the update launch did not take it (no weight copy, process-group exchange)
 extern "C" int ultr_feed_train_step(const ultr_step_args* a, const ultr_click_args* next, void* stream) {
   if (next != nullptr && !ultr_click_args_ok(next)) return ULTR_E_BADARG;
-  g_ultr_click_rider = next;
-  const int rc = ultr_train_step(a, stream);
-  const bool pending = g_ultr_click_rider != nullptr;
-  g_ultr_click_rider = nullptr;
-  if (rc != 0 || !pending) return rc;
+  StepCtx ctx;
+  ctx.rider = next;
+  const int rc = ultr_train_step_ctx(a, &ctx, stream);
+  if (rc != 0 || ctx.rider == nullptr) return rc;
   return ultr_click_batch_args(next, stream);
 }

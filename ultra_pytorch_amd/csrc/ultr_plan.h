@@ -239,52 +239,58 @@ int ultr_dnn_big_forward(const DnnPlan& p, const float* params, const float* wt,
 int ultr_dnn_big_backward(const DnnPlan& p, const BwdPlan& bp, const float* params, const float* saved, const float* dscores, float* ws,
                           hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, bool split_half);
 
-// library-internal: the small-batch NA/IPW step as one fused forward+loss+backward launch (+ weight gradients +
-// reduction); ULTR_E_UNSUPPORTED = shape does not qualify, use the separate calls
-int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features, int64_t n_docs,
-                            const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
-                            const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw, float* dscores_out,
-                            void* loss_ws, void* bwd_ws, float* grads, void* stream);
-
 // library-internal, ultr_comm.hip: device address of a communicator's status word (the guard of the update behind the exchange)
 struct ultr_comm;
 const uint32_t* ultr_comm_status_word(const ultr_comm* c);
 
-// Early loss report (single GPU, l2_loss = 0): the spare workgroup of the weight-gradient launch that folds the loss partials
-// into the step tail also writes the step's loss to the host-mapped report (ultr_update_desc::host_scalars) - [0] = loss, then
-// [10] = seq - i.e. as soon as the loss is FINAL (behind forward + loss), while the weight gradients, the reduction and the
-// update of the same step are still running.  The host's read of the loss (the reference's loss.item()) then returns ~20 us
-// before the step's last kernel ends and the next step is queued behind it without a bubble.  ultr_train_step sets this
-// around its backward call; every other caller leaves host == nullptr (the update kernel's report is the only one then).
+// Early loss report (l2_loss = 0): the spare workgroup of the weight-gradient launch that folds the loss partials into the step
+// tail also writes the step's loss to the host-mapped report (ultr_update_desc::host_scalars) - [0] = loss, then [10] = seq -
+// i.e. as soon as the loss is FINAL (behind forward + loss), while the weight gradients, the reduction and the update of the same
+// step are still running.  The host's read of the loss (the reference's loss.item()) then returns ~20 us before the step's last
+// kernel ends and the next step is queued behind it without a bubble.  host == nullptr: no report from this launch (the update
+// kernel's is the only one then).
 struct EarlyReport {
   float* host;
   uint32_t seq;
   int algo;
   float rlw;
 };
-extern thread_local EarlyReport g_ultr_early;  // ultr_step.hip
-// the weight copies of the step in flight (ultr_step_args::wt) for the backward kernels ultr_train_step launches: the public
-// ultr_dnn_backward has no such argument (nullptr there: the row-major parameters are streamed)
-extern thread_local const float* g_ultr_step_wt;  // ultr_step.hip
 // ... and in the data-parallel step the loss needs the GLOBAL sums: the exchange kernel's workgroup that reduces the head of
 // the step tail reports it (ultr_comm.hip), one launch ahead of the update
-struct ultr_comm;
 int ultr_comm_allreduce_ex(ultr_comm* c, uint64_t step, const float* src, int64_t n, int64_t n_params, float* out, void* sumsq_ws,
                            int32_t sumsq_parts, void* stream, EarlyReport er);
 
-// ... and the data-parallel step hands its communicator to the backward it launches: where the backward ends in the slab
-// reduction, that launch runs the exchange on its own output (grad_reduce_xchg_kernel) and says so (`done`); ultr_train_step then
-// goes straight to the guarded update.  nullptr everywhere else.
-struct StepXchg {
-  ultr_comm* comm;
-  uint64_t step;
-  EarlyReport er;
-  bool done;
+// The step in flight: on the stack of ultr_train_step / ultr_feed_train_step, handed to the stages the step calls.  nullptr =
+// a stand-alone stage call (the public entry points): the row-major parameters are streamed, nothing reports early, nothing is
+// exchanged and no draw rides on the update launch.
+struct StepCtx {
+  const float* wt = nullptr;                      // ultr_step_args::wt, the weight copies for the backward kernels
+  EarlyReport early = {nullptr, 0u, 0, 1.0f};     // single-GPU report of the weight-gradient launch
+  ultr_comm* comm = nullptr;                      // data-parallel step: where the backward ends in the slab reduction, that launch
+  uint64_t comm_step = 0;                         //   runs the exchange on its own output (grad_reduce_xchg_kernel)
+  EarlyReport early_dp = {nullptr, 0u, 0, 1.0f};  // its report; the launch that reports first clears .host
+  bool xchg_done = false;                         // out: the reduction launch did exchange: straight to the guarded update
+  int nsq2 = 0;                                   // out: level-2 sum-of-squares partials the reduction launch wrote (0: none)
+  const ultr_click_args* rider = nullptr;         // in: a draw waiting for the update launch; out: nullptr once a launch took it
 };
-extern thread_local StepXchg g_ultr_step_xchg;  // ultr_step.hip
-extern thread_local int g_ultr_step_nsq2;       // ultr_step.hip: level-2 sum-of-squares partials this step's reduction launch wrote (0: none)
+int ultr_train_step_ctx(const ultr_step_args* a, StepCtx* ctx, void* stream);  // ultr_step.hip: ultr_train_step on a given context
+// ultr_dnn.hip: the public backward entry points as stages of a step
+int ultr_dnn_backward_ctx(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs, const int32_t* docids,
+                          int32_t batch, int32_t list_size, const void* saved, const float* dscores, const void* loss_ws, void* bwd_ws,
+                          float* grads, void* stream, StepCtx* ctx);
+int ultr_dnn_backward_softmax_ctx(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs,
+                                  const int32_t* docids, int32_t batch, int32_t list_size, const void* saved, const float* scores,
+                                  const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw, float* dscores_out,
+                                  void* loss_ws, void* bwd_ws, float* grads, void* stream, StepCtx* ctx);
+// ... and the small-batch NA/IPW step as one fused forward+loss+backward launch (+ weight gradients + reduction);
+// ULTR_E_UNSUPPORTED = shape does not qualify, use the separate calls
+int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features, int64_t n_docs,
+                            const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
+                            const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw, float* dscores_out,
+                            void* loss_ws, void* bwd_ws, float* grads, void* stream, StepCtx* ctx);
+// ultr_update.hip: ultr_apply_update with the step's level-2 partials and its waiting draw (*rider, cleared when the launch took it)
 int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state, const float* grads,
-                         float* aux, const void* bwd_ws, float* scalars_out, int nsq2, void* stream);  // ultr_update.hip
+                         float* aux, const void* bwd_ws, float* scalars_out, int nsq2, const ultr_click_args** rider, void* stream);
 
 #define ULTR_TAIL_FIXED 4
 __host__ __device__ static inline int64_t ultr_tail_len(int L) { return ULTR_TAIL_FIXED + 2 * (int64_t)L; }

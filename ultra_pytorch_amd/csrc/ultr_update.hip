@@ -440,11 +440,11 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
 
 extern "C" int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state,
                                  const float* grads, float* aux, const void* bwd_ws, float* scalars_out, void* stream) {
-  return ultr_apply_update_ex(u, d, params, wt, state, grads, aux, bwd_ws, scalars_out, 0, stream);
+  return ultr_apply_update_ex(u, d, params, wt, state, grads, aux, bwd_ws, scalars_out, 0, nullptr, stream);
 }
 // nsq2 > 0: the step's slab-reduction launch left level-2 sum-of-squares partials (ultr_plan.h) - library-internal (ultr_train_step)
 int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state, const float* grads,
-                         float* aux, const void* bwd_ws, float* scalars_out, int nsq2, void* stream) {
+                         float* aux, const void* bwd_ws, float* scalars_out, int nsq2, const ultr_click_args** rider_io, void* stream) {
   if (!u || !params || !grads || !bwd_ws || u->n_params <= 0 || u->list_size <= 0) return ULTR_E_BADARG;
   DnnPlan dp;
   memset(&dp, 0, sizeof(dp));
@@ -474,10 +474,10 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
     ultr_click_args rider;
     memset(&rider, 0, sizeof(rider));
     int rider_blocks = 0;
-    if (g_ultr_click_rider != nullptr) {
-      rider = *g_ultr_click_rider;
+    if (rider_io != nullptr && *rider_io != nullptr) {
+      rider = **rider_io;
       rider_blocks = (rider.batch + 3) / 4;
-      g_ultr_click_rider = nullptr;
+      *rider_io = nullptr;
     }
     if (n_tiles + (n_vec + 255) / 256 < 1536) {  // one unit per workgroup keeps the launch wide (config 2: 401 units, config 3: 940 -
                                                  // four per workgroup left 235 workgroups for 256 CUs: 7.0 -> 9.0 us)
