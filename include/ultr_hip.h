@@ -261,6 +261,31 @@ int ultr_setrank_forward(const ultr_setrank_desc* c, const float* params, const 
 int ultr_setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t batch, int32_t list_size, const void* saved,
                           const float* dscores, const void* loss_ws, int32_t n_loss_parts, void* workspace, float* grads,
                           void* stream);
+/* SetRank's dropout.  Replaces the nn.Dropout(rate) calls of EncoderLayer.forward and Encoder.forward (ranking_model/SetRank.py:103-117,
+ * 141-153) at 1 + 2 num_layers sites: 0 behind input_embedding, 1 + 2 l behind encoder l's mha.dense, 2 + 2 l behind its ffn - each on
+ * the Linear's output with its bias, before the residual is added; the output FFN has none.
+ * keep(site, t, c) is a pure function: word c & 3 of Philox-4x32-10 under the (seed, step) key of the online feeds, counter
+ * (t, (stream << 8) | site, c >> 2, 0x5352444F), t = l * batch + b the position-major token, c the column; keep iff
+ * u01(word) >= rate in float32; y = keep ? v / (1 - rate) : 0.  Nothing is stored: the backward draws the mask again, so it takes the
+ * (seed, step, stream) of its forward.  stream: 0 on one GPU, the rank under data parallelism (< 2^24).
+ * A dropout step runs the separate launches in both directions (none of the fused persistent kernels).  dropout == NULL or
+ * rate == 0: exactly ultr_setrank_forward / ultr_setrank_backward, bit for bit.  rate outside [0, 1) (or NaN): ULTR_E_BADARG.
+ * backward: scratch = ultr_setrank_dropout_workspace_bytes(desc, n_rows) bytes, 16-byte aligned, next to `workspace` (which keeps its
+ * size); a missing, unaligned or short scratch: ULTR_E_WORKSPACE.  The forward reads rate, seed, step and stream only. */
+typedef struct ultr_setrank_dropout {
+  float rate;
+  uint64_t seed, step;
+  uint32_t stream;
+  void* scratch;
+  int64_t scratch_bytes;
+} ultr_setrank_dropout;
+int64_t ultr_setrank_dropout_workspace_bytes(const ultr_setrank_desc* c, int64_t n_rows);
+int ultr_setrank_forward_dropout(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
+                                 const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
+                                 const ultr_setrank_dropout* dropout, void* stream);
+int ultr_setrank_backward_dropout(const ultr_setrank_desc* c, const float* params, int32_t batch, int32_t list_size, const void* saved,
+                                  const float* dscores, const void* loss_ws, int32_t n_loss_parts, void* workspace, float* grads,
+                                  const ultr_setrank_dropout* dropout, void* stream);
 
 /* ---- a5 (clip) + a6 (optimizer) + EM / propensity updates ----------------------------
  * Replaces torch.nn.utils.clip_grad_norm_ + Adagrad.step / SGD.step

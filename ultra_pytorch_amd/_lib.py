@@ -93,6 +93,11 @@ class SetRankDesc(ctypes.Structure):
                 ("attention_dtype", c_i32), ("flags", c_i32)]
 
 
+class SetRankDropout(ctypes.Structure):  # ultr_setrank_dropout
+    _fields_ = [("rate", c_f32), ("seed", ctypes.c_uint64), ("step", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("scratch", c_vp),
+                ("scratch_bytes", c_i64)]
+
+
 class StepArgs(ctypes.Structure):
     _fields_ = [("desc", ctypes.POINTER(DnnDesc)), ("upd", ctypes.POINTER(UpdateDesc)), ("params", c_vp), ("wt", c_vp),
                 ("state", c_vp), ("aux", c_vp), ("features", c_vp), ("docids", c_vp), ("labels", c_vp), ("pw", c_vp),
@@ -139,6 +144,11 @@ SIGNATURES = {
     "ultr_setrank_forward": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_setrank_backward": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
                                       c_vp]),
+    "ultr_setrank_dropout_workspace_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
+    "ultr_setrank_forward_dropout": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp,
+                                             ctypes.POINTER(SetRankDropout), c_vp]),
+    "ultr_setrank_backward_dropout": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
+                                              ctypes.POINTER(SetRankDropout), c_vp]),
     "ultr_apply_update": (c_i32, [ctypes.POINTER(UpdateDesc), ctypes.POINTER(DnnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp]),
     "ultr_train_step": (c_i32, [ctypes.POINTER(StepArgs), c_vp]),

@@ -44,6 +44,7 @@ extern "C" int ultr_gemm_trace_arm(int on) {  // slot 31 != 0: frozen
 #include "ultr_plan.h"
 #include "ultr_sr_attn.h"
 #include "ultr_sr_bwd.h"
+#include "ultr_sr_dropout.h"
 
 #define SR_EPS 1e-6f  // nn.LayerNorm(eps=1e-6) everywhere in SetRank.py (:100-101, :134)
 #define SR_ROWS 4     // rows per workgroup (= waves) of the row-wise kernels
@@ -1260,7 +1261,7 @@ void colsum(const SrPlan& p, const float* a, const float* s, const float* mean, 
 }
 
 // dst[0..W) = d gamma, dst[W..2W) = d beta (adjacent in the flat layout: <ln>.weight then <ln>.bias)
-// dx = LayerNorm backward of dy; dst_gb = dgamma | dbeta; dst_bias = column sums of dx.  W <= 1024.
+// dx = LayerNorm backward of dy; dst_gb = dgamma | dbeta; dst_bias = column sums of dx (may be NULL).  W <= 1024.
 int ln_bwd_cs(const SrPlan& p, const float* dy, const float* s, const float* mean, const float* rstd, const float* gamma, int W,
               float* dx, float* ws, float* dst_gb, float* dst_bias, hipStream_t st) {
   float* part = part_scratch(ws + p.ws_part, (int64_t)p.n_lb * 3 * W);
@@ -1271,7 +1272,7 @@ int ln_bwd_cs(const SrPlan& p, const float* dy, const float* s, const float* mea
   else if (W <= 256) hipLaunchKernelGGL(sr_ln_bwd_cs_kernel<4>, dim3(p.n_lb), dim3(256), lds, st, dy, s, mean, rstd, gamma, p.T, W, dx, part);
   else hipLaunchKernelGGL(sr_ln_bwd_cs_kernel<16>, dim3(p.n_lb), dim3(256), lds, st, dy, s, mean, rstd, gamma, p.T, W, dx, part);
   fold(part, (int64_t)3 * W, p.n_lb, 2 * W, dst_gb, st);
-  fold(part + 2 * W, (int64_t)3 * W, p.n_lb, W, dst_bias, st);
+  if (dst_bias != nullptr) fold(part + 2 * W, (int64_t)3 * W, p.n_lb, W, dst_bias, st);  // (NULL: a dropout site sits between ds and the bias)
   return 0;
 }
 void colsum_ln(const SrPlan& p, const float* dy, const float* s, const float* mean, const float* rstd, int W, float* ws, float* dst,
@@ -2026,15 +2027,33 @@ extern "C" int64_t ultr_setrank_workspace_bytes(const ultr_setrank_desc* c, int6
   return (n_rows >= 0 && make_plan(c, n_rows, &p)) ? (p.ws_total + 4) * (int64_t)sizeof(float) : 0;
 }
 
-extern "C" int ultr_setrank_forward(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
-                                    const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
-                                    void* stream) {
+namespace {
+
+// ONE predicate for both directions of a step: a dropout step runs the separate launches (no sr_embed_fwd_kernel, no block kernels,
+// no fused launches of ultr_sr_bwd.hip); NULL or rate == 0 is the plain step.  0: plain, 1: dropout (args filled), < 0: error
+int sr_dropout_plan(const ultr_setrank_dropout* dr, int batch, int list_size, SrDropArgs* out) {
+  if (dr == nullptr || dr->rate == 0.0f) return 0;
+  const int rc = sr_drop_args(dr->rate, dr->seed, dr->step, dr->stream, batch, list_size, out);
+  return rc != 0 ? rc : 1;
+}
+// floats of the backward's extra buffer: the masked branch gradient [T, d] and the bias column-sum partials of the 2 nl encoder sites
+int64_t sr_dropout_ws_floats(const SrPlan& p) {
+  return ((p.T * p.d + 3) & ~(int64_t)3) + (int64_t)2 * p.nl * ((sr_drop_parts(p.T) * p.d + 3) & ~(int64_t)3);
+}
+
+int setrank_forward(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
+                    const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
+                    const ultr_setrank_dropout* dropout, void* stream) {
   if (!params || !docids || !scores || !saved || batch <= 0 || list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features))
     return ULTR_E_BADARG;
   const int64_t T = (int64_t)batch * list_size;
   SrPlan p;
   if (!make_plan(c, T, &p)) return ULTR_E_BADARG;
   const int L = list_size;
+  SrDropArgs da;
+  const int drop_rc = sr_dropout_plan(dropout, batch, list_size, &da);
+  if (drop_rc < 0) return drop_rc;
+  const bool drop = drop_rc == 1;
   const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16};
   SR_CHECK(sr_attn_supported(ash, L, 0));
   if (T > 0x7fffffff / 4) return ULTR_E_UNSUPPORTED;
@@ -2064,7 +2083,7 @@ extern "C" int ultr_setrank_forward(const ultr_setrank_desc* c, const float* par
   }
   // input LayerNorm on the gathered rows, then the embedding FFN (SetRank.py:134-135, 146)
   int erc = 0;
-  const bool embedded = n_docs > 0 && embed_fwd(p, params, features, docids, n_docs, (int)batch, L, sv, st, &erc);  // one launch (sr_embed_fwd_kernel)
+  const bool embedded = !drop && n_docs > 0 && embed_fwd(p, params, features, docids, n_docs, (int)batch, L, sv, st, &erc);  // one launch (sr_embed_fwd_kernel)
   if (embedded && erc) return erc;
   if (embedded) {
   } else if (F % 4 == 0 && F <= 1024 && ((uintptr_t)features & 15) == 0)
@@ -2078,6 +2097,7 @@ extern "C" int ultr_setrank_forward(const ultr_setrank_desc* c, const float* par
     SR_CHECK(gemm_xwT(sv + p.sv_xn0, params + p.w1, params + p.b1, sv + p.sv_h0, T, F, dff, 1, st));
     SR_CHECK(gemm_xwT(sv + p.sv_h0, params + p.w2, params + p.b2, sv + p.sv_x[0], T, dff, d, 0, st));
   }
+  if (drop) sr_drop_mask_launch(da, 0, sv + p.sv_x[0], sv + p.sv_x[0], nullptr, T, d, st);  // x0 = D(embedding): attention and the residual read it
   bool head_done = false;
   for (int l = 0; l < p.nl; ++l) {
     const SrLayer& y = p.lay[l];
@@ -2086,6 +2106,16 @@ extern "C" int ultr_setrank_forward(const ultr_setrank_desc* c, const float* par
     // A Wd^T lands in out1's buffer, then out1 = LN1(x + (A Wd^T + bd)) in place (s1 keeps the pre-norm sum)
     // the Linear's epilogue writes the pre-norm sum s1 = x + (A Wd^T + bd) straight into `saved` (one pass over [T, d] less on
     // each side of the LayerNorm); shapes the tiled GEMM does not take: Linear, then the residual pass
+    if (drop) {  // o = D(dense(A)), f = D(ffn(out1)): the Linear without its bias, then dropout + residual + LayerNorm in one row pass
+      SR_CHECK(gemm_xwT(sv + p.sv_A[l], params + y.wd, nullptr, sv + p.sv_out1[l], T, d, d, 0, st));
+      sr_drop_ln_fwd_launch(da, 1 + 2 * l, x, sv + p.sv_out1[l], params + y.bd, T, d, params + y.g1, params + y.b1, sv + p.sv_s1[l],
+                            sv + p.sv_out1[l], sv + p.sv_m1[l], sv + p.sv_r1[l], st);
+      SR_CHECK(gemm_xwT(sv + p.sv_out1[l], params + y.wf1, params + y.bf1, sv + p.sv_f[l], T, d, dff, 1, st));
+      SR_CHECK(gemm_xwT(sv + p.sv_f[l], params + y.wf2, nullptr, sv + p.sv_x[l + 1], T, dff, d, 0, st));
+      sr_drop_ln_fwd_launch(da, 2 + 2 * l, sv + p.sv_out1[l], sv + p.sv_x[l + 1], params + y.bf2, T, d, params + y.g2, params + y.b2,
+                            sv + p.sv_s2[l], sv + p.sv_x[l + 1], sv + p.sv_m2[l], sv + p.sv_r2[l], st);
+      continue;
+    }
     {
       int brc = 0;
       if (block_fwd(p, l, params, sv, scores, st, &brc)) {  // everything behind the attention in one launch (sr_block_fwd_kernel)
@@ -2121,14 +2151,29 @@ extern "C" int ultr_setrank_forward(const ultr_setrank_desc* c, const float* par
   return (int)hipGetLastError();
 }
 
-extern "C" int ultr_setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t batch, int32_t list_size,
-                                     const void* saved, const float* dscores, const void* loss_ws, int32_t n_loss_parts, void* ws_,
-                                     float* grads, void* stream) {
+int setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t batch, int32_t list_size,
+                     const void* saved, const float* dscores, const void* loss_ws, int32_t n_loss_parts, void* ws_,
+                     float* grads, const ultr_setrank_dropout* dropout, void* stream) {
   if (!params || !saved || !dscores || !ws_ || !grads || batch <= 0 || list_size <= 0) return ULTR_E_BADARG;
   const int64_t T = (int64_t)batch * list_size;
   SrPlan p;
   if (!make_plan(c, T, &p)) return ULTR_E_BADARG;
   const int L = list_size;
+  SrDropArgs da;
+  const int drop_rc = sr_dropout_plan(dropout, batch, list_size, &da);
+  if (drop_rc < 0) return drop_rc;
+  const bool drop = drop_rc == 1;
+  float* DM = nullptr;     // the masked branch gradient of the site at hand [T, d]
+  float* dpart = nullptr;  // its bias column-sum partials, one piece per encoder site (the folds run at the end)
+  int64_t dpart_floats = 0;
+  if (drop) {
+    if (dropout->scratch == nullptr || ((uintptr_t)dropout->scratch & 15) != 0 ||
+        dropout->scratch_bytes < sr_dropout_ws_floats(p) * (int64_t)sizeof(float))
+      return ULTR_E_WORKSPACE;
+    DM = (float*)dropout->scratch;
+    dpart = DM + ((T * p.d + 3) & ~(int64_t)3);
+    dpart_floats = (sr_drop_parts(T) * p.d + 3) & ~(int64_t)3;
+  }
   const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16};
   SR_CHECK(sr_attn_supported(ash, L, 1));
   sr_knobs_load();
@@ -2151,7 +2196,7 @@ extern "C" int ultr_setrank_backward(const ultr_setrank_desc* c, const float* pa
   // the fused launches of ultr_sr_bwd.hip: config 5's widths, split-half products on, the transposed fragment copies built by this
   // step's forward
   int fz_R = 0, fz_tiles = 0, fz_nwg = 0;
-  bool fused = p.bwd_fused && g_sr_knob_bwd_fused != 0 && g_sr_h3.planes != nullptr && T * (int64_t)d * 4 < ((int64_t)1 << 31);
+  bool fused = !drop && p.bwd_fused && g_sr_knob_bwd_fused != 0 && g_sr_h3.planes != nullptr && T * (int64_t)d * 4 < ((int64_t)1 << 31);
   if (fused) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
@@ -2229,38 +2274,51 @@ extern "C" int ultr_setrank_backward(const ultr_setrank_desc* c, const float* pa
       }
     }
     // (the forward did not write out1 when it expected the fused launches: sr_block_fwd_kernel's skip_out1 - same predicate)
-    if (sr_bwd_blocks_fused(p) && g_sr_knob_block != 0) return ULTR_E_UNSUPPORTED;
+    // (a dropout step's forward ran the separate launches and wrote out1)
+    if (!drop && sr_bwd_blocks_fused(p) && g_sr_knob_block != 0) return ULTR_E_UNSUPPORTED;
+    // a dropout site: the branch gradient d(b + bias) = keep * scale * ds goes to DM with its column sums (the bias gradient); the
+    // residual keeps the unmasked ds
+    auto masked_branch = [&](int site, const float* ds, float* dst_bias) {
+      float* part = dpart + (int64_t)(site - 1) * dpart_floats;
+      sr_drop_mask_launch(da, site, ds, DM, part, T, d, st);
+      fold(part, (int64_t)d, (int)sr_drop_parts(T), d, dst_bias, st, /*own_buffer=*/true);
+    };
     // x_{l+1} = LN2(s2),  s2 = out1 + ffn
     if (d <= 1024) {  // g2 | b2, G2 = d s2 = d out1 (residual) = d ffn, bf2: one pass
       SR_CHECK(ln_bwd_cs(p, G0, sv + p.sv_s2[l], sv + p.sv_m2[l], sv + p.sv_r2[l], params + y.g2, d, G2, ws, grads + y.g2,
-                         grads + y.bf2, st));
+                         drop ? nullptr : grads + y.bf2, st));
     } else {
       colsum_ln(p, G0, sv + p.sv_s2[l], sv + p.sv_m2[l], sv + p.sv_r2[l], d, ws, grads + y.g2, st);
       hipLaunchKernelGGL(sr_ln_bwd_kernel, dim3(rblk), dim3(SR_ROWS * 64), 0, st, (const float*)G0, sv + p.sv_s2[l], sv + p.sv_m2[l],
                          sv + p.sv_r2[l], params + y.g2, T, d, G2);
-      colsum(p, G2, nullptr, nullptr, nullptr, d, 0, ws, grads + y.bf2, st);
+      if (!drop) colsum(p, G2, nullptr, nullptr, nullptr, d, 0, ws, grads + y.bf2, st);
     }
-    SR_CHECK(wgrad(p, G2, sv + p.sv_f[l], grads + y.wf2, nullptr, T, dff, d, ws, st));
-    SR_CHECK(gemm_dyw(G2, params + y.wf2, G1, sv + p.sv_f[l], T, dff, d, 0, st));  // G1 = d f  [T, dff], ReLU mask fused
+    if (drop) masked_branch(2 + 2 * l, G2, grads + y.bf2);
+    const float* dffn = drop ? DM : G2;  // d (f Wf2^T + bf2)
+    SR_CHECK(wgrad(p, dffn, sv + p.sv_f[l], grads + y.wf2, nullptr, T, dff, d, ws, st));
+    SR_CHECK(gemm_dyw(dffn, params + y.wf2, G1, sv + p.sv_f[l], T, dff, d, 0, st));  // G1 = d f  [T, dff], ReLU mask fused
     SR_CHECK(wgrad(p, G1, sv + p.sv_out1[l], grads + y.wf1, grads + y.bf1, T, d, dff, ws, st));
     SR_CHECK(gemm_dyw(G1, params + y.wf1, G2, nullptr, T, d, dff, 1, st));   // G2 = d out1 (both paths): accumulated
     // out1 = LN1(s1),  s1 = x_l + o
     if (d <= 1024) {  // g1 | b1, G0 = d s1 = d x_l (residual) = d o, bd
       SR_CHECK(ln_bwd_cs(p, G2, sv + p.sv_s1[l], sv + p.sv_m1[l], sv + p.sv_r1[l], params + y.g1, d, G0, ws, grads + y.g1,
-                         grads + y.bd, st));
+                         drop ? nullptr : grads + y.bd, st));
     } else {
       colsum_ln(p, G2, sv + p.sv_s1[l], sv + p.sv_m1[l], sv + p.sv_r1[l], d, ws, grads + y.g1, st);
       hipLaunchKernelGGL(sr_ln_bwd_kernel, dim3(rblk), dim3(SR_ROWS * 64), 0, st, (const float*)G2, sv + p.sv_s1[l], sv + p.sv_m1[l],
                          sv + p.sv_r1[l], params + y.g1, T, d, G0);
-      colsum(p, G0, nullptr, nullptr, nullptr, d, 0, ws, grads + y.bd, st);
+      if (!drop) colsum(p, G0, nullptr, nullptr, nullptr, d, 0, ws, grads + y.bd, st);
     }
-    SR_CHECK(wgrad(p, G0, sv + p.sv_A[l], grads + y.wd, nullptr, T, d, d, ws, st));
-    SR_CHECK(gemm_dyw(G0, params + y.wd, G1, nullptr, T, d, d, 0, st));      // G1 = d A  [T, d]
+    if (drop) masked_branch(1 + 2 * l, G0, grads + y.bd);
+    const float* dproj = drop ? DM : G0;  // d (A Wd^T + bd)
+    SR_CHECK(wgrad(p, dproj, sv + p.sv_A[l], grads + y.wd, nullptr, T, d, d, ws, st));
+    SR_CHECK(gemm_dyw(dproj, params + y.wd, G1, nullptr, T, d, d, 0, st));      // G1 = d A  [T, d]
     // G0 += attention path -> d x_l
     SR_CHECK(sr_attn_backward(ash, attn_split_half(l), sv + p.sv_x[l], G1, sv + p.sv_A[l], sv + p.sv_lse[l], batch, L, G0, st));
   }
   // ---- embedding FFN and the input LayerNorm's parameters -------------------------------------------------------------
   bool embed_done = false;
+  if (drop) sr_drop_mask_launch(da, 0, G0, G0, nullptr, T, d, st);  // x0 has no residual: d embedding = D'(d x0) in place; wgrad sums d b2
   if (fused && (g_sr_knob_bwd_fused & 4) && F % 4 == 0 && F <= SR_BWD_D && p.b_in == p.g_in + F && p.w1 == p.b_in + F && p.b1 == p.w1 + (int64_t)dff * F &&
       p.w2 == p.b1 + dff && p.b2 == p.w2 + (int64_t)d * dff) {
     const SrPlan::SplitMat* m1 = sr_find_split(params + p.w1, dff, F);
@@ -2293,4 +2351,31 @@ extern "C" int ultr_setrank_backward(const ultr_setrank_desc* c, const float* pa
   }
   folds.flush(st);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int ultr_setrank_forward(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
+                                    const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
+                                    void* stream) {
+  return setrank_forward(c, params, features, n_docs, docids, batch, list_size, scores, saved, nullptr, stream);
+}
+extern "C" int ultr_setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t batch, int32_t list_size,
+                                     const void* saved, const float* dscores, const void* loss_ws, int32_t n_loss_parts, void* ws_,
+                                     float* grads, void* stream) {
+  return setrank_backward(c, params, batch, list_size, saved, dscores, loss_ws, n_loss_parts, ws_, grads, nullptr, stream);
+}
+extern "C" int64_t ultr_setrank_dropout_workspace_bytes(const ultr_setrank_desc* c, int64_t n_rows) {
+  SrPlan p;
+  return (n_rows >= 0 && make_plan(c, n_rows, &p)) ? sr_dropout_ws_floats(p) * (int64_t)sizeof(float) : 0;
+}
+extern "C" int ultr_setrank_forward_dropout(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
+                                            const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
+                                            const ultr_setrank_dropout* dropout, void* stream) {
+  return setrank_forward(c, params, features, n_docs, docids, batch, list_size, scores, saved, dropout, stream);
+}
+extern "C" int ultr_setrank_backward_dropout(const ultr_setrank_desc* c, const float* params, int32_t batch, int32_t list_size,
+                                             const void* saved, const float* dscores, const void* loss_ws, int32_t n_loss_parts,
+                                             void* ws_, float* grads, const ultr_setrank_dropout* dropout, void* stream) {
+  return setrank_backward(c, params, batch, list_size, saved, dscores, loss_ws, n_loss_parts, ws_, grads, dropout, stream);
 }

@@ -573,7 +573,12 @@ def _setrank_draw(list_size):
 class SetRankStepEngine(StepEngine):
     """The same step for the SetRank ranking model: ultr_setrank_forward -> ultr_<loss> ->
     ultr_setrank_backward -> [all-reduce] -> ultr_grad_sumsq -> ultr_apply_update.  Stage calls instead of ONE C call:
-    at SetRank's size (hundreds of microseconds to milliseconds per step) the host is not on the critical path."""
+    at SetRank's size (hundreds of microseconds to milliseconds per step) the host is not on the critical path.
+
+    Dropout (shape.rate > 0): forward(train=True) takes the model's next dropout step (shape.next_dropout_step()) and passes
+    (rate, shape.dropout_seed, step, dropout_stream) to ultr_setrank_forward_dropout; backward() hands the same struct, with the
+    extra scratch, to ultr_setrank_backward_dropout.  dropout_stream is the data-parallel rank: replicas drop different elements of
+    their different shards.  forward(train=False) never drops."""
 
     def __init__(self, shape, batch, list_size, device, **kw):
         self._sr_shape = shape
@@ -586,16 +591,25 @@ class SetRankStepEngine(StepEngine):
         self.bwd_ws = _f32((self.P + self.tail + 63) // 64 + self.P // 4096 + 16, device)
         self._flag_off = shape.range_flag_offset(self.N)
         self.saved[self._flag_off].zero_()  # (every forward zeroes it again: this is for a report before the first forward)
+        self.dropout_stream = self.rank
+        self.drop_ws = None  # the backward's extra buffer of a dropout step, allocated by the first one
+        self._drop = None    # ultr_setrank_dropout of the forward in flight (None: a plain step)
 
     def forward(self, params, features, n_docs, docids, scores=None, train=False):
         scores = self.scores if scores is None else scores
         _setrank_draw(self.L)
-        hip_ops.setrank_forward(self.shape, params, features, n_docs, docids, self.B, self.L, scores, self.saved)
+        self._drop = None
+        if train and getattr(self.shape, "rate", 0.0) > 0.0:
+            if self.drop_ws is None:
+                self.drop_ws = _f32(self.shape.dropout_workspace_bytes(self.N) // 4, self.device)
+            self._drop = hip_ops.setrank_dropout(self.shape.rate, self.shape.dropout_seed, self.shape.next_dropout_step(),
+                                                 self.dropout_stream, self.drop_ws)
+        hip_ops.setrank_forward(self.shape, params, features, n_docs, docids, self.B, self.L, scores, self.saved, dropout=self._drop)
         return scores
 
     def backward(self, params, features, n_docs, docids):
         hip_ops.setrank_backward(self.shape, params, self.B, self.L, self.saved, self.dscores, self.loss_ws, hip_ops.loss_part_count(self.B),
-                                 self.sr_ws, self.grads)
+                                 self.sr_ws, self.grads, dropout=self._drop)
         if self.pg is not None:
             self.dp_reduce()
         else:

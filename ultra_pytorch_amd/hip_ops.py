@@ -74,9 +74,18 @@ class DnnShape:
 
 class SetRankShape:
     """Host-side geometry of one SetRank model: descriptor + flat parameter layout in the reference's
-    state_dict order (SetRank.py:95-103, 130-141)."""
+    state_dict order (SetRank.py:95-103, 130-141).
 
-    def __init__(self, feature_size, d_model=256, num_heads=8, num_layers=2, dff=64, attention_dtype="fp32"):
+    `rate` is the dropout rate of TRAINING forwards (SetRank.py:103-117, 141-153).  It lives beside the descriptor, not in it: the
+    parameter layout, the buffer sizes and every evaluation are those of the rate-0 model.  The dropout key rides along:
+    `dropout_seed` (the owner of the shape sets it; ranking_model.SetRank captures torch.initial_seed()) and `dropout_step`, the count
+    of training forwards so far - engines are cached and evicted, so the counter is the model's, shared through this object."""
+
+    def __init__(self, feature_size, d_model=256, num_heads=8, num_layers=2, dff=64, attention_dtype="fp32", rate=0.0):
+        rate = float(rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError("rate must be in [0, 1) (got %r)" % rate)
+        self.rate, self.dropout_seed, self.dropout_step = rate, 0, 0
         self.lib = _lib.load()
         self.feature_size, self.d_model, self.num_heads = int(feature_size), int(d_model), int(num_heads)
         self.num_layers, self.dff = int(num_layers), int(dff)
@@ -123,17 +132,49 @@ class SetRankShape:
     def workspace_bytes(self, n_rows):
         return int(self.lib.ultr_setrank_workspace_bytes(ctypes.byref(self.desc), n_rows))
 
+    def dropout_workspace_bytes(self, n_rows):
+        """The backward's extra buffer of a dropout step (ultr_setrank_dropout::scratch)."""
+        return int(self.lib.ultr_setrank_dropout_workspace_bytes(ctypes.byref(self.desc), n_rows))
+
+    def next_dropout_step(self):
+        """The step number of the training forward about to run; counts it."""
+        step = self.dropout_step
+        self.dropout_step = step + 1
+        return step
+
     def range_flag_offset(self, n_rows):
         """Float offset in `saved` of the range word of the split-half planes (ultr_update_desc::range_flag)."""
         return int(self.lib.ultr_setrank_range_flag_offset(ctypes.byref(self.desc), n_rows))
 
 
-def setrank_forward(shape, params, features, n_docs, docids, B, L, scores, saved):
+def setrank_dropout(rate, seed, step, stream=0, scratch=None):
+    """ultr_setrank_dropout for one step: the forward reads (rate, seed, step, stream), the backward of the same step the scratch too."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError("rate must be in [0, 1) (got %r)" % rate)
+    d = _lib.SetRankDropout()
+    d.rate, d.seed, d.step, d.stream = rate, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(stream)
+    d.scratch = scratch.data_ptr() if scratch is not None else None
+    d.scratch_bytes = scratch.numel() * scratch.element_size() if scratch is not None else 0
+    return d
+
+
+def setrank_forward(shape, params, features, n_docs, docids, B, L, scores, saved, dropout=None):
+    if dropout is not None:
+        check(shape.lib.ultr_setrank_forward_dropout(ctypes.byref(shape.desc), _p(params), _p(features), int(n_docs), _p(docids), int(B),
+                                                     int(L), _p(scores), _p(saved), ctypes.byref(dropout), _stream()),
+              "ultr_setrank_forward_dropout")
+        return
     check(shape.lib.ultr_setrank_forward(ctypes.byref(shape.desc), _p(params), _p(features), int(n_docs), _p(docids), int(B),
                                          int(L), _p(scores), _p(saved), _stream()), "ultr_setrank_forward")
 
 
-def setrank_backward(shape, params, B, L, saved, dscores, loss_ws, n_loss_parts, ws, grads):
+def setrank_backward(shape, params, B, L, saved, dscores, loss_ws, n_loss_parts, ws, grads, dropout=None):
+    if dropout is not None:
+        check(shape.lib.ultr_setrank_backward_dropout(ctypes.byref(shape.desc), _p(params), int(B), int(L), _p(saved), _p(dscores),
+                                                      _p(loss_ws), int(n_loss_parts), _p(ws), _p(grads), ctypes.byref(dropout), _stream()),
+              "ultr_setrank_backward_dropout")
+        return
     check(shape.lib.ultr_setrank_backward(ctypes.byref(shape.desc), _p(params), int(B), int(L), _p(saved), _p(dscores), _p(loss_ws),
                                           int(n_loss_parts), _p(ws), _p(grads), _stream()), "ultr_setrank_backward")
 

@@ -6,7 +6,15 @@ Same constructor `(hparams_str, feature_size)`, hparams (`d_model`, `num_heads`,
 interchange.  All parameters are views into ONE flat fp32 tensor in state_dict order - the layout the HIP path
 (ultr_setrank_forward / ultr_setrank_backward) consumes.  Quirks kept: no Q/K/V projections, no mask (PAD documents
 attend and are attended), LayerNorm eps 1e-6, the shuffled index list of `build` is computed by the reference but never
-used (SetRank.py:245-246) - dropped.  `rate` must stay 0.0 (the default): dropout is not implemented.
+used (SetRank.py:245-246) - dropped.
+
+Dropout (`rate` in [0, 1), SetRank.py:103-117, 141-153): as the reference's nn.Dropout it follows the module's `training` flag - a
+fresh module is in training mode, every learning algorithm calls `model.train()` before a step and `model.eval()` in
+`validation()` - and acts at 1 + 2 num_layers sites (behind the embedding FFN, behind each encoder's mha.dense and ffn), PAD rows
+included.  The masks are this engine's own law, not torch's stream: a pure function of (`dropout_seed`, `dropout_step`, stream,
+site, token, column) on the Philox generator of the click feeds, drawn again by the backward.
+`dropout_seed` is torch.initial_seed() at construction; `dropout_step` counts the TRAINING forwards of this model object, through
+`build()` and through every step engine alike.  Evaluation never drops.
 """
 import math
 
@@ -54,14 +62,33 @@ class SetRank(nn.Module):
         self.hparams = HParams(d_model=256, num_heads=8, num_layers=2, diff=64, rate=0.0, initializer=None,
                                attention_dtype="fp32")
         self.hparams.parse(hparams_str)
-        if float(self.hparams.rate) != 0.0:
-            raise NotImplementedError("rate=%r: dropout is not implemented (the reference's default is 0.0)" % self.hparams.rate)
+        rate = float(self.hparams.rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError("rate=%r: the dropout rate must be in [0, 1)" % self.hparams.rate)
         self.feature_size = int(feature_size)
         self.shape = hip_ops.SetRankShape(self.feature_size, self.hparams.d_model, self.hparams.num_heads,
                                           self.hparams.num_layers, self.hparams.diff,
-                                          attention_dtype=str(self.hparams.attention_dtype))
+                                          attention_dtype=str(self.hparams.attention_dtype), rate=rate)
+        self.shape.dropout_seed = int(torch.initial_seed())  # as DBGD keys its noise
         self._bind(init_setrank_params(self.shape))
         self._fwd_saved = {}
+
+    # the dropout key lives on the shape, which every step engine of this model shares
+    @property
+    def dropout_seed(self):
+        return self.shape.dropout_seed
+
+    @dropout_seed.setter
+    def dropout_seed(self, v):
+        self.shape.dropout_seed = int(v)
+
+    @property
+    def dropout_step(self):
+        return self.shape.dropout_step
+
+    @dropout_step.setter
+    def dropout_step(self, v):
+        self.shape.dropout_step = int(v)
 
     def _bind(self, flat):
         self.flat_params = flat
@@ -110,5 +137,8 @@ class SetRank(nn.Module):
         key = (B, L)
         if key not in self._fwd_saved:
             self._fwd_saved[key] = torch.empty(max(self.shape.saved_bytes(B * L) // 4, 1), dtype=torch.float32, device=dev)
-        hip_ops.setrank_forward(self.shape, self.flat_params, x, L * B, docids, B, L, scores, self._fwd_saved[key])
+        drop = None
+        if self.training and self.shape.rate > 0.0:  # nn.Dropout follows the module's flag, not is_training (SetRank.py:103-117)
+            drop = hip_ops.setrank_dropout(self.shape.rate, self.shape.dropout_seed, self.shape.next_dropout_step())
+        hip_ops.setrank_forward(self.shape, self.flat_params, x, L * B, docids, B, L, scores, self._fwd_saved[key], dropout=drop)
         return list(torch.split(scores.t().contiguous().view(L * B, 1), B, dim=0))
