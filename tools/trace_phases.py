@@ -28,7 +28,8 @@ torch.cuda.synchronize()
 buf = (ctypes.c_ulonglong * (3 * 64 * 32))()
 lib.ultr_trace_read.argtypes = [ctypes.c_void_p]
 lib.ultr_trace_read(buf)
-a = np.array(buf[:], dtype=np.uint64).reshape(3, 64, 32)[0]  # bank 0: the 8-wave kernels
+banks = np.array(buf[:], dtype=np.uint64).reshape(3, 64, 32)
+a = banks[0]  # bank 0: the 8-wave kernels
 # fused forward+loss+backward kernel (dnn_fb_kernel): 0 start, 1 prologue done, 2+2j LayerNorm_j done, 3+2j GEMM_j done,
 # 16 loss done, then the backward stamps of dnn_bwd2_kernel (18+4jj row pass start, 19+4jj row pass done, 17+4jj GEMM done)
 if os.environ.get("ULTR_NO_FUSED_FB", "0") != "1":
@@ -45,7 +46,17 @@ if os.environ.get("ULTR_NO_FUSED_FB", "0") != "1":
               % (blk * 32, t[28] - t[0], t[29] - t[28], t[1] - t[29], t[30] - t[1], t[31] - t[30], t[7] - t[31], t[2] - t[7], t[13] - t[23], t[13] - t[0]))
     for blk in range(0, 7, 1):
         t = a[blk].astype(np.int64)
-        print("wgrad wg %3d: preamble=%d mainloop=%d ldswrite+sync=%d reduce+store=%d total=%d" % (blk * 32, t[9] - t[8], t[10] - t[9], t[11] - t[10], t[12] - t[11], t[12] - t[8]))
+        print("wgrad wg %3d: entry->role=%d preamble=%d mainloop=%d ldswrite+sync=%d reduce+store=%d total=%d (from entry: %d)"
+              % (blk * 32, t[8] - t[14], t[9] - t[8], t[10] - t[9], t[11] - t[10], t[12] - t[11], t[12] - t[8], t[12] - t[14]))
+    # the step's tail (banks 1 / 2 are free in the fused step): grad_reduce_kernel<true> and update_tiled_kernel stamp
+    # 0 entry, 1 indices known, 2 first data arrived, 3 after the sum-of-squares block sum, 4 end
+    for name, bank, blks in (("reduce", banks[1], (0, 4, 8, 11, 12)), ("update", banks[2], (0, 4, 8, 11, 12))):
+        for blk in blks:
+            t = bank[blk].astype(np.int64)
+            if t[0] == 0 or t[4] == 0:
+                continue
+            print("%s wg %3d: entry->indices=%d ->first data=%d ->block sum=%d ->end=%d total=%d"
+                  % (name, blk * 32, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[4] - t[0]))
     sys.exit(0)
 names = ["start", "gather+sync", "LN0", "GEMM0", "sync", "LN1", "GEMM1", "sync", "LN2", "dot"]
 for blk in range(5):

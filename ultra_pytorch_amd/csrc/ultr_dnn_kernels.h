@@ -632,7 +632,10 @@ __device__ __forceinline__ int pick_ct(int width, int nw) {
 #ifdef ULTR_TRACE
 // three banks: 0 = the 8-wave kernels (their slot numbers overlap each other: trace one kernel at a time), 1 = dnn_fwdw_kernel,
 // 2 = dnn_bwdw_kernel (a training step runs all of them).  One array PER TRANSLATION UNIT (the kernels of a bank live in one unit:
-// ultr_dnn_fwd.hip banks 0 / 1, ultr_dnn_bwd.hip 0 / 2, ultr_dnn_fb.hip and ultr_dnn_wgrad.hip 0); ultr_trace_read (ultr_dnn.hip) adds the units' arrays
+// ultr_dnn_fwd.hip banks 0 / 1, ultr_dnn_bwd.hip 0 / 2, ultr_dnn_fb.hip and ultr_dnn_wgrad.hip 0); ultr_trace_read (ultr_dnn.hip)
+// adds the units' arrays.  The step's tail borrows the other banks: grad_reduce_kernel<true> stamps bank 1 and
+// update_tiled_kernel bank 2 of an array of its own (ultr_update.hip).  Trace them in a step that runs neither dnn_fwdw_kernel
+// nor dnn_bwdw_kernel: the fused one.
 static __device__ unsigned long long g_ultr_trace[3 * 64 * 32];
 #define TRACE_STAMP_B(bank, slot)                                                                   \
   do {                                                                                              \
@@ -645,6 +648,8 @@ static __device__ unsigned long long g_ultr_trace[3 * 64 * 32];
     if (threadIdx.x == 0 && (blockIdx.x & 31) == 0 && (slot) < 32 && (blockIdx.x >> 5) < 64)        \
       g_ultr_trace[(bank) * 2048 + (blockIdx.x >> 5) * 32 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
+// a stamp must not be taken before `v` exists (s_memtime depends on nothing: the scheduler would hoist it above the loads)
+#define TRACE_AFTER(v) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"(v) : "memory")
 #define ULTR_TRACE_READER(name)                                                                                              \
   int name(unsigned long long* host_out) {                                                                                  \
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_ultr_trace), sizeof(unsigned long long) * 3 * 64 * 32);          \
@@ -655,6 +660,9 @@ static __device__ unsigned long long g_ultr_trace[3 * 64 * 32];
   } while (0)
 #define TRACE_REAL_B(bank, slot) \
   do {                           \
+  } while (0)
+#define TRACE_AFTER(v) \
+  do {                 \
   } while (0)
 #define ULTR_TRACE_READER(name)
 #endif
@@ -788,4 +796,5 @@ int ultr_trace_read_fwd(unsigned long long* host_out);
 int ultr_trace_read_bwd(unsigned long long* host_out);
 int ultr_trace_read_fb(unsigned long long* host_out);
 int ultr_trace_read_wgrad(unsigned long long* host_out);
+int ultr_trace_read_update(unsigned long long* host_out);  // ultr_update.hip
 #endif

@@ -93,8 +93,77 @@ __device__ __forceinline__ void wg_spare_roles(const DnnPlan& p, const BwdPlan& 
   }
 }
 
+// The head of a weight-gradient workgroup: which layer, which tile, where its operands are.  The plans are by-value kernel
+// arguments (2.3 KB) and the argument segment is rewritten by every launch, so every first touch of one of its lines is a miss to
+// memory.  The head used to chain such reads - bp.wgrad_blocks, then `while (blockIdx.x >= bp.wl[j + 1].blk_begin)`, then the copy
+// of bp.wl[j], then p.sv_x[j] / p.off_lnw[j] ... of DnnPlan, each runtime-indexed and each waiting for the one before: 2.4k cycles
+// between the role split and the first dz / u request at config 2, 0.9k now (profiles/plan_tables.md).
+// wg_stage copies the three pieces of the plans the head indexes at run time -
+// bp.wl[], p.sv_x | sv_mean | sv_rstd, p.off_lnw | off_lnb | off_w - into LDS with ONE load per thread whose address depends on
+// threadIdx alone (the same round trip as the scalar arguments), BEFORE the role split; wg_head searches the copy (lane i of a wave
+// compares with layer i's first block: the leading ones of the ballot are what the `while` loop counted) and reads layer j's
+// record with one ds_read per wave (lane = field), fields by v_readlane - the idiom of dnn_fb_kernel's FbPlan.
+#define WGH_WL_DW ((int)(sizeof(WgradLayer) / 4))
+#define WGH_A_DW (ULTR_MAXL * WGH_WL_DW)  // bp.wl[]
+#define WGH_B_DW (3 * 2 * ULTR_MAXL)      // p.sv_x, sv_mean, sv_rstd
+#define WGH_C_DW (3 * 2 * ULTR_MAXL)      // p.off_lnw, off_lnb, off_w
+#define WGH_DW (WGH_A_DW + WGH_B_DW + WGH_C_DW)
+// word index of a WgradLayer field = the lane of wg_head's record read that holds it
+#define WGW(field) ((int)(offsetof(WgradLayer, field) / 4))
+static_assert(WGH_DW <= 256 && WGH_WL_DW <= 16, "one word per thread; a record fits lanes 0..15");
+static_assert(offsetof(DnnPlan, sv_mean) == offsetof(DnnPlan, sv_x) + 8 * ULTR_MAXL && offsetof(DnnPlan, sv_rstd) == offsetof(DnnPlan, sv_x) + 16 * ULTR_MAXL &&
+              offsetof(DnnPlan, off_lnb) == offsetof(DnnPlan, off_lnw) + 8 * ULTR_MAXL && offsetof(DnnPlan, off_w) == offsetof(DnnPlan, off_lnw) + 16 * ULTR_MAXL,
+              "wg_stage copies these arrays as two contiguous pieces");
+struct WgHead {
+  int j;
+  WgradLayer wl;
+  int64_t sv_x, sv_mean, sv_rstd, off_lnw, off_lnb;  // of layer j
+};
+// the two plans as ONE kernel argument, so that wg_stage's three pieces are words of one object (picked by index, one load)
+struct WgPlans {
+  DnnPlan p;
+  BwdPlan bp;
+};
+__device__ __forceinline__ void wg_stage(const WgPlans& pl, int* __restrict__ sm_head) {
+  const DnnPlan& p = pl.p;
+  const BwdPlan& bp = pl.bp;
+  const int t = threadIdx.x;
+  constexpr int A0 = (int)((offsetof(WgPlans, bp) + offsetof(BwdPlan, wl)) / 4), B0 = (int)((offsetof(WgPlans, p) + offsetof(DnnPlan, sv_x)) / 4),
+                C0 = (int)((offsetof(WgPlans, p) + offsetof(DnnPlan, off_lnw)) / 4);
+  const int w = t < WGH_A_DW ? A0 + t : t < WGH_A_DW + WGH_B_DW ? B0 + (t - WGH_A_DW) : C0 + (t - WGH_A_DW - WGH_B_DW);
+  const int v = reinterpret_cast<const int*>(&pl)[t < WGH_DW ? w : 0];  // unconditional: issued ahead of every wait
+  // ... and every scalar argument the head reads is requested HERE, in the same round trip: left to the compiler they are
+  // fetched where first used, one wait after the other behind every branch of the head
+  asm volatile("" ::"s"(bp.wgrad_blocks), "s"(bp.N), "s"(p.nl), "s"(bp.l0g), "s"(bp.wg_prenorm), "s"(p.sv_total), "s"(bp.l0part_off),
+               "s"(p.off_w[0]), "s"(p.off_lnw[0]), "s"(p.off_lnb[0]), "s"(bp.wg_chunk), "s"(bp.wg_live), "s"(bp.wg_tiles2),
+               "v"(v));  // (the staged word is an operand too: its load cannot be scheduled behind the wait for the scalars)
+  if (t < WGH_DW) sm_head[t] = v;
+}
+// behind wg_stage and a workgroup barrier; nh = p.nl - 1 hidden layers, tix = the block / tile number blk_begin counts
+__device__ __forceinline__ WgHead wg_head(const int* __restrict__ sm_head, int nh, int tix) {
+  const int lane = threadIdx.x & 63;
+  const int bb = sm_head[(lane & (ULTR_MAXL - 1)) * WGH_WL_DW + WGW(blk_begin)];  // lane i: wl[i].blk_begin
+  const unsigned long long bal = __ballot(lane >= 1 && lane < nh && tix >= bb);
+  WgHead h;
+  h.j = __builtin_ctzll(~(bal >> 1));
+  // lanes 0..13: the words of wl[j] (lane WGW(field)); lanes 16..25: (lo, hi) of sv_x[j], sv_mean[j], sv_rstd[j], off_lnw[j], off_lnb[j]
+  const int f = (lane & 31) - 16;
+  const int at = f < 0 ? h.j * WGH_WL_DW + (lane & 15) : WGH_A_DW + ((f >> 1) % 5) * 2 * ULTR_MAXL + 2 * h.j + (f & 1);
+  const int rv = sm_head[at < WGH_DW ? at : 0];
+#define WGF(k) __builtin_amdgcn_readlane(rv, (k))
+#define WGF64(k) ((int64_t)(((unsigned long long)(unsigned)WGF((k) + 1) << 32) | (unsigned)WGF(k)))
+  h.wl.M = WGF(WGW(M)); h.wl.K = WGF(WGW(K)); h.wl.nmb = WGF(WGW(nmb)); h.wl.nkb = WGF(WGW(nkb)); h.wl.nsplit = WGF(WGW(nsplit));
+  h.wl.rows_per_split = WGF(WGW(rows_per_split)); h.wl.blk_begin = WGF(WGW(blk_begin)); h.wl.vec = WGF(WGW(vec));
+  h.wl.nmb2 = WGF(WGW(nmb2)); h.wl.nkb2 = WGF(WGW(nkb2));
+  h.wl.dz_off = WGF64(WGW(dz_off)); h.wl.slab_off = WGF64(WGW(slab_off));
+  h.sv_x = WGF64(16); h.sv_mean = WGF64(18); h.sv_rstd = WGF64(20); h.off_lnw = WGF64(22); h.off_lnb = WGF64(24);
+#undef WGF64
+#undef WGF
+  return h;
+}
+
 template <bool VEC>
-__global__ __launch_bounds__(256) void dnn_wgrad_kernel(DnnPlan p, BwdPlan bp, const float* __restrict__ params,
+__global__ __launch_bounds__(256) void dnn_wgrad_kernel(WgPlans pl, const float* __restrict__ params,
                                                         const float* __restrict__ features, int64_t n_docs,
                                                         const int32_t* __restrict__ docids, int B, int L,
                                                         const float* __restrict__ saved, float* __restrict__ ws,
@@ -106,15 +175,22 @@ __global__ __launch_bounds__(256) void dnn_wgrad_kernel(DnnPlan p, BwdPlan bp, c
   float (*red)[64 * 64] = reinterpret_cast<float (*)[64 * 64]>(smem);
   float (*bred)[64] = reinterpret_cast<float (*)[64]>(smem + 4 * 64 * 64);
   int* sm_ids = reinterpret_cast<int*>(smem + 4 * 64 * 64 + 4 * 64);
+  __shared__ int sm_head[WGH_DW];
+  const DnnPlan& p = pl.p;
+  const BwdPlan& bp = pl.bp;
+  TRACE_STAMP(14);  // entry (slot 14: free in the fused step - the fused kernel owns 0 - 7, 13 and 16 - 31 of the bank)
+  wg_stage(pl, sm_head);
+  asm volatile("" ::"s"(params), "s"(features), "s"(n_docs), "s"(docids), "s"(B), "s"(L), "s"(saved), "s"(ws));  // (as in wg_stage)
   const int64_t N = bp.N;
   if ((int)blockIdx.x >= bp.wgrad_blocks) {
     wg_spare_roles(p, bp, smem, ws, grads, loss_part, n_loss_part, tail, er, cd);
     return;
   }
+  lds_barrier();
   TRACE_STAMP(8);
-  int j = 0;
-  while (j + 1 < p.nl - 1 && (int)blockIdx.x >= bp.wl[j + 1].blk_begin) ++j;
-  const WgradLayer wl = bp.wl[j];
+  const WgHead hd = wg_head(sm_head, p.nl - 1, (int)blockIdx.x);
+  const int j = hd.j;
+  const WgradLayer wl = hd.wl;
   const int local = blockIdx.x - wl.blk_begin;
   const int split = local % wl.nsplit;
   const int tile = local / wl.nsplit;
@@ -134,9 +210,9 @@ __global__ __launch_bounds__(256) void dnn_wgrad_kernel(DnnPlan p, BwdPlan bp, c
   // layer 0 alone after a per-layer forward that wrote xhat_0 (it says so in the marker word behind the saved activations -
   // every forward writes that word, so the two calls cannot disagree)
   const bool prenorm = bp.wg_prenorm != 0 || (VEC && j == 0 && bp.l0g != 0 && saved[p.sv_total] != 0.f);
-  const Src xs = (j == 0 && !prenorm) ? make_src(features, n_docs * K) : make_src(saved + p.sv_x[j], N * K);
-  const Src meansrc = make_src(saved + p.sv_mean[j], N);
-  const Src rstdsrc = make_src(saved + p.sv_rstd[j], N);
+  const Src xs = (j == 0 && !prenorm) ? make_src(features, n_docs * K) : make_src(saved + hd.sv_x, N * K);
+  const Src meansrc = make_src(saved + hd.sv_mean, N);
+  const Src rstdsrc = make_src(saved + hd.sv_rstd, N);
   const int64_t nsplit0 = (int64_t)split * wl.rows_per_split;
   if (j == 0 && !prenorm) {
     // layer 0 reads feature rows through the doc ids: resolve them once into LDS so that the main loop has no
@@ -155,8 +231,8 @@ __global__ __launch_bounds__(256) void dnn_wgrad_kernel(DnnPlan p, BwdPlan bp, c
   }
   TRACE_STAMP(9);
   const bool l0g = (j == 0) && bp.l0g != 0;  // layer-0 shortcut: contract with xhat, apply gamma/beta in the epilogue
-  const float4 gam = l0g ? make_float4(1.f, 1.f, 1.f, 1.f) : ld4_masked(params + p.off_lnw[j], k0 + 4 * i, K, false);
-  const float4 bet = l0g ? make_float4(0.f, 0.f, 0.f, 0.f) : ld4_masked(params + p.off_lnb[j], k0 + 4 * i, K, false);
+  const float4 gam = l0g ? make_float4(1.f, 1.f, 1.f, 1.f) : ld4_masked(params + hd.off_lnw, k0 + 4 * i, K, false);
+  const float4 bet = l0g ? make_float4(0.f, 0.f, 0.f, 0.f) : ld4_masked(params + hd.off_lnb, k0 + 4 * i, K, false);
   // layer-0 shortcut: the epilogue's operands (this thread's four W_0 pieces, gamma_0, beta_0) are requested NOW and ride
   // through the main loop in registers - fetched in the epilogue they added ~4k cycles of exposed latency to its tail
   float4 l0w[4], l0g4 = make_float4(0.f, 0.f, 0.f, 0.f), l0b4 = l0g4;
@@ -398,13 +474,18 @@ __global__ __launch_bounds__(256) void dnn_wgrad_kernel(DnnPlan p, BwdPlan bp, c
 struct WhStep {
   u32x4 v[8];
 };
-__global__ __launch_bounds__(512) void dnn_wgrad_h3_kernel(DnnPlan p, BwdPlan bp, const float* __restrict__ params,
+__global__ __launch_bounds__(512) void dnn_wgrad_h3_kernel(WgPlans pl, const float* __restrict__ params,
                                                            const float* __restrict__ features, int64_t n_docs,
                                                            const int32_t* __restrict__ docids, int B, int L,
                                                            const float* __restrict__ saved, float* __restrict__ ws,
                                                            float* __restrict__ grads, const float* __restrict__ loss_part,
                                                            int n_loss_part, int tail, EarlyReport er, CommDev cd) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ int sm_head[WGH_DW];
+  const DnnPlan& p = pl.p;
+  const BwdPlan& bp = pl.bp;
+  wg_stage(pl, sm_head);
+  asm volatile("" ::"s"(params), "s"(features), "s"(n_docs), "s"(docids), "s"(B), "s"(L), "s"(saved), "s"(ws));  // (as in wg_stage)
   if ((int)blockIdx.x >= bp.wgrad_blocks) {
     if (threadIdx.x >= 256) return;  // (the spare roles are written for four waves)
     wg_spare_roles(p, bp, smem, ws, grads, loss_part, n_loss_part, tail, er, cd);
@@ -412,11 +493,12 @@ __global__ __launch_bounds__(512) void dnn_wgrad_h3_kernel(DnnPlan p, BwdPlan bp
   }
   const int lin = ((int)blockIdx.x & 7) * bp.wg_chunk + ((int)blockIdx.x >> 3);  // BwdPlan::wg_chunk
   if (lin >= bp.wg_live) return;
+  lds_barrier();
   const int split = lin / bp.wg_tiles2;
   const int tix = lin - split * bp.wg_tiles2;
-  int j = 0;
-  while (j + 1 < p.nl - 1 && tix >= bp.wl[j + 1].blk_begin) ++j;
-  const WgradLayer wl = bp.wl[j];
+  const WgHead hd = wg_head(sm_head, p.nl - 1, tix);
+  const int j = hd.j;
+  const WgradLayer wl = hd.wl;
   const int tile = tix - wl.blk_begin;
   const int mb2 = tile / wl.nkb2, kb2 = tile - mb2 * wl.nkb2;
   const int M = wl.M, K = wl.K;
@@ -441,8 +523,8 @@ __global__ __launch_bounds__(512) void dnn_wgrad_h3_kernel(DnnPlan p, BwdPlan bp
   int* sm_bump = sm_se + 8;                                                                  // [8] exponent decrease of the step in LDS
   float* sm_bsum = smem + WH_MAIN_BYTES / 4 + 16;                                            // [2 groups][2][64]
   if (xform) {
-    const float* mp = saved + p.sv_mean[j];
-    const float* rp = saved + p.sv_rstd[j];
+    const float* mp = saved + hd.sv_mean;
+    const float* rp = saved + hd.sv_rstd;
     for (int r = tid; r < 32 * (nsteps + 2); r += 512) sm_stat[r] = (r < rows) ? make_float2(mp[nbeg + r], rp[nbeg + r]) : make_float2(0.f, 0.f);
   }
   if (gather) {
@@ -465,7 +547,7 @@ __global__ __launch_bounds__(512) void dnn_wgrad_h3_kernel(DnnPlan p, BwdPlan bp
   const bool colok = col < ncols;
   // the buffer ends with this split's last row: rows of the tail step beyond it read as zeros, no per-row predicate
   const Src src = isA ? make_src(ws + wl.dz_off, (nbeg + rows) * M)
-                      : (gather ? make_src(features, n_docs * K) : make_src(saved + p.sv_x[j], (nbeg + rows) * K));
+                      : (gather ? make_src(features, n_docs * K) : make_src(saved + hd.sv_x, (nbeg + rows) * K));
   const unsigned stride = (unsigned)ncols * 4u;
   unsigned vo = colok ? (unsigned)(((nbeg + 32 * g + 8 * rg) * ncols + col) * 4) : ULTR_OOB;  // advanced by 64 rows per load_step
   int tl = g;  // step the next load_step fetches
@@ -474,8 +556,8 @@ __global__ __launch_bounds__(512) void dnn_wgrad_h3_kernel(DnnPlan p, BwdPlan bp
   if (!isA && xform && colok) {
     if (l0g) gam = make_float4(1.f, 1.f, 1.f, 1.f);
     else {
-      gam = ld4(params + p.off_lnw[j] + col);
-      bet = ld4(params + p.off_lnb[j] + col);
+      gam = ld4(params + hd.off_lnw + col);
+      bet = ld4(params + hd.off_lnb + col);
     }
   }
   const int swz_w = c16 & 3;  // (column >> 2) & 3 of the lane's four columns
@@ -756,6 +838,47 @@ __device__ __forceinline__ float block_sum_256(float v, float* sm) {
   return t;
 }
 
+// Segment look-up of the slab-reduction kernels (red_stage at the very top of the kernel, a workgroup barrier, red_lookup).
+// The table travels as a by-value kernel argument, and the argument segment is rewritten by every launch: each first touch of
+// one of its lines is a miss all the way to memory.  The look-up used to be a
+// per-thread `while (e >= rp.seg[s + 1].off) ++s; sg = rp.seg[s]` - vector loads of the argument segment, each one waiting for the
+// one before, a new line every fourth - so a workgroup deep in the table (W_1, the last layer's vectors) paid several such misses
+// in a row before it could ask for its first slab word.  Now every thread fetches ONE word of the table (address = threadIdx
+// only: a single round trip, together with the scalar arguments) into LDS, and the search runs on the copy: lane i of every wave
+// compares segment i's start with the FIRST and the LAST element of the workgroup (two ballots give the wave-uniform range
+// [s0, s1] of segments the workgroup touches; s0 == s1 for all but a handful of workgroups of a big model), a thread then
+// advances from s0 by at most s1 - s0 uniform-address LDS reads, none of which depends on another.  The result is the segment
+// the `while` loop gave for every element (it stops at the first segment that starts beyond e: so does the count of leading ones).
+static_assert(sizeof(RedSeg) == 32 && offsetof(RedPlan, seg) == 8 && sizeof(RedPlan) == 8 + 256 * 4, "red_stage copies 256 words behind nseg");
+__device__ __forceinline__ void red_stage(const RedPlan& rp, int* __restrict__ sm_seg) {
+  sm_seg[threadIdx.x] = reinterpret_cast<const int*>(&rp)[2 + threadIdx.x];  // 256 threads: all 4 * ULTR_MAXL records
+  // (the kernels then name their scalar arguments in one empty asm: all of them are requested in this same round trip, not where
+  // each is first used, one wait behind the other)
+}
+// e0 / e1: first / last element of the workgroup (e1 < P); every lane of the wave must call (ballots), whatever its e
+__device__ __forceinline__ RedSeg red_lookup(const int* __restrict__ sm_seg, int nseg, int64_t e0, int64_t e1, int64_t e) {
+  const int64_t* off = reinterpret_cast<const int64_t*>(sm_seg);  // segment i starts at off[4 * i]
+  const int lane = threadIdx.x & 63;
+  const int64_t off_l = off[4 * (lane & 31)];
+  const bool in = lane >= 1 && lane < nseg;
+  const unsigned long long b0 = __ballot(in && e0 >= off_l), b1 = __ballot(in && e1 >= off_l);
+  const int s0 = __builtin_ctzll(~(b0 >> 1)), s1 = __builtin_ctzll(~(b1 >> 1));  // leading ones from segment 1 on
+  int s = s0;
+  bool ok = true;
+  for (int i = s0 + 1; i <= s1; ++i) {
+    ok = ok && e >= off[4 * i];
+    s += ok ? 1 : 0;
+  }
+  const int4 a = *reinterpret_cast<const int4*>(sm_seg + 8 * s), b = *reinterpret_cast<const int4*>(sm_seg + 8 * s + 4);
+  RedSeg sg;
+  sg.off = (int64_t)(((unsigned long long)(unsigned)a.y << 32) | (unsigned)a.x);
+  sg.base = (int64_t)(((unsigned long long)(unsigned)a.w << 32) | (unsigned)a.z);
+  sg.stride = (int64_t)(((unsigned long long)(unsigned)b.y << 32) | (unsigned)b.x);
+  sg.len = b.z;
+  sg.nparts = b.w;
+  return sg;
+}
+
 // ONE = a thread folds all partials of its element (full_sum: the same bits as the four cooperating groups of strided_sum),
 // 256 elements per workgroup: a quarter of the workgroups for the same work when there are at most 32 slabs per segment
 // (config 2: 1600 -> 400 workgroups, no change in time; config 4: 11.9 -> 8.8 us).  Sum-of-squares partials keep their geometry (one per 64 elements).
@@ -765,7 +888,11 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(RedPlan rp, int64_t P,
                                                           float* __restrict__ grads, float* __restrict__ sumsq_part, int nsq,
                                                           float* __restrict__ sumsq2) {
   __shared__ float sm[4][64];
+  __shared__ __attribute__((aligned(16))) int sm_seg[256];  // the segment table (red_stage)
   const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
+  TRACE_STAMP_B(1, 0);  // phase trace of the reduction (tools/trace_phases.py): entry, 1 segment known, 2 slab words arrived, 3 block sum, 4 end
+  red_stage(rp, sm_seg);  // ahead of the role split: nothing before the table's load waits for another argument
+  asm volatile("" ::"s"(rp.nseg), "s"(P), "s"(ws), "s"(grads), "s"(sumsq_part), "s"(nsq), "s"(sumsq2), "s"(n_loss_part));
   if (n_loss_part > 0 && blockIdx.x == gridDim.x - 1) {
     // second level of the loss-partial fold (see dnn_wgrad_kernel): loss_part = [n_loss_part][tail] chunk sums
     for (int t0 = 0; t0 < tail; t0 += 64) {
@@ -777,16 +904,19 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(RedPlan rp, int64_t P,
     }
     return;
   }
+  lds_barrier();
   if constexpr (ONE) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * 256, e = e0 + threadIdx.x;
+    const RedSeg sg = red_lookup(sm_seg, rp.nseg, e0, e0 + 255 < P ? e0 + 255 : P - 1, e);
+    TRACE_AFTER(sg.nparts);
+    TRACE_STAMP_B(1, 1);
     float g = 0.f;
     if (e < P) {
-      int s = 0;
-      while (s + 1 < rp.nseg && e >= rp.seg[s + 1].off) ++s;
-      const RedSeg sg = rp.seg[s];
       g = full_sum(ws + sg.base + (e - sg.off), sg.stride, sg.nparts);
       grads[e] = g;
     }
+    TRACE_AFTER(g);
+    TRACE_STAMP_B(1, 2);
     // the product must be ROUNDED before the first cross-lane add: left alone (and with __fmul_rn as well) hipcc turns
     // `g * g + shuffled(g * g)` into an fma in this variant and not in the other - one-ulp different partials, a different clip
     // coefficient, forked trajectories.  The empty asm makes the product opaque.
@@ -795,21 +925,21 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(RedPlan rp, int64_t P,
     const float sq = wave_sum(gg);
     const int k = (int)blockIdx.x * 4 + grp;
     if (lane == 0 && k < nsq) sumsq_part[k] = sq;
+    TRACE_AFTER(sq);
+    TRACE_STAMP_B(1, 3);
     if (sumsq2 != nullptr) {  // level 2: the block's four partials in order (partials beyond nsq are sums of zeros)
       if (lane == 0) sm[0][grp] = sq;
       __syncthreads();
       if (threadIdx.x == 0) sumsq2[blockIdx.x] = ((sm[0][0] + sm[0][1]) + sm[0][2]) + sm[0][3];
     }
+    TRACE_STAMP_B(1, 4);
     return;
   }
-  const int64_t e = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t e0 = (int64_t)blockIdx.x * 64, e = e0 + lane;
+  const RedSeg sg = red_lookup(sm_seg, rp.nseg, e0, e0 + 63 < P ? e0 + 63 : P - 1, e);
   float part = 0.f;
-  if (e < P) {
-    int s = 0;
-    while (s + 1 < rp.nseg && e >= rp.seg[s + 1].off) ++s;
-    const RedSeg sg = rp.seg[s];
-    part = strided_sum(ws + sg.base + (e - sg.off), sg.stride, sg.nparts, grp);
-  }  // the step tail grads[P ..] was written by the wgrad launch's last spare workgroup
+  // (the step tail grads[P ..] was written by the wgrad launch's last spare workgroup)
+  if (e < P) part = strided_sum(ws + sg.base + (e - sg.off), sg.stride, sg.nparts, grp);
   sm[grp][lane] = part;
   __syncthreads();
   if (grp == 0) {
@@ -835,15 +965,17 @@ __global__ __launch_bounds__(256) void grad_reduce_xchg_kernel(RedPlan rp, int64
   __shared__ int sm_fail;
   __shared__ float sm_head[4];
   __shared__ float sm_sq[4];
+  __shared__ __attribute__((aligned(16))) int sm_seg[256];  // the segment table (red_stage)
   const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6;
   const int64_t n = P + tail;
-  const int64_t e = (int64_t)blockIdx.x * 256 + tid;
+  const int64_t e0 = (int64_t)blockIdx.x * 256, e = e0 + tid;
   if (tid == 0) sm_fail = 0;
+  red_stage(rp, sm_seg);
+  asm volatile("" ::"s"(rp.nseg), "s"(P), "s"(tail), "s"(ws), "s"(grads), "s"(sumsq_part), "s"(nsq), "s"(sumsq2), "s"(er.host));
+  lds_barrier();
+  const RedSeg sg = red_lookup(sm_seg, rp.nseg, e0, e0 + 255 < P ? e0 + 255 : P - 1, e);
   float g = 0.f;
   if (e < P) {
-    int s = 0;
-    while (s + 1 < rp.nseg && e >= rp.seg[s + 1].off) ++s;
-    const RedSeg sg = rp.seg[s];
     g = full_sum(ws + sg.base + (e - sg.off), sg.stride, sg.nparts);
   } else if (e < n) {
     g = grads[e];
@@ -904,20 +1036,21 @@ int ultr_launch_dnn_wgrad(UltrProfScope& prof, const DnnPlan& p, const BwdPlan& 
                           const float* saved, float* ws, int l0_vec, float* grads, const float* lp, int nlp, int tail, const EarlyReport& er,
                           const CommDev& cd) {
   hipError_t e;
+  const WgPlans pl = {p, bp};
   if (h3) {
     e = set_lds(dnn_wgrad_h3_kernel, (size_t)WH_LDS_BYTES);
     if (e != hipSuccess) return (int)e;
-    ULTR_LAUNCH(prof, dnn_wgrad_h3_kernel, wgrid, dim3(512), (size_t)WH_LDS_BYTES, st, p, bp, params, features, n_docs, docids, batch,
+    ULTR_LAUNCH(prof, dnn_wgrad_h3_kernel, wgrid, dim3(512), (size_t)WH_LDS_BYTES, st, pl, params, features, n_docs, docids, batch,
                 list_size, saved, ws, grads, lp, nlp, tail, er, cd);
     return (int)hipGetLastError();
   }
   e = av ? set_lds(dnn_wgrad_kernel<true>, wlds) : set_lds(dnn_wgrad_kernel<false>, wlds);
   if (e != hipSuccess) return (int)e;
   if (av)
-    ULTR_LAUNCH(prof, dnn_wgrad_kernel<true>, wgrid, dim3(256), wlds, st, p, bp, params, features, n_docs, docids, batch, list_size, saved, ws,
+    ULTR_LAUNCH(prof, dnn_wgrad_kernel<true>, wgrid, dim3(256), wlds, st, pl, params, features, n_docs, docids, batch, list_size, saved, ws,
                 l0_vec, grads, lp, nlp, tail, er, cd);
   else
-    ULTR_LAUNCH(prof, dnn_wgrad_kernel<false>, wgrid, dim3(256), wlds, st, p, bp, params, features, n_docs, docids, batch, list_size, saved, ws,
+    ULTR_LAUNCH(prof, dnn_wgrad_kernel<false>, wgrid, dim3(256), wlds, st, pl, params, features, n_docs, docids, batch, list_size, saved, ws,
                 l0_vec, grads, lp, nlp, tail, er, cd);
   return (int)hipGetLastError();
 }
@@ -992,7 +1125,8 @@ int ultr_wgrad_h3_plain(const float* dY, const float* X, int64_t T, int M, int K
   EarlyReport er = {nullptr, 0u, 0, 1.0f};
   CommDev cd;
   memset(&cd, 0, sizeof(cd));
-  hipLaunchKernelGGL(dnn_wgrad_h3_kernel, dim3((unsigned)bp.wgrad_blocks), dim3(512), (size_t)WH_LDS_BYTES, st, p, bp, (const float*)nullptr,
+  const WgPlans pl = {p, bp};
+  hipLaunchKernelGGL(dnn_wgrad_h3_kernel, dim3((unsigned)bp.wgrad_blocks), dim3(512), (size_t)WH_LDS_BYTES, st, pl, (const float*)nullptr,
                      (const float*)nullptr, (int64_t)0, (const int32_t*)nullptr, 1, 1, X, const_cast<float*>(dY), (float*)nullptr,
                      (const float*)nullptr, 0, 0, er, cd);
   return (int)hipGetLastError();

@@ -3,6 +3,16 @@
 // A plan is plain-old-data computed on the host from (ultr_dnn_desc, n_rows) and passed BY VALUE
 // as a kernel argument, so kernels never chase pointers for their geometry.  All offsets are in
 // floats.  Row n of the batch is document (b = n / L, l = n % L); its id is docids[l*B + b].
+//
+// The argument segment is rewritten by every launch: the first touch of each of its lines is a miss to memory (~2k cycles), and
+// a read whose index comes out of another read of it waits for that one first.  So no kernel walks a plan entry by entry on its
+// critical path.  Fields with a fixed index are plain scalar loads, all requested at the top of the kernel.  Whatever is indexed at
+// run time (by layer, by segment, by tile) is first copied into LDS - one load per thread, address = threadIdx only, in the same
+// round trip as the scalars - and searched / read there: FbPlan in dnn_fb_kernel; bp.wl[] and the per-layer offsets in the
+// weight-gradient kernels (wg_stage / wg_head, ultr_dnn_wgrad.hip); RedPlan in the slab reductions (red_stage / red_lookup); the
+// update's work map (upd_at, ultr_update.hip).  The plans stay by-value arguments built per call from the model's shape and
+// (B, L): nothing is cached on the device, so nothing can go stale when the shape, the batch or the launch mode changes, and
+// every caller (ultr_train_step, the stage API, SetRank's ultr_wgrad_h3_plain, plans re-made with wg_mode 0) takes the same path.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

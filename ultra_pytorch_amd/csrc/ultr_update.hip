@@ -15,6 +15,28 @@
 #include "ultr_feed.h"
 #include "ultr_prof.h"
 
+// Optional phase tracing (-DULTR_TRACE, as ultr_dnn_kernels.h): update_tiled_kernel stamps bank 2 of this unit's array - 0 entry,
+// 1 indices known, 2 gradient / parameter / state words arrived, 3 after the sum-of-squares block sum, 4 end (tools/trace_phases.py)
+#ifdef ULTR_TRACE
+static __device__ unsigned long long g_upd_trace[3 * 64 * 32];
+#define UPD_STAMP(slot)                                                                        \
+  do {                                                                                         \
+    if (threadIdx.x == 0 && (blockIdx.x & 31) == 0 && (blockIdx.x >> 5) < 64)                  \
+      g_upd_trace[2 * 2048 + (blockIdx.x >> 5) * 32 + (slot)] = __builtin_amdgcn_s_memtime();  \
+  } while (0)
+#define UPD_AFTER(v) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"(v) : "memory")
+int ultr_trace_read_update(unsigned long long* host_out) {
+  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_upd_trace), sizeof(unsigned long long) * 3 * 64 * 32);
+}
+#else
+#define UPD_STAMP(slot) \
+  do {                  \
+  } while (0)
+#define UPD_AFTER(v) \
+  do {               \
+  } while (0)
+#endif
+
 __device__ __forceinline__ float block_sum256(float v, float* sm) {
   v = wave_sum(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -286,6 +308,34 @@ __global__ __launch_bounds__(256) void update_kernel(ultr_update_desc u, DnnPlan
   update_body<1>(u, dp, params, state, grads + P, aux, ss, ea, g_raw, p_old, s_old, pn, sm, scalars_out, l2_sums, u.range_flag);
 }
 
+// The update's work map (DnnPlan::upd_* / vs_* and the K, M, off_w of the layers) in LDS.  DnnPlan is a by-value kernel
+// argument of 1.6 KB and the argument segment is rewritten by every launch: the old head chained runtime-indexed reads of it
+// (upd_tile_begin[nl - 1], the `while` over upd_tile_begin[j + 1], upd_ntk[j], M[j], K[j], off_w[j]; per THREAD over vs_begin[] in
+// the vector workgroups), each on another cold line and each waiting for the one before, ahead of the first gradient word.
+// update_tiled_kernel copies two pieces of the plan - words [0, UPD_A_DW): nl .. off_w[], and [UPD_B0, UPD_B0 + UPD_B_DW):
+// upd_tile_begin .. vs_begin[] - with one load per thread and searches the copy.
+#define UPD_A_DW ((int)(offsetof(DnnPlan, off_b) / 4))
+#define UPD_B0 ((int)(offsetof(DnnPlan, upd_tile_begin) / 4))
+#define UPD_B_DW ((int)(offsetof(DnnPlan, fwd_ksplit) / 4) - UPD_B0)
+static_assert(UPD_A_DW + UPD_B_DW <= 256, "one word per thread");
+static_assert(offsetof(DnnPlan, off_w) < offsetof(DnnPlan, off_b) && offsetof(DnnPlan, M) < offsetof(DnnPlan, off_b) &&
+              offsetof(DnnPlan, upd_ntk) > offsetof(DnnPlan, upd_tile_begin) && offsetof(DnnPlan, vs_begin) < offsetof(DnnPlan, fwd_ksplit) &&
+              offsetof(DnnPlan, vs_off) > offsetof(DnnPlan, upd_tile_begin) && offsetof(DnnPlan, vs_pv) < offsetof(DnnPlan, fwd_ksplit),
+              "the staged pieces hold every field the head reads");
+// index of the staged copy of the word at byte `off` of DnnPlan
+__device__ __forceinline__ constexpr int upd_at(size_t off) {
+  return (int)(off / 4) < UPD_A_DW ? (int)(off / 4) : UPD_A_DW + (int)(off / 4) - UPD_B0;
+}
+// element j (workgroup-uniform) of an int / int64 array of the plan, as a scalar
+__device__ __forceinline__ int upd_u(const int* sm_plan, size_t off, int j) {
+  return __builtin_amdgcn_readfirstlane(sm_plan[upd_at(off) + j]);
+}
+__device__ __forceinline__ int64_t upd_u64(const int* sm_plan, size_t off, int j) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane(sm_plan[upd_at(off) + 2 * j]);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane(sm_plan[upd_at(off) + 2 * j + 1]);
+  return (int64_t)(((unsigned long long)hi << 32) | lo);
+}
+
 // Variant that keeps the k-major weight copy and the vector-parameter image current (DnnPlan::wt_*).  Workgroups
 // [0, n_tiles): one 16x16 tile of a hidden W_j - thread (r, c) updates W_j[m0 + r][k0 + c] (64-byte row segments) and
 // the tile goes out transposed through LDS as WT_j[k0 + r][m0 + c] (64-byte segments again; a per-element scatter wrote
@@ -303,16 +353,29 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
                                                            const float* __restrict__ l2_sums, int nsq2, int rider_first, ultr_click_args rider) {
   __shared__ float sm[4];
   __shared__ float tile[TPW][16][17];
+  __shared__ int sm_plan[UPD_A_DW + UPD_B_DW];
   // workgroups behind the update's own: the click draw of the NEXT batch (ultr_feed_train_step) - independent of the update, and of
   // its guard (a feed keeps drawing when a data-parallel step was refused)
+  const int tid = threadIdx.x, r = tid >> 4, c = tid & 15, lane = tid & 63;
+  UPD_STAMP(0);
+  // the work map -> LDS (upd_at): one word per thread, address = threadIdx only, in the same round trip as the scalar arguments -
+  // ahead of the role split and the guard, so that nothing before this load waits for another argument
+  const int pw = reinterpret_cast<const int*>(&dp)[tid < UPD_A_DW ? tid : tid < UPD_A_DW + UPD_B_DW ? UPD_B0 + tid - UPD_A_DW : 0];
+  // (... and so are the scalar arguments of the head: named here, all of them are fetched now instead of one wait after the other)
+  asm volatile("" ::"s"(rider_first), "s"(u.guard), "s"(u.n_params), "s"(dp.nl), "s"(dp.n_vs), "s"(n_tile_blocks), "s"(grads), "s"(params),
+               "s"(state), "s"(sumsq_part), "s"(nsq), "s"(nsq2),
+               "v"(pw));  // (the staged word is an operand too: its load cannot be scheduled behind the wait for the scalars)
+  if (tid < UPD_A_DW + UPD_B_DW) sm_plan[tid] = pw;
   if ((int)blockIdx.x >= rider_first) {
     click_draw(rider, (int)blockIdx.x - rider_first);
     return;
   }
   if (update_guarded(u)) return;
   const int64_t P = u.n_params;
-  const int n_tiles = dp.upd_tile_begin[dp.nl - 1];
-  const int tid = threadIdx.x, r = tid >> 4, c = tid & 15;
+  __syncthreads();
+  const int nl = dp.nl;
+  const int tbeg = sm_plan[upd_at(offsetof(DnnPlan, upd_tile_begin)) + (lane & 15)];  // lane i: first tile of layer i, i <= ULTR_MAXL
+  const int n_tiles = __builtin_amdgcn_readlane(tbeg, nl - 1);
   int64_t ea[TPW];
   int jj[TPW], m0[TPW], k0[TPW], pvpos[TPW];
   const bool is_tile = (int)blockIdx.x < n_tile_blocks;
@@ -322,25 +385,49 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
     if (is_tile) {
       const int tb = (int)blockIdx.x * TPW + q;
       if (tb < n_tiles) {
-        int j = 0;
-        while (j + 1 < dp.nl - 1 && tb >= dp.upd_tile_begin[j + 1]) ++j;
-        const int t = tb - dp.upd_tile_begin[j];
-        const int tm = t / dp.upd_ntk[j];
+        // the layer of tile tb: lane i compares with layer i's first tile; the leading ones from layer 1 on are what
+        // `while (j + 1 < nl - 1 && tb >= upd_tile_begin[j + 1]) ++j` counted
+        const unsigned long long bal = __ballot(lane >= 1 && lane < nl - 1 && tb >= tbeg);
+        const int j = __builtin_ctzll(~(bal >> 1));
+        const int t = tb - __builtin_amdgcn_readlane(tbeg, j);
+        const int ntk = upd_u(sm_plan, offsetof(DnnPlan, upd_ntk), j);
+        const int Mj = upd_u(sm_plan, offsetof(DnnPlan, M), j), Kj = upd_u(sm_plan, offsetof(DnnPlan, K), j);
+        const int64_t ow = upd_u64(sm_plan, offsetof(DnnPlan, off_w), j);
+        const int tm = t / ntk;
         jj[q] = j;
         m0[q] = tm * 16;
-        k0[q] = (t - tm * dp.upd_ntk[j]) * 16;
-        if (m0[q] + r < dp.M[j] && k0[q] + c < dp.K[j]) ea[q] = dp.off_w[j] + (int64_t)(m0[q] + r) * dp.K[j] + k0[q] + c;
+        k0[q] = (t - tm * ntk) * 16;
+        if (m0[q] + r < Mj && k0[q] + c < Kj) ea[q] = ow + (int64_t)(m0[q] + r) * Kj + k0[q] + c;
       }
     } else {
-      const int v = (((int)blockIdx.x - n_tile_blocks) * TPW + q) * 256 + tid;
-      if (v < dp.vs_begin[dp.n_vs]) {
-        int sg = 0;
-        while (sg + 1 < dp.n_vs && v >= dp.vs_begin[sg + 1]) ++sg;
-        ea[q] = dp.vs_off[sg] + (v - dp.vs_begin[sg]);
-        pvpos[q] = dp.vs_pv[sg] + (v - dp.vs_begin[sg]);
+      // vector parameters: the segments the workgroup's 256 elements touch are [s0, s1] (two ballots over the segment starts,
+      // as in the slab reduction's red_lookup); a thread advances from s0 by uniform-address LDS reads
+      const int n_vs = dp.n_vs;
+      const int vs_begin = upd_at(offsetof(DnnPlan, vs_begin));
+      const int n_vec = sm_plan[vs_begin + n_vs];
+      const int v0 = (((int)blockIdx.x - n_tile_blocks) * TPW + q) * 256, v = v0 + tid;
+      const int v1 = v0 + 255 < n_vec ? v0 + 255 : n_vec - 1;
+      const int vb = sm_plan[vs_begin + (lane < 2 * ULTR_MAXL + 2 ? lane : 2 * ULTR_MAXL + 2)];
+      const bool in = lane >= 1 && lane < n_vs;
+      const unsigned long long b0 = __ballot(in && v0 >= vb), b1 = __ballot(in && v1 >= vb);
+      const int s0 = __builtin_ctzll(~(b0 >> 1)), s1 = __builtin_ctzll(~(b1 >> 1));
+      int sg = s0;
+      bool ok = true;
+      for (int i = s0 + 1; i <= s1; ++i) {
+        ok = ok && v >= sm_plan[vs_begin + i];
+        sg += ok ? 1 : 0;
+      }
+      if (v < n_vec) {
+        const int at = upd_at(offsetof(DnnPlan, vs_off)) + 2 * sg;
+        const int64_t vo = (int64_t)(((unsigned long long)(unsigned)sm_plan[at + 1] << 32) | (unsigned)sm_plan[at]);
+        const int d = v - sm_plan[vs_begin + sg];
+        ea[q] = vo + d;
+        pvpos[q] = sm_plan[upd_at(offsetof(DnnPlan, vs_pv)) + sg] + d;
       }
     }
   }
+  UPD_AFTER((int)ea[0]);
+  UPD_STAMP(1);
   float g_raw[TPW], p_old[TPW], s_old[TPW];
 #pragma unroll
   for (int q = 0; q < TPW; ++q) {
@@ -349,6 +436,10 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
     p_old[q] = live ? params[ea[q]] : 0.f;
     s_old[q] = (live && state != nullptr) ? state[ea[q]] : 0.f;
   }
+#ifdef ULTR_TRACE
+  UPD_AFTER(g_raw[0] + p_old[0] + s_old[0]);
+  UPD_STAMP(2);
+#endif
   float ss = 0.f;
   if (nsq2 > 0) {  // level-2 partials of this step's reduction launch (ultr_sumsq2_off): a quarter of the words every workgroup reads
     const float* s2 = sumsq_part + ultr_sumsq2_off(P);
@@ -357,6 +448,8 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
     ss = sumsq_level1_as_level2(sumsq_part, nsq, tid);
   }
   ss = block_sum256(ss, sm);
+  UPD_AFTER(ss);
+  UPD_STAMP(3);
   float pn[TPW];
   // block 0's extra duties (EM / propensity updates, step scalars) run inside update_body and need all 256 threads
   if (blockIdx.x != 0) {
@@ -436,6 +529,7 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
     for (int q = 0; q < TPW; ++q)
       if (pvpos[q] >= 0) wt[dp.wt_pv_off + pvpos[q]] = pn[q];
   }
+  UPD_STAMP(4);
 }
 
 extern "C" int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state,
