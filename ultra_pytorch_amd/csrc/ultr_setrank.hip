@@ -8,7 +8,9 @@
 //     WITHOUT Q/K/V projections (the heads are slices of x itself, SetRank.py:57-66) lives in ultr_sr_attn.hip, the fused
 //     persistent launches of the encoder blocks in ultr_sr_fwd.hip / ultr_sr_bwd.hip (round 6);
 //   * deterministic: no atomics; every partial sum (slabs, row-block partials) is folded in a fixed order, all folds of a
-//     backward in ONE launch at its end (sr_fold_all_kernel).
+//     backward in ONE launch at its end (sr_fold_all_kernel);
+//   * no state between or beside calls: ultr_setrank_forward / _backward build ONE SrCall on their stack (plan, parameters, split-half
+//     planes, a copy of the knobs, CU count, buffers, stream, the backward's FoldQueue) and every host helper takes it.
 // Token n = b*L + l (list-major), all activations row-major [T, width].  Parameters: ONE flat vector in the
 // reference's state_dict order (ultr_setrank_param_offsets).
 #include <hip/hip_runtime.h>
@@ -733,60 +735,50 @@ __global__ __launch_bounds__(256) void sr_fold_all_kernel(FoldTable t) {
     if (grp == 0 && c < jb.len) jb.dst[c] = ((sm[lane] + sm[64 + lane]) + sm[128 + lane]) + sm[192 + lane];
   }
 }
-struct FoldCtx {
-  bool active = false;
-  int64_t used = 0, cap = 0;
-  float* arena = nullptr;
-  FoldTable tab;
-};
-thread_local FoldCtx g_folds;
-// scratch for one producer's partials: a fresh arena piece while a backward is queueing, the shared region otherwise
-float* part_scratch(float* shared_region, int64_t floats) {
-  FoldCtx& f = g_folds;
-  const int64_t need = (floats + 3) & ~(int64_t)3;
-  if (f.active && f.used + need <= f.cap && f.tab.n + 2 <= SR_MAX_FOLDS) {
-    float* at = f.arena + f.used;
-    f.used += need;
+// The queue of ONE backward, on setrank_backward's stack: flush() launches what was queued (an early error return just drops it).
+struct FoldQueue {
+  float* arena;
+  int64_t cap, used;
+  FoldTable tab;  // (never zeroed: sr_fold_all_kernel reads job[0 .. n) only)
+  FoldQueue(float* arena_, int64_t cap_) : arena(arena_), cap(cap_), used(0) { tab.n = 0; tab.nblocks = 0; }
+  // scratch for one producer's partials: a fresh arena piece while there is room, the shared region otherwise
+  float* scratch(float* shared_region, int64_t floats) {
+    const int64_t need = (floats + 3) & ~(int64_t)3;
+    if (used + need <= cap && tab.n + 2 <= SR_MAX_FOLDS) {
+      float* at = arena + used;
+      used += need;
+      return at;
+    }
+    return shared_region;
+  }
+  // a piece of the arena or NULL (producers whose partials do not fit the shared region)
+  float* piece(int64_t floats) {
+    const int64_t need = (floats + 3) & ~(int64_t)3;
+    if (!(used + need <= cap && tab.n + 4 <= SR_MAX_FOLDS)) return nullptr;
+    float* at = arena + used;
+    used += need;
     return at;
   }
-  return shared_region;
-}
-// a piece of the arena or NULL (producers whose partials do not fit the shared region)
-float* arena_piece(int64_t floats) {
-  FoldCtx& f = g_folds;
-  const int64_t need = (floats + 3) & ~(int64_t)3;
-  if (!(f.active && f.used + need <= f.cap && f.tab.n + 4 <= SR_MAX_FOLDS)) return nullptr;
-  float* at = f.arena + f.used;
-  f.used += need;
-  return at;
-}
-void fold(const float* part, int64_t stride, int nparts, int len, float* dst, hipStream_t st, bool own_buffer = false) {
-  FoldCtx& f = g_folds;
-  const bool wide = nparts >= 256;
-  const bool in_arena = f.active && part >= f.arena && part < f.arena + f.cap;
-  if (f.active && (in_arena || own_buffer) && f.tab.n < SR_MAX_FOLDS) {
-    FoldJob& j = f.tab.job[f.tab.n++];
-    // (a partial is a 16-byte-aligned run of `stride` = 4 k floats and `part` starts 4 m floats into it: the last float4 of a row stays inside)
-    const bool vec4 = wide && len >= 1024 && (stride & 3) == 0 && ((uintptr_t)part & 15) == 0;
-    j.part = part; j.dst = dst; j.stride = stride; j.nparts = nparts; j.len = len; j.wide = vec4 ? 2 : (wide ? 1 : 0);
-    j.blk_begin = f.tab.nblocks;
-    f.tab.nblocks += (wide && !vec4) ? (len + 15) / 16 : (len + 63) / 64;
-    return;
+  // queues the fold of partials that nobody overwrites before flush() (an arena piece, or the caller's own buffer); a partial in a
+  // shared region, or one more than the table holds, is folded by a launch of its own right here
+  void add(const float* part, int64_t stride, int nparts, int len, float* dst, hipStream_t st, bool own_buffer = false) {
+    const bool wide = nparts >= 256;
+    const bool in_arena = part >= arena && part < arena + cap;
+    if ((in_arena || own_buffer) && tab.n < SR_MAX_FOLDS) {
+      FoldJob& j = tab.job[tab.n++];
+      // (a partial is a 16-byte-aligned run of `stride` = 4 k floats and `part` starts 4 m floats into it: the last float4 of a row stays inside)
+      const bool vec4 = wide && len >= 1024 && (stride & 3) == 0 && ((uintptr_t)part & 15) == 0;
+      j.part = part; j.dst = dst; j.stride = stride; j.nparts = nparts; j.len = len; j.wide = vec4 ? 2 : (wide ? 1 : 0);
+      j.blk_begin = tab.nblocks;
+      tab.nblocks += (wide && !vec4) ? (len + 15) / 16 : (len + 63) / 64;
+      return;
+    }
+    if (wide) hipLaunchKernelGGL(sr_fold16_kernel, dim3((len + 15) / 16), dim3(256), 0, st, part, stride, nparts, len, dst);
+    else hipLaunchKernelGGL(sr_fold_kernel, dim3((len + 63) / 64), dim3(256), 0, st, part, stride, nparts, len, dst);
   }
-  if (wide) hipLaunchKernelGGL(sr_fold16_kernel, dim3((len + 15) / 16), dim3(256), 0, st, part, stride, nparts, len, dst);
-  else hipLaunchKernelGGL(sr_fold_kernel, dim3((len + 63) / 64), dim3(256), 0, st, part, stride, nparts, len, dst);
-}
-// RAII: queue folds for the lifetime of the scope; flush() launches them (an early error return just drops the queue)
-struct FoldScope {
-  FoldScope(float* arena, int64_t cap) {
-    FoldCtx& f = g_folds;
-    f.active = true; f.used = 0; f.cap = cap; f.arena = arena; f.tab.n = 0; f.tab.nblocks = 0;
-  }
-  ~FoldScope() { g_folds.active = false; }
   void flush(hipStream_t st) {
-    FoldCtx& f = g_folds;
-    if (f.tab.n > 0) hipLaunchKernelGGL(sr_fold_all_kernel, dim3(f.tab.nblocks), dim3(256), 0, st, f.tab);
-    f.tab.n = 0; f.tab.nblocks = 0; f.used = 0;
+    if (tab.n > 0) hipLaunchKernelGGL(sr_fold_all_kernel, dim3(tab.nblocks), dim3(256), 0, st, tab);
+    tab.n = 0; tab.nblocks = 0; used = 0;
   }
 };
 
@@ -1062,144 +1054,187 @@ __global__ __launch_bounds__(256) void sr_split_planes_kernel(SrSplitTable tb, c
   dst[e] = hi;
   dst[(int64_t)rows * ld + e] = lo;
 }
-// the planes of the step in flight (set by ultr_setrank_forward / _backward around their GEMM calls)
-struct SrH3Ctx {
-  const float* params;
-  const _Float16* planes;
-  const SrPlan* plan;
+// Knobs of this file (README.md): read from the environment ONCE (first use), replaced whole by ultr_config_reload(); every call
+// takes one copy into its context, so one forward or backward sees one set of values.
+struct SrKnobs {
+  bool loaded;
+  int h3;         // ULTR_SR_H3 (default 1): the Linear products on split-half planes of the weights (fp16 matrix cores); 0: fp32 matrix cores
+  int attn_h3;    // ULTR_SR_ATTN_H3 0: fp32 matrix cores; 1 (default): split-half BACKWARD kernel (the forward always runs on the fp32 matrix cores)
+  int attn_mask;  // ULTR_SR_ATTN_H3_MASK (default -1 = all), debug: bit (2 layer + dir), dir 0 forward / 1 backward
+  int wg_h3;      // ULTR_SR_WG_H3 (default 1): square-ish weight gradients on the DNN's split-half weight-gradient kernel
+  int bwd_fused;  // ULTR_SR_BWD_FUSED bits (default 7 = all): 1 the row-local chain of a block's backward as two launches (ultr_sr_bwd.hip)
+                  // instead of seven, 2 the output FFN's backward as one instead of three, 4 the embedding FFN's
+  int block;      // ULTR_SR_BLOCK 0: off; 1: one 16-wave workgroup per CU; 2: two 8-wave workgroups per CU; 3 (default): the persistent kernel of round 6 where its widths apply, 2 elsewhere
 };
-thread_local SrH3Ctx g_sr_h3 = {nullptr, nullptr, nullptr};
-// knobs of this file: read at first use, re-read after ultr_config_reload()
-int g_sr_knob_h3 = -1, g_sr_knob_attn_h3 = -1, g_sr_knob_attn_mask = 0, g_sr_knob_wg_h3 = -1, g_sr_knob_bwd_fused = 1;
+SrKnobs g_knobs = {};
 void sr_knobs_load() {
-  if (g_sr_knob_h3 >= 0) return;
-  const char* e = getenv("ULTR_SR_H3");
-  g_sr_knob_h3 = (e && *e) ? atoi(e) : 1;
-  e = getenv("ULTR_SR_ATTN_H3");  // 0: fp32 matrix cores; 1 (default): split-half BACKWARD kernel (the forward always runs on the fp32 matrix cores)
-  g_sr_knob_attn_h3 = (e && *e) ? atoi(e) : 1;
-  e = getenv("ULTR_SR_ATTN_H3_MASK");  // debug: bit (2 layer + dir), dir 0 forward / 1 backward
-  g_sr_knob_attn_mask = (e && *e) ? atoi(e) : -1;
-  e = getenv("ULTR_SR_WG_H3");
-  g_sr_knob_wg_h3 = (e && *e) ? atoi(e) : 1;
-  e = getenv("ULTR_SR_BWD_FUSED");  // bits (default 7 = all): 1 the row-local chain of a block's backward as two launches (ultr_sr_bwd.hip)
-  g_sr_knob_bwd_fused = (e && *e) ? atoi(e) : 7;  // instead of seven, 2 the output FFN's backward as one instead of three, 4 the embedding FFN's
+  auto num = [](const char* s, int dflt) { return (s && *s) ? atoi(s) : dflt; };
+  SrKnobs k;
+  k.h3 = num(getenv("ULTR_SR_H3"), 1);
+  k.attn_h3 = num(getenv("ULTR_SR_ATTN_H3"), 1);
+  k.attn_mask = num(getenv("ULTR_SR_ATTN_H3_MASK"), -1);
+  k.wg_h3 = num(getenv("ULTR_SR_WG_H3"), 1);
+  k.bwd_fused = num(getenv("ULTR_SR_BWD_FUSED"), 7);
+  k.block = num(getenv("ULTR_SR_BLOCK"), 3);
+  k.loaded = true;
+  g_knobs = k;
 }
-int sr_h3_enabled() {
-  sr_knobs_load();
-  return g_sr_knob_h3;
+const SrKnobs& sr_knobs() {
+  if (!g_knobs.loaded) sr_knobs_load();
+  return g_knobs;
 }
-const SrPlan::SplitMat* sr_find_split(const float* W, int M, int K) {
-  if (g_sr_h3.plan == nullptr || g_sr_h3.planes == nullptr || !sr_h3_enabled()) return nullptr;
-  const int64_t off = W - g_sr_h3.params;
-  for (int k = 0; k < g_sr_h3.plan->n_split; ++k) {
-    const SrPlan::SplitMat& m = g_sr_h3.plan->split[k];
-    if (m.off == off && m.M == M && m.K == K) return &m;
-  }
-  return nullptr;
+// compute units of the current device (the row tiling of the persistent launches)
+int sr_cu_count() {
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  return cus;
 }
 
-bool vec_ok(const void* a, const void* w, const void* c, int K, int ld_out) {
-  (void)w;
+#define SR_CHECK(call)        \
+  do {                        \
+    const int rc_ = (call);   \
+    if (rc_ != 0) return rc_; \
+  } while (0)
+
+// What ONE ultr_setrank_forward / _backward call hands to its helpers, built on that call's stack: the helpers below read no global.
+struct SrCall {
+  const SrPlan& p;
+  const float* params;
+  const _Float16* planes;  // split-half planes in `saved` (built by the forward); NULL: those products are off for this call (ULTR_SR_H3=0, ULTR_MODEL_FP32_PRODUCTS)
+  SrKnobs knobs;
+  int cus;
+  float* sv;               // `saved` (the backward only reads it)
+  float* ws;               // the backward's workspace, NULL in the forward
+  hipStream_t st;
+  FoldQueue* folds;        // the backward's, NULL in the forward
+  // the planes of the weight matrix W[M][K] at float offset `off` of the parameter vector, NULL: none (the product runs in fp32)
+  const SrPlan::SplitMat* split(int64_t off, int M, int K) const {
+    if (planes == nullptr) return nullptr;
+    for (int k = 0; k < p.n_split; ++k) {
+      const SrPlan::SplitMat& m = p.split[k];
+      if (m.off == off && m.M == M && m.K == K) return &m;
+    }
+    return nullptr;
+  }
+};
+
+bool vec_ok(const void* a, const void* c, int K, int ld_out) {
   return K % 4 == 0 && ld_out % 4 == 0 && ((((uintptr_t)a | (uintptr_t)c) & 15) == 0);
 }
+// the Linears below: X, Y, dY, dX are [T, .] with T = c.p.T, the weight W[M, K] sits at float offset `w` of the parameter vector
 // row-major  Y[T, M] = act(X[T, K] . W[M, K]^T + bias)      (bias may be NULL; relu 0 / 1)
-int gemm_xwT(const float* X, const float* W, const float* bias, float* Y, int64_t T, int K, int M, int relu, hipStream_t st) {
-  if (M >= 16 && vec_ok(X, W, Y, K, M) && T * (K > M ? K : M) * 4 < ((int64_t)1 << 31)) {
+int gemm_xwT(const SrCall& c, const float* X, int64_t w, const float* bias, float* Y, int K, int M, int relu) {
+  const int64_t T = c.p.T;
+  const float* W = c.params + w;
+  if (M >= 16 && vec_ok(X, Y, K, M) && T * (K > M ? K : M) * 4 < ((int64_t)1 << 31)) {
     const ugemm::APlain a{X, T, K, K};
     const ugemm::EBiasAct e{Y, bias, M, relu ? 1 : -1};
-    if (const SrPlan::SplitMat* sm = sr_find_split(W, M, K)) {  // split-half planes of W: the product on the fp16 matrix cores
+    if (const SrPlan::SplitMat* sm = c.split(w, M, K)) {  // split-half planes of W: the product on the fp16 matrix cores
       const ugemm::Dims dh{T, M, K, sm->ldK};
-      const _Float16* hi = g_sr_h3.planes + sm->f_off;
-      return ugemm::run_h3(dh, a, hi, hi + (int64_t)M * sm->ldK, e, st) == hipSuccess ? 0 : ULTR_E_UNSUPPORTED;
+      const _Float16* hi = c.planes + sm->f_off;
+      return ugemm::run_h3(dh, a, hi, hi + (int64_t)M * sm->ldK, e, c.st) == hipSuccess ? 0 : ULTR_E_UNSUPPORTED;
     }
     const ugemm::Dims d{T, M, K, K};
-    return ugemm::run<true>(d, a, W, e, st) == hipSuccess ? 0 : ULTR_E_UNSUPPORTED;
+    return ugemm::run<true>(d, a, W, e, c.st) == hipSuccess ? 0 : ULTR_E_UNSUPPORTED;
   }
   if (M == 1 && !relu) {
-    hipLaunchKernelGGL(sr_rowdot_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, X, W, bias, Y, T, K);
+    hipLaunchKernelGGL(sr_rowdot_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, c.st, X, W, bias, Y, T, K);
     return 0;
   }
-  hipLaunchKernelGGL(sr_gemm_xwT_ref_kernel, dim3((unsigned)((T * M + 255) / 256)), dim3(256), 0, st, X, W, bias, Y, T, K, M, relu);
+  hipLaunchKernelGGL(sr_gemm_xwT_ref_kernel, dim3((unsigned)((T * M + 255) / 256)), dim3(256), 0, c.st, X, W, bias, Y, T, K, M, relu);
   return 0;
 }
 // S[T, M] = (X[T, K] . W[M, K]^T + bias) + res: a Linear onto the residual stream, fused (the tiled GEMM only); false = the
 // shape does not take it and the caller runs the Linear and the residual pass separately
-bool gemm_xwT_res(const float* X, const float* W, const float* bias, const float* res, float* S, int64_t T, int K, int M, hipStream_t st) {
-  if (!(M >= 16 && M % 4 == 0 && vec_ok(X, W, S, K, M) && (((uintptr_t)res) & 15) == 0 && T * (K > M ? K : M) * 4 < ((int64_t)1 << 31)))
+bool gemm_xwT_res(const SrCall& c, const float* X, int64_t w, const float* bias, const float* res, float* S, int K, int M) {
+  const int64_t T = c.p.T;
+  const float* W = c.params + w;
+  if (!(M >= 16 && M % 4 == 0 && vec_ok(X, S, K, M) && (((uintptr_t)res) & 15) == 0 && T * (K > M ? K : M) * 4 < ((int64_t)1 << 31)))
     return false;
   const ugemm::APlain a{X, T, K, K};
   const ugemm::EBiasRes e{S, bias, res, M};
-  if (const SrPlan::SplitMat* sm = sr_find_split(W, M, K)) {
+  if (const SrPlan::SplitMat* sm = c.split(w, M, K)) {
     const ugemm::Dims dh{T, M, K, sm->ldK};
-    const _Float16* hi = g_sr_h3.planes + sm->f_off;
-    return ugemm::run_h3(dh, a, hi, hi + (int64_t)M * sm->ldK, e, st) == hipSuccess;
+    const _Float16* hi = c.planes + sm->f_off;
+    return ugemm::run_h3(dh, a, hi, hi + (int64_t)M * sm->ldK, e, c.st) == hipSuccess;
   }
   const ugemm::Dims d{T, M, K, K};
-  return ugemm::run<true>(d, a, W, e, st) == hipSuccess;
+  return ugemm::run<true>(d, a, W, e, c.st) == hipSuccess;
 }
 // row-major  dX[T, K] = (accumulate ? dX : 0) + dY[T, M] . W[M, K], then zeroed where mask <= 0 (mask may be NULL)
-int gemm_dyw(const float* dY, const float* W, float* dX, const float* mask, int64_t T, int K, int M, int accumulate, hipStream_t st) {
-  if (M % 4 == 0 && K >= 16 && vec_ok(dY, W, dX, K, K) && (mask == nullptr || ((uintptr_t)mask & 15) == 0) &&
+int gemm_dyw(const SrCall& c, const float* dY, int64_t w, float* dX, const float* mask, int K, int M, int accumulate) {
+  const int64_t T = c.p.T;
+  const float* W = c.params + w;
+  if (M % 4 == 0 && K >= 16 && vec_ok(dY, dX, K, K) && (mask == nullptr || ((uintptr_t)mask & 15) == 0) &&
       T * (K > M ? K : M) * 4 < ((int64_t)1 << 31)) {
     const ugemm::APlain a{dY, T, M, M};
     const ugemm::EStore e{dX, mask, K, accumulate};
-    if (const SrPlan::SplitMat* sm = K >= 16 ? sr_find_split(W, M, K) : nullptr) {  // the planes of W^T: [K][ldM], contraction over M
+    if (const SrPlan::SplitMat* sm = K >= 16 ? c.split(w, M, K) : nullptr) {  // the planes of W^T: [K][ldM], contraction over M
       const ugemm::Dims dh{T, K, M, sm->ldM};
-      const _Float16* hi = g_sr_h3.planes + sm->t_off;
-      return ugemm::run_h3(dh, a, hi, hi + (int64_t)K * sm->ldM, e, st) == hipSuccess ? 0 : ULTR_E_UNSUPPORTED;
+      const _Float16* hi = c.planes + sm->t_off;
+      return ugemm::run_h3(dh, a, hi, hi + (int64_t)K * sm->ldM, e, c.st) == hipSuccess ? 0 : ULTR_E_UNSUPPORTED;
     }
     const ugemm::Dims d{T, K, M, K};
-    return ugemm::run<false>(d, a, W, e, st) == hipSuccess ? 0 : ULTR_E_UNSUPPORTED;
+    return ugemm::run<false>(d, a, W, e, c.st) == hipSuccess ? 0 : ULTR_E_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(sr_gemm_dyw_ref_kernel, dim3((unsigned)((T * K + 255) / 256)), dim3(256), 0, st, dY, W, dX, mask, T, K, M, accumulate);
+  hipLaunchKernelGGL(sr_gemm_dyw_ref_kernel, dim3((unsigned)((T * K + 255) / 256)), dim3(256), 0, c.st, dY, W, dX, mask, T, K, M, accumulate);
   return 0;
 }
 // row-major  dW[M, K] = dY[T, M]^T . X[T, K] for the shapes sr_wgrad_kernel does not take: `wg_split` equal row chunks
 // into partials, folded in canonical order
-int gemm_dyTx(const SrPlan& p, const float* dY, const float* X, float* dW, int64_t T, int K, int M, float* ws, hipStream_t st) {
+int gemm_dyTx(const SrCall& c, const float* dY, const float* X, float* dW, int K, int M) {
+  const SrPlan& p = c.p;
   if (M == 1 && K <= 3 * p.maxw) {  // the scorer's weight row: weighted column sums, partials per SR_CS_ROWS rows
-    float* cpart = part_scratch(ws + p.ws_part, (int64_t)p.n_cs * K);
-    hipLaunchKernelGGL(sr_colsum_w_kernel, dim3(p.n_cs), dim3(256), 0, st, dY, X, T, K, cpart);
-    fold(cpart, (int64_t)K, p.n_cs, K, dW, st);
+    float* cpart = c.folds->scratch(c.ws + p.ws_part, (int64_t)p.n_cs * K);
+    hipLaunchKernelGGL(sr_colsum_w_kernel, dim3(p.n_cs), dim3(256), 0, c.st, dY, X, p.T, K, cpart);
+    c.folds->add(cpart, (int64_t)K, p.n_cs, K, dW, c.st);
     return 0;
   }
   const int S = p.wg_split;
-  const int64_t rows = T / S;
+  const int64_t rows = p.T / S;
   const int len = M * K;
-  float* part = part_scratch(ws + p.ws_wg, (int64_t)S * len);
-  hipLaunchKernelGGL(sr_gemm_dyTx_ref_kernel, dim3((len + 255) / 256, S), dim3(256), 0, st, dY, X, part, rows, K, M);
-  fold(part, (int64_t)len, S, len, dW, st);
+  float* part = c.folds->scratch(c.ws + p.ws_wg, (int64_t)S * len);
+  hipLaunchKernelGGL(sr_gemm_dyTx_ref_kernel, dim3((len + 255) / 256, S), dim3(256), 0, c.st, dY, X, part, rows, K, M);
+  c.folds->add(part, (int64_t)len, S, len, dW, c.st);
   return 0;
+}
+
+// dst[0..W) = column sums of a (mode 0) or of a o xhat (mode 1)
+void colsum(const SrCall& c, const float* a, const float* s, const float* mean, const float* rstd, int W, int mode, float* dst) {
+  float* part = c.folds->scratch(c.ws + c.p.ws_part, (int64_t)c.p.n_cs * W);
+  hipLaunchKernelGGL(sr_colsum_kernel, dim3(c.p.n_cs), dim3(256), 0, c.st, a, s, mean, rstd, c.p.T, W, mode, part);
+  c.folds->add(part, (int64_t)W, c.p.n_cs, W, dst, c.st);
 }
 
 // dW = dY^T X and (db != NULL) db = column sums of dY.  Aligned shapes go through sr_wgrad_kernel; the rest through
 // the plain chunked kernel + the column-sum kernels.
-void colsum(const SrPlan& p, const float* a, const float* s, const float* mean, const float* rstd, int W, int mode, float* ws,
-            float* dst, hipStream_t st);
-int wgrad(const SrPlan& p, const float* dY, const float* X, float* dW, float* db, int64_t T, int K, int M, float* ws, hipStream_t st) {
+int wgrad(const SrCall& c, const float* dY, const float* X, float* dW, float* db, int K, int M) {
+  const SrPlan& p = c.p;
+  const int64_t T = p.T;
+  hipStream_t st = c.st;
+  FoldQueue& q = *c.folds;
   const bool ok = M % 4 == 0 && K % 4 == 0 && (((uintptr_t)dY | (uintptr_t)X) & 15) == 0;
   if (!ok) {
-    const int rc = gemm_dyTx(p, dY, X, dW, T, K, M, ws, st);
-    if (rc != 0) return rc;
-    if (db != nullptr) colsum(p, dY, nullptr, nullptr, nullptr, M, 0, ws, db, st);
+    SR_CHECK(gemm_dyTx(c, dY, X, dW, K, M));
+    if (db != nullptr) colsum(c, dY, nullptr, nullptr, nullptr, M, 0, db);
     return 0;
   }
   {
     // square-ish products (d x d: 66 % matrix-core occupancy on the fp32 instruction) take the DNN's split-half weight-gradient
     // kernel: same slab layout, so the fold below is the same.  The thin ones (dff = 64 wide) run at their HBM floor already.
     int S2 = 0, rps2 = 0;
-    if (sr_h3_enabled() && !p.no_h3 && g_sr_knob_wg_h3 != 0 && M >= 128 && K >= 128 && ultr_wgrad_h3_geometry(T, M, K, &S2, &rps2) &&
+    if (c.planes != nullptr && c.knobs.wg_h3 != 0 && M >= 128 && K >= 128 && ultr_wgrad_h3_geometry(T, M, K, &S2, &rps2) &&
         (int64_t)S2 * ((int64_t)M * K + M) <= p.wg_floats) {
-      float* part2 = part_scratch(ws + p.ws_wg, (int64_t)S2 * ((int64_t)M * K + M));
+      float* part2 = q.scratch(c.ws + p.ws_wg, (int64_t)S2 * ((int64_t)M * K + M));
       const int rc = ultr_wgrad_h3_plain(dY, X, T, M, K, part2, st);
       if (rc == 0) {
         const int64_t stride2 = (int64_t)M * K + M;
         const int len2 = M * K;
         if (db == dW + len2) {
-          fold(part2, stride2, S2, len2 + M, dW, st);
+          q.add(part2, stride2, S2, len2 + M, dW, st);
         } else {
-          fold(part2, stride2, S2, len2, dW, st);
-          if (db != nullptr) fold(part2 + len2, stride2, S2, M, db, st);
+          q.add(part2, stride2, S2, len2, dW, st);
+          if (db != nullptr) q.add(part2 + len2, stride2, S2, M, db, st);
         }
         return 0;
       }
@@ -1210,7 +1245,7 @@ int wgrad(const SrPlan& p, const float* dY, const float* X, float* dW, float* db
   const int S = wgrad_chunks(T, M, K, &rps);
   if ((int64_t)rps * (M > K ? M : K) * 4 >= ((int64_t)1 << 31)) return ULTR_E_UNSUPPORTED;
   const int nmb = (M + 63) / 64, nkb = (K + 63) / 64;
-  float* part = part_scratch(ws + p.ws_wg, (int64_t)S * ((int64_t)M * K + M));
+  float* part = q.scratch(c.ws + p.ws_wg, (int64_t)S * ((int64_t)M * K + M));
   const size_t lds = (size_t)(4 * 64 * 64 + 4 * 64) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
@@ -1223,10 +1258,10 @@ int wgrad(const SrPlan& p, const float* dY, const float* X, float* dW, float* db
   const int64_t stride = (int64_t)M * K + M;
   const int len = M * K;
   if (db == dW + len) {  // weight and bias are neighbours in the flat parameter vector, as in the slab: one fold
-    fold(part, stride, S, len + M, dW, st);
+    q.add(part, stride, S, len + M, dW, st);
   } else {
-    fold(part, stride, S, len, dW, st);
-    if (db != nullptr) fold(part + len, stride, S, M, db, st);
+    q.add(part, stride, S, len, dW, st);
+    if (db != nullptr) q.add(part + len, stride, S, M, db, st);
   }
   return 0;
 }
@@ -1246,45 +1281,34 @@ void ln_residual_fwd(const float* a, const float* b, const float* bias, int64_t 
                        gamma, beta, sum_out, y, mean_out, rstd_out);
 }
 
-#define SR_CHECK(call)        \
-  do {                        \
-    const int rc_ = (call);   \
-    if (rc_ != 0) return rc_; \
-  } while (0)
-
-// dst[0..W) = column sums of a (mode 0) or of a o xhat (mode 1)
-void colsum(const SrPlan& p, const float* a, const float* s, const float* mean, const float* rstd, int W, int mode, float* ws,
-            float* dst, hipStream_t st) {
-  float* part = part_scratch(ws + p.ws_part, (int64_t)p.n_cs * W);
-  hipLaunchKernelGGL(sr_colsum_kernel, dim3(p.n_cs), dim3(256), 0, st, a, s, mean, rstd, p.T, W, mode, part);
-  fold(part, (int64_t)W, p.n_cs, W, dst, st);
-}
-
 // dst[0..W) = d gamma, dst[W..2W) = d beta (adjacent in the flat layout: <ln>.weight then <ln>.bias)
 // dx = LayerNorm backward of dy; dst_gb = dgamma | dbeta; dst_bias = column sums of dx (may be NULL).  W <= 1024.
-int ln_bwd_cs(const SrPlan& p, const float* dy, const float* s, const float* mean, const float* rstd, const float* gamma, int W,
-              float* dx, float* ws, float* dst_gb, float* dst_bias, hipStream_t st) {
-  float* part = part_scratch(ws + p.ws_part, (int64_t)p.n_lb * 3 * W);
+int ln_bwd_cs(const SrCall& c, const float* dy, const float* s, const float* mean, const float* rstd, const float* gamma, int W,
+              float* dx, float* dst_gb, float* dst_bias) {
+  const SrPlan& p = c.p;
+  hipStream_t st = c.st;
+  float* part = c.folds->scratch(c.ws + p.ws_part, (int64_t)p.n_lb * 3 * W);
   const size_t lds = (size_t)4 * 3 * W * sizeof(float);
   const bool v4 = (W == 256 || W == 512) && ((((uintptr_t)dy | (uintptr_t)s | (uintptr_t)dx) & 15) == 0);
   if (v4 && W == 256) hipLaunchKernelGGL(sr_ln_bwd_cs_v4_kernel<1>, dim3(p.n_lb), dim3(256), lds, st, dy, s, mean, rstd, gamma, p.T, dx, part);
   else if (v4) hipLaunchKernelGGL(sr_ln_bwd_cs_v4_kernel<2>, dim3(p.n_lb), dim3(256), lds, st, dy, s, mean, rstd, gamma, p.T, dx, part);
   else if (W <= 256) hipLaunchKernelGGL(sr_ln_bwd_cs_kernel<4>, dim3(p.n_lb), dim3(256), lds, st, dy, s, mean, rstd, gamma, p.T, W, dx, part);
   else hipLaunchKernelGGL(sr_ln_bwd_cs_kernel<16>, dim3(p.n_lb), dim3(256), lds, st, dy, s, mean, rstd, gamma, p.T, W, dx, part);
-  fold(part, (int64_t)3 * W, p.n_lb, 2 * W, dst_gb, st);
-  if (dst_bias != nullptr) fold(part + 2 * W, (int64_t)3 * W, p.n_lb, W, dst_bias, st);  // (NULL: a dropout site sits between ds and the bias)
+  c.folds->add(part, (int64_t)3 * W, p.n_lb, 2 * W, dst_gb, st);
+  if (dst_bias != nullptr) c.folds->add(part + 2 * W, (int64_t)3 * W, p.n_lb, W, dst_bias, st);  // (NULL: a dropout site sits between ds and the bias)
   return 0;
 }
-void colsum_ln(const SrPlan& p, const float* dy, const float* s, const float* mean, const float* rstd, int W, float* ws, float* dst,
-               hipStream_t st) {
-  float* part = part_scratch(ws + p.ws_part, (int64_t)p.n_lb * 2 * W);  // n_lb >= n_cs
+void colsum_ln(const SrCall& c, const float* dy, const float* s, const float* mean, const float* rstd, int W, float* dst) {
+  const SrPlan& p = c.p;
+  hipStream_t st = c.st;
+  float* part = c.folds->scratch(c.ws + p.ws_part, (int64_t)p.n_lb * 2 * W);  // n_lb >= n_cs
   if (W % 4 == 0 && W <= 1024 && ((((uintptr_t)dy | (uintptr_t)s) & 15) == 0)) {
     hipLaunchKernelGGL(sr_colsum_ln_v4_kernel, dim3(p.n_lb), dim3(256), (size_t)8 * W * sizeof(float), st, dy, s, mean, rstd, p.T, W, part);
-    fold(part, (int64_t)2 * W, p.n_lb, 2 * W, dst, st);
+    c.folds->add(part, (int64_t)2 * W, p.n_lb, 2 * W, dst, st);
     return;
   }
   hipLaunchKernelGGL(sr_colsum_ln_kernel, dim3(p.n_cs), dim3(256), 0, st, dy, s, mean, rstd, p.T, W, part);
-  fold(part, (int64_t)2 * W, p.n_cs, 2 * W, dst, st);
+  c.folds->add(part, (int64_t)2 * W, p.n_cs, 2 * W, dst, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1641,32 +1665,28 @@ __global__ __launch_bounds__(NW * 64) void sr_block_fwd_kernel(SrBlockArgs a, co
 
 // Will the backward of this step run the encoder blocks' row-local chain as the fused launches of ultr_sr_bwd.hip?  ONE predicate
 // for the forward (which then does not write out1: sr_bwd_proj_kernel recomputes it from s1) and for the backward (which then
-// refuses to fall back to the launches that read out1).  A function of the plan and the knobs only.
-bool sr_bwd_blocks_fused(const SrPlan& p) {
-  sr_knobs_load();
+// refuses to fall back to the launches that read out1).  A function of the plan and the knobs only: the geometry is asked for 256
+// compute units whatever the device has (c.cus), the same answer on both sides of a step.
+bool sr_bwd_blocks_fused(const SrCall& c) {
+  const SrPlan& p = c.p;
   int R = 0, nt = 0, nw = 0;
-  return p.bwd_fused && (g_sr_knob_bwd_fused & 1) && sr_h3_enabled() && !p.no_h3 && p.T * (int64_t)p.d * 4 < ((int64_t)1 << 31) &&
+  return p.bwd_fused && (c.knobs.bwd_fused & 1) && c.planes != nullptr && p.T * (int64_t)p.d * 4 < ((int64_t)1 << 31) &&
          sr_bwd_geometry(p.T, 256, &R, &nt, &nw);
 }
 // sr_block_fwd_kernel: legal for widths that are multiples of 32 (d <= 256, dff <= 128) with the split-half products on; rows per
 // workgroup = whole rounds of one workgroup per CU, as many as the LDS holds (<= 60 at d = 256)
-int g_sr_knob_block = -1;
-bool block_fwd(const SrPlan& p, int l, const float* params, float* sv, float* scores, hipStream_t st, int* rc) {
-  if (g_sr_knob_block < 0) {
-    const char* e = getenv("ULTR_SR_BLOCK");
-    g_sr_knob_block = (e && *e) ? atoi(e) : 3;  // 0: off; 1: one 16-wave workgroup per CU; 2: two 8-wave workgroups per CU; 3 (default): the persistent kernel of round 6 where its widths apply, 2 elsewhere
-  }
-  const int d = p.d, dff = p.dff;
-  if (!g_sr_knob_block || !sr_h3_enabled() || p.no_h3 || g_sr_h3.planes == nullptr || d % 32 != 0 || (dff != 32 && dff != 64 && dff != 128) || d > 256 || d < 32)
+bool block_fwd(const SrCall& c, int l, float* scores, int* rc) {
+  const SrPlan& p = c.p;
+  const int d = p.d, dff = p.dff, cus = c.cus;
+  if (!c.knobs.block || c.planes == nullptr || d % 32 != 0 || (dff != 32 && dff != 64 && dff != 128) || d > 256 || d < 32)
     return false;
-  const SrPlan::SplitMat* md = sr_find_split(params + p.lay[l].wd, d, d);
-  const SrPlan::SplitMat* m1 = sr_find_split(params + p.lay[l].wf1, dff, d);
-  const SrPlan::SplitMat* m2 = sr_find_split(params + p.lay[l].wf2, d, dff);
-  if (!md || !m1 || !m2 || md->g_off < 0 || m1->g_off < 0 || m2->g_off < 0 || (((uintptr_t)sv | (uintptr_t)g_sr_h3.planes) & 15) != 0) return false;
-  if (g_sr_knob_block >= 3 && d == SR_BWD_D && dff == SR_BWD_DFF && p.T * (int64_t)d * 4 < ((int64_t)1 << 31)) {
+  const SrPlan::SplitMat* md = c.split(p.lay[l].wd, d, d);
+  const SrPlan::SplitMat* m1 = c.split(p.lay[l].wf1, dff, d);
+  const SrPlan::SplitMat* m2 = c.split(p.lay[l].wf2, d, dff);
+  if (!md || !m1 || !m2 || md->g_off < 0 || m1->g_off < 0 || m2->g_off < 0 || (((uintptr_t)c.sv | (uintptr_t)c.planes) & 15) != 0) return false;
+  if (c.knobs.block >= 3 && d == SR_BWD_D && dff == SR_BWD_DFF && p.T * (int64_t)d * 4 < ((int64_t)1 << 31)) {
     // round 6: ONE persistent 8-wave workgroup per CU over 60-row tiles (sr_fwd_block_kernel, ultr_sr_fwd.hip)
-    int dev = 0, cus = 256, R = 0, nt = 0, nw = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    int R = 0, nt = 0, nw = 0;
     if (sr_bwd_geometry(p.T, cus, &R, &nt, &nw)) {
       const SrLayer& y = p.lay[l];
       SrFwdBlockArgs fa;
@@ -1676,26 +1696,24 @@ bool block_fwd(const SrPlan& p, int l, const float* params, float* sv, float* sc
       fa.gd = md->g_off; fa.gf1 = m1->g_off; fa.gf2 = m2->g_off;
       fa.A = p.sv_A[l]; fa.x = p.sv_x[l]; fa.s1 = p.sv_s1[l]; fa.m1 = p.sv_m1[l]; fa.r1 = p.sv_r1[l]; fa.out1 = p.sv_out1[l]; fa.f = p.sv_f[l];
       fa.s2 = p.sv_s2[l]; fa.m2 = p.sv_m2[l]; fa.r2 = p.sv_r2[l]; fa.xn = p.sv_x[l + 1];
-      fa.skip_out1 = sr_bwd_blocks_fused(p) ? 1 : 0;
+      fa.skip_out1 = sr_bwd_blocks_fused(c) ? 1 : 0;
       if (l == p.nl - 1 && p.bo2 == p.wo2 + dff) {
-        const SrPlan::SplitMat* mo = sr_find_split(params + p.wo1, dff, d);
+        const SrPlan::SplitMat* mo = c.split(p.wo1, dff, d);
         if (mo != nullptr && mo->g_off >= 0 && scores != nullptr) {
           fa.head = 1;
           fa.go1 = mo->g_off; fa.bo1 = p.bo1; fa.wo2 = p.wo2; fa.bo2 = p.bo2; fa.oh = p.sv_oh;
         }
       }
-      *rc = sr_fwd_block_launch(fa, nw, params, g_sr_h3.planes, sv, scores, st);
+      *rc = sr_fwd_block_launch(fa, nw, c.params, c.planes, c.sv, scores, c.st);
       if (fa.head && *rc == 0) *rc = -1;
       return true;
     }
   }
   const int64_t per_row = (int64_t)(2 * (d + 8) + (dff + 8)) * 4, fixed = (int64_t)(6 * d + 3 * dff + 4 + 128) * 4;
-  const bool two = g_sr_knob_block != 1;  // two 8-wave workgroups per CU (default) / 1: one 16-wave workgroup
+  const bool two = c.knobs.block != 1;  // two 8-wave workgroups per CU (default) / 1: one 16-wave workgroup
   int64_t rmax = ((two ? 80 : 160) * 1024 - fixed) / per_row - 1;
   if (rmax > (two ? 32 : 64)) rmax = two ? 32 : 64;
   if (rmax < 16) return false;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   const int64_t slots = (int64_t)cus * (two ? 2 : 1);
   const int64_t rounds = (p.T + slots * rmax - 1) / (slots * rmax);
   int64_t R = (p.T + slots * rounds - 1) / (slots * rounds);
@@ -1708,9 +1726,9 @@ bool block_fwd(const SrPlan& p, int l, const float* params, float* sv, float* sc
   a.gd = md->g_off; a.gf1 = m1->g_off; a.gf2 = m2->g_off;
   a.A = p.sv_A[l]; a.x = p.sv_x[l]; a.s1 = p.sv_s1[l]; a.m1 = p.sv_m1[l]; a.r1 = p.sv_r1[l]; a.out1 = p.sv_out1[l]; a.f = p.sv_f[l];
   a.s2 = p.sv_s2[l]; a.m2 = p.sv_m2[l]; a.r2 = p.sv_r2[l]; a.xn = p.sv_x[l + 1];
-  a.skip_out1 = sr_bwd_blocks_fused(p) ? 1 : 0;
+  a.skip_out1 = sr_bwd_blocks_fused(c) ? 1 : 0;
   if (l == p.nl - 1 && p.bo2 == p.wo2 + dff) {  // the output FFN rides along with the last block
-    const SrPlan::SplitMat* mo = sr_find_split(params + p.wo1, dff, d);
+    const SrPlan::SplitMat* mo = c.split(p.wo1, dff, d);
     if (mo != nullptr && mo->g_off >= 0 && scores != nullptr) {
       a.head = 1;
       a.go1 = mo->g_off; a.bo1 = p.bo1; a.wo2 = p.wo2; a.bo2 = p.bo2; a.oh = p.sv_oh;
@@ -1727,8 +1745,8 @@ bool block_fwd(const SrPlan& p, int l, const float* params, float* sv, float* sc
     *rc = ULTR_E_UNSUPPORTED;
     return true;
   }
-  if (two) hipLaunchKernelGGL(sr_block_fwd_kernel<8>, dim3((unsigned)((p.T + R - 1) / R)), dim3(512), lds, st, a, params, g_sr_h3.planes, sv, scores);
-  else hipLaunchKernelGGL(sr_block_fwd_kernel<16>, dim3((unsigned)((p.T + R - 1) / R)), dim3(1024), lds, st, a, params, g_sr_h3.planes, sv, scores);
+  if (two) hipLaunchKernelGGL(sr_block_fwd_kernel<8>, dim3((unsigned)((p.T + R - 1) / R)), dim3(512), lds, c.st, a, c.params, c.planes, c.sv, scores);
+  else hipLaunchKernelGGL(sr_block_fwd_kernel<16>, dim3((unsigned)((p.T + R - 1) / R)), dim3(1024), lds, c.st, a, c.params, c.planes, c.sv, scores);
   *rc = (int)hipGetLastError();
   if (a.head && *rc == 0) *rc = -1;  // (-1: launched, and the output FFN is done as well)
   return true;
@@ -1959,27 +1977,21 @@ __global__ __launch_bounds__(NW * 64) void sr_embed_fwd_kernel(SrEmbedArgs a, co
 }
 
 // legal: F a multiple of 4 and at most 256, widths as for sr_block_fwd_kernel; two 8-wave workgroups per CU
-bool embed_fwd(const SrPlan& p, const float* params, const float* feats, const int32_t* docids, int64_t n_docs, int batch, int L, float* sv,
-               hipStream_t st, int* rc) {
+bool embed_fwd(const SrCall& c, const float* feats, const int32_t* docids, int64_t n_docs, int batch, int L, int* rc) {
+  const SrPlan& p = c.p;
   const int F = p.F, d = p.d, dff = p.dff;
-  if (g_sr_knob_block < 0) {
-    const char* e = getenv("ULTR_SR_BLOCK");
-    g_sr_knob_block = (e && *e) ? atoi(e) : 3;
-  }
-  if (!g_sr_knob_block || !sr_h3_enabled() || p.no_h3 || g_sr_h3.planes == nullptr || F % 4 != 0 || F > 256 || d % 32 != 0 || d > 256 || d < 32 ||
+  if (!c.knobs.block || c.planes == nullptr || F % 4 != 0 || F > 256 || d % 32 != 0 || d > 256 || d < 32 ||
       (dff != 32 && dff != 64 && dff != 128) || n_docs * (int64_t)F * 4 >= ((int64_t)1 << 31))
     return false;
-  const SrPlan::SplitMat* m1 = sr_find_split(params + p.w1, dff, F);
-  const SrPlan::SplitMat* m2 = sr_find_split(params + p.w2, d, dff);
-  if (!m1 || !m2 || m1->g_off < 0 || m2->g_off < 0 || (((uintptr_t)sv | (uintptr_t)g_sr_h3.planes | (uintptr_t)feats) & 15) != 0) return false;
+  const SrPlan::SplitMat* m1 = c.split(p.w1, dff, F);
+  const SrPlan::SplitMat* m2 = c.split(p.w2, d, dff);
+  if (!m1 || !m2 || m1->g_off < 0 || m2->g_off < 0 || (((uintptr_t)c.sv | (uintptr_t)c.planes | (uintptr_t)feats) & 15) != 0) return false;
   const int K16 = (F + 31) / 32 * 32;
   const int64_t per_row = (int64_t)((K16 + 8) + (dff + 8)) * 4, fixed = (int64_t)(2 * F + dff + d + 128) * 4;
   int64_t rmax = (80 * 1024 - fixed) / per_row - 1;
   if (rmax > 32) rmax = 32;
   if (rmax < 16) return false;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const int64_t slots = (int64_t)cus * 2;
+  const int64_t slots = (int64_t)c.cus * 2;
   const int64_t rounds = (p.T + slots * rmax - 1) / (slots * rmax);
   int64_t R = (p.T + slots * rounds - 1) / (slots * rounds);
   if (R < 16) R = 16;
@@ -1998,17 +2010,14 @@ bool embed_fwd(const SrPlan& p, const float* params, const float* feats, const i
     *rc = ULTR_E_UNSUPPORTED;
     return true;
   }
-  hipLaunchKernelGGL(sr_embed_fwd_kernel<8>, dim3((unsigned)((p.T + R - 1) / R)), dim3(512), lds, st, a, params, feats, docids, g_sr_h3.planes, sv);
+  hipLaunchKernelGGL(sr_embed_fwd_kernel<8>, dim3((unsigned)((p.T + R - 1) / R)), dim3(512), lds, c.st, a, c.params, feats, docids, c.planes, c.sv);
   *rc = (int)hipGetLastError();
   return true;
 }
 
 }  // namespace
 
-void ultr_setrank_knobs_reload() {
-  g_sr_knob_h3 = -1;
-  g_sr_knob_block = -1;
-}
+void ultr_setrank_knobs_reload() { sr_knobs_load(); }
 
 extern "C" int64_t ultr_setrank_param_count(const ultr_setrank_desc* c) {
   SrPlan p;
@@ -2041,14 +2050,14 @@ int64_t sr_dropout_ws_floats(const SrPlan& p) {
   return ((p.T * p.d + 3) & ~(int64_t)3) + (int64_t)2 * p.nl * ((sr_drop_parts(p.T) * p.d + 3) & ~(int64_t)3);
 }
 
-int setrank_forward(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
+int setrank_forward(const ultr_setrank_desc* desc, const float* params, const float* features, int64_t n_docs,
                     const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
                     const ultr_setrank_dropout* dropout, void* stream) {
   if (!params || !docids || !scores || !saved || batch <= 0 || list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features))
     return ULTR_E_BADARG;
   const int64_t T = (int64_t)batch * list_size;
   SrPlan p;
-  if (!make_plan(c, T, &p)) return ULTR_E_BADARG;
+  if (!make_plan(desc, T, &p)) return ULTR_E_BADARG;
   const int L = list_size;
   SrDropArgs da;
   const int drop_rc = sr_dropout_plan(dropout, batch, list_size, &da);
@@ -2061,12 +2070,10 @@ int setrank_forward(const ultr_setrank_desc* c, const float* params, const float
   float* sv = (float*)saved;
   const unsigned rblk = (unsigned)((T + SR_ROWS - 1) / SR_ROWS);
   const int F = p.F, d = p.d, dff = p.dff;
+  SrCall c = {p, params, nullptr, sr_knobs(), sr_cu_count(), sv, nullptr, st, nullptr};
   // split-half planes of every weight matrix (the weights change with every update: rebuilt per forward, ~2 MB, one small launch)
-  struct H3Scope {
-    ~H3Scope() { g_sr_h3 = {nullptr, nullptr, nullptr}; }
-  } h3scope;
   SR_CHECK((int)hipMemsetAsync(sv + p.sv_flag, 0, sizeof(uint32_t), st));  // this step's range word
-  if (sr_h3_enabled() && !p.no_h3) {
+  if (c.knobs.h3 && !p.no_h3) {
     _Float16* planes = reinterpret_cast<_Float16*>(sv + p.sv_planes);
     SrSplitTable tb;
     tb.n = p.n_split;
@@ -2079,11 +2086,11 @@ int setrank_forward(const ultr_setrank_desc* c, const float* params, const float
     }
     hipLaunchKernelGGL(sr_split_planes_kernel, dim3((unsigned)((maxe + 255) / 256), (unsigned)(4 * p.n_split)), dim3(256), 0, st, tb, params, planes,
                        reinterpret_cast<uint32_t*>(sv + p.sv_flag));
-    g_sr_h3 = {params, planes, &p};
+    c.planes = planes;
   }
   // input LayerNorm on the gathered rows, then the embedding FFN (SetRank.py:134-135, 146)
   int erc = 0;
-  const bool embedded = !drop && n_docs > 0 && embed_fwd(p, params, features, docids, n_docs, (int)batch, L, sv, st, &erc);  // one launch (sr_embed_fwd_kernel)
+  const bool embedded = !drop && n_docs > 0 && embed_fwd(c, features, docids, n_docs, (int)batch, L, &erc);  // one launch (sr_embed_fwd_kernel)
   if (embedded && erc) return erc;
   if (embedded) {
   } else if (F % 4 == 0 && F <= 1024 && ((uintptr_t)features & 15) == 0)
@@ -2094,8 +2101,8 @@ int setrank_forward(const ultr_setrank_desc* c, const float* params, const float
                        (int)batch, L, T, F, params + p.g_in, params + p.b_in, sv + p.sv_xg, sv + p.sv_xn0, sv + p.sv_mean_in,
                        sv + p.sv_rstd_in);
   if (!embedded) {
-    SR_CHECK(gemm_xwT(sv + p.sv_xn0, params + p.w1, params + p.b1, sv + p.sv_h0, T, F, dff, 1, st));
-    SR_CHECK(gemm_xwT(sv + p.sv_h0, params + p.w2, params + p.b2, sv + p.sv_x[0], T, dff, d, 0, st));
+    SR_CHECK(gemm_xwT(c, sv + p.sv_xn0, p.w1, params + p.b1, sv + p.sv_h0, F, dff, 1));
+    SR_CHECK(gemm_xwT(c, sv + p.sv_h0, p.w2, params + p.b2, sv + p.sv_x[0], dff, d, 0));
   }
   if (drop) sr_drop_mask_launch(da, 0, sv + p.sv_x[0], sv + p.sv_x[0], nullptr, T, d, st);  // x0 = D(embedding): attention and the residual read it
   bool head_done = false;
@@ -2107,57 +2114,57 @@ int setrank_forward(const ultr_setrank_desc* c, const float* params, const float
     // the Linear's epilogue writes the pre-norm sum s1 = x + (A Wd^T + bd) straight into `saved` (one pass over [T, d] less on
     // each side of the LayerNorm); shapes the tiled GEMM does not take: Linear, then the residual pass
     if (drop) {  // o = D(dense(A)), f = D(ffn(out1)): the Linear without its bias, then dropout + residual + LayerNorm in one row pass
-      SR_CHECK(gemm_xwT(sv + p.sv_A[l], params + y.wd, nullptr, sv + p.sv_out1[l], T, d, d, 0, st));
+      SR_CHECK(gemm_xwT(c, sv + p.sv_A[l], y.wd, nullptr, sv + p.sv_out1[l], d, d, 0));
       sr_drop_ln_fwd_launch(da, 1 + 2 * l, x, sv + p.sv_out1[l], params + y.bd, T, d, params + y.g1, params + y.b1, sv + p.sv_s1[l],
                             sv + p.sv_out1[l], sv + p.sv_m1[l], sv + p.sv_r1[l], st);
-      SR_CHECK(gemm_xwT(sv + p.sv_out1[l], params + y.wf1, params + y.bf1, sv + p.sv_f[l], T, d, dff, 1, st));
-      SR_CHECK(gemm_xwT(sv + p.sv_f[l], params + y.wf2, nullptr, sv + p.sv_x[l + 1], T, dff, d, 0, st));
+      SR_CHECK(gemm_xwT(c, sv + p.sv_out1[l], y.wf1, params + y.bf1, sv + p.sv_f[l], d, dff, 1));
+      SR_CHECK(gemm_xwT(c, sv + p.sv_f[l], y.wf2, nullptr, sv + p.sv_x[l + 1], dff, d, 0));
       sr_drop_ln_fwd_launch(da, 2 + 2 * l, sv + p.sv_out1[l], sv + p.sv_x[l + 1], params + y.bf2, T, d, params + y.g2, params + y.b2,
                             sv + p.sv_s2[l], sv + p.sv_x[l + 1], sv + p.sv_m2[l], sv + p.sv_r2[l], st);
       continue;
     }
     {
       int brc = 0;
-      if (block_fwd(p, l, params, sv, scores, st, &brc)) {  // everything behind the attention in one launch (sr_block_fwd_kernel)
+      if (block_fwd(c, l, scores, &brc)) {  // everything behind the attention in one launch (sr_block_fwd_kernel)
         if (brc > 0 || brc < -1) return brc;
         head_done = brc == -1;
         continue;
       }
     }
     const bool ln_v4 = (d == 256 || d == 512 || d == 768 || d == 1024);
-    if (ln_v4 && gemm_xwT_res(sv + p.sv_A[l], params + y.wd, params + y.bd, x, sv + p.sv_s1[l], T, d, d, st)) {
+    if (ln_v4 && gemm_xwT_res(c, sv + p.sv_A[l], y.wd, params + y.bd, x, sv + p.sv_s1[l], d, d)) {
       ln_residual_fwd(sv + p.sv_s1[l], nullptr, nullptr, T, d, params + y.g1, params + y.b1, nullptr, sv + p.sv_out1[l],
                       sv + p.sv_m1[l], sv + p.sv_r1[l], (int)batch, L, st);
     } else {
-      SR_CHECK(gemm_xwT(sv + p.sv_A[l], params + y.wd, nullptr, sv + p.sv_out1[l], T, d, d, 0, st));
+      SR_CHECK(gemm_xwT(c, sv + p.sv_A[l], y.wd, nullptr, sv + p.sv_out1[l], d, d, 0));
       ln_residual_fwd(x, sv + p.sv_out1[l], params + y.bd, T, d, params + y.g1, params + y.b1, sv + p.sv_s1[l], sv + p.sv_out1[l],
                       sv + p.sv_m1[l], sv + p.sv_r1[l], (int)batch, L, st);
     }
-    SR_CHECK(gemm_xwT(sv + p.sv_out1[l], params + y.wf1, params + y.bf1, sv + p.sv_f[l], T, d, dff, 1, st));
-    if (ln_v4 && gemm_xwT_res(sv + p.sv_f[l], params + y.wf2, params + y.bf2, sv + p.sv_out1[l], sv + p.sv_s2[l], T, dff, d, st)) {
+    SR_CHECK(gemm_xwT(c, sv + p.sv_out1[l], y.wf1, params + y.bf1, sv + p.sv_f[l], d, dff, 1));
+    if (ln_v4 && gemm_xwT_res(c, sv + p.sv_f[l], y.wf2, params + y.bf2, sv + p.sv_out1[l], sv + p.sv_s2[l], dff, d)) {
       ln_residual_fwd(sv + p.sv_s2[l], nullptr, nullptr, T, d, params + y.g2, params + y.b2, nullptr, sv + p.sv_x[l + 1],
                       sv + p.sv_m2[l], sv + p.sv_r2[l], (int)batch, L, st);
     } else {
-      SR_CHECK(gemm_xwT(sv + p.sv_f[l], params + y.wf2, nullptr, sv + p.sv_x[l + 1], T, dff, d, 0, st));
+      SR_CHECK(gemm_xwT(c, sv + p.sv_f[l], y.wf2, nullptr, sv + p.sv_x[l + 1], dff, d, 0));
       ln_residual_fwd(sv + p.sv_out1[l], sv + p.sv_x[l + 1], params + y.bf2, T, d, params + y.g2, params + y.b2, sv + p.sv_s2[l],
                       sv + p.sv_x[l + 1], sv + p.sv_m2[l], sv + p.sv_r2[l], (int)batch, L, st);
     }
   }
   // output FFN (SetRank.py:136, 153)
   if (!head_done) {
-    SR_CHECK(gemm_xwT(sv + p.sv_x[p.nl], params + p.wo1, params + p.bo1, sv + p.sv_oh, T, d, dff, 1, st));
-    SR_CHECK(gemm_xwT(sv + p.sv_oh, params + p.wo2, params + p.bo2, scores, T, dff, 1, 0, st));
+    SR_CHECK(gemm_xwT(c, sv + p.sv_x[p.nl], p.wo1, params + p.bo1, sv + p.sv_oh, d, dff, 1));
+    SR_CHECK(gemm_xwT(c, sv + p.sv_oh, p.wo2, params + p.bo2, scores, dff, 1, 0));
   }
   return (int)hipGetLastError();
 }
 
-int setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t batch, int32_t list_size,
+int setrank_backward(const ultr_setrank_desc* desc, const float* params, int32_t batch, int32_t list_size,
                      const void* saved, const float* dscores, const void* loss_ws, int32_t n_loss_parts, void* ws_,
                      float* grads, const ultr_setrank_dropout* dropout, void* stream) {
   if (!params || !saved || !dscores || !ws_ || !grads || batch <= 0 || list_size <= 0) return ULTR_E_BADARG;
   const int64_t T = (int64_t)batch * list_size;
   SrPlan p;
-  if (!make_plan(c, T, &p)) return ULTR_E_BADARG;
+  if (!make_plan(desc, T, &p)) return ULTR_E_BADARG;
   const int L = list_size;
   SrDropArgs da;
   const int drop_rc = sr_dropout_plan(dropout, batch, list_size, &da);
@@ -2176,9 +2183,6 @@ int setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t ba
   }
   const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16};
   SR_CHECK(sr_attn_supported(ash, L, 1));
-  sr_knobs_load();
-  // ULTR_SR_ATTN_H3 and its mask (bit 2 layer + 1: this layer's backward) allow the split-half attention backward kernel
-  auto attn_split_half = [&](int layer) { return g_sr_knob_attn_h3 >= 1 && ((g_sr_knob_attn_mask >> (2 * layer + 1)) & 1) != 0; };
   hipStream_t st = (hipStream_t)stream;
   const float* sv = (const float*)saved;
   float* ws = (float*)ws_;
@@ -2187,65 +2191,61 @@ int setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t ba
   float* G2 = ws + p.ws_g[2];
   const unsigned rblk = (unsigned)((T + SR_ROWS - 1) / SR_ROWS);
   const int F = p.F, d = p.d, dff = p.dff;
-  struct H3Scope {
-    ~H3Scope() { g_sr_h3 = {nullptr, nullptr, nullptr}; }
-  } h3scope;
-  if (sr_h3_enabled() && !p.no_h3) g_sr_h3 = {params, reinterpret_cast<const _Float16*>(sv + p.sv_planes), &p};  // built by this step's forward
+  FoldQueue folds(ws + p.ws_arena, p.arena_floats);  // every fold below is queued; ONE launch at the end
+  SrCall c = {p, params, nullptr, sr_knobs(), sr_cu_count(), const_cast<float*>(sv), ws, st, &folds};
+  if (c.knobs.h3 && !p.no_h3) c.planes = reinterpret_cast<const _Float16*>(sv + p.sv_planes);  // built by this step's forward
+  // ULTR_SR_ATTN_H3 and its mask (bit 2 layer + 1: this layer's backward) allow the split-half attention backward kernel
+  auto attn_split_half = [&](int layer) { return c.knobs.attn_h3 >= 1 && ((c.knobs.attn_mask >> (2 * layer + 1)) & 1) != 0; };
   // ---- output FFN:  s = oh wo2^T + bo2,  oh = relu(x_nl Wo1^T + bo1) ----------------------------------------------
-  FoldScope folds(ws + p.ws_arena, p.arena_floats);  // every fold below is queued; ONE launch at the end
   // the fused launches of ultr_sr_bwd.hip: config 5's widths, split-half products on, the transposed fragment copies built by this
   // step's forward
   int fz_R = 0, fz_tiles = 0, fz_nwg = 0;
-  bool fused = !drop && p.bwd_fused && g_sr_knob_bwd_fused != 0 && g_sr_h3.planes != nullptr && T * (int64_t)d * 4 < ((int64_t)1 << 31);
-  if (fused) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    fused = sr_bwd_geometry(T, cus, &fz_R, &fz_tiles, &fz_nwg);
-  }
+  const bool fused = !drop && p.bwd_fused && c.knobs.bwd_fused != 0 && c.planes != nullptr && T * (int64_t)d * 4 < ((int64_t)1 << 31) &&
+                     sr_bwd_geometry(T, c.cus, &fz_R, &fz_tiles, &fz_nwg);
   bool head_done = false;
-  if (fused && (g_sr_knob_bwd_fused & 2) && p.bo1 == p.wo1 + (int64_t)dff * d && p.wo2 == p.bo1 + dff && p.bo2 == p.wo2 + dff) {
-    const SrPlan::SplitMat* mo = sr_find_split(params + p.wo1, dff, d);
+  if (fused && (c.knobs.bwd_fused & 2) && p.bo1 == p.wo1 + (int64_t)dff * d && p.wo2 == p.bo1 + dff && p.bo2 == p.wo2 + dff) {
+    const SrPlan::SplitMat* mo = c.split(p.wo1, dff, d);
     const int64_t sh = ((int64_t)dff * d + 2 * dff + 2 + 3) & ~(int64_t)3;  // (whole float4s: sr_fold_all_kernel's vector form)
     float* ph = nullptr;
-    if (mo && mo->gt_off >= 0 && (ph = arena_piece(fz_nwg * sh)) != nullptr) {
+    if (mo && mo->gt_off >= 0 && (ph = folds.piece(fz_nwg * sh)) != nullptr) {
       SrBwdHeadArgs ha;
       memset(&ha, 0, sizeof(ha));
       ha.R = fz_R; ha.d = d; ha.dff = dff; ha.ntiles = fz_tiles; ha.T = T;
       ha.dx = p.ws_g[0]; ha.x = p.sv_x[p.nl]; ha.oh = p.sv_oh; ha.wo2 = p.wo2; ha.gto1 = mo->gt_off;
       ha.part = ph - ws; ha.part_stride = sh;
-      SR_CHECK(sr_bwd_head_launch(ha, fz_nwg, params, g_sr_h3.planes, sv, dscores, ws, st));  // G0 = d x_nl
-      fold(ph, sh, fz_nwg, dff * d + 2 * dff + 1, grads + p.wo1, st);                         // d Wo1 | d bo1 | d wo2 | d bo2
+      SR_CHECK(sr_bwd_head_launch(ha, fz_nwg, params, c.planes, sv, dscores, ws, st));  // G0 = d x_nl
+      folds.add(ph, sh, fz_nwg, dff * d + 2 * dff + 1, grads + p.wo1, st);              // d Wo1 | d bo1 | d wo2 | d bo2
       head_done = true;
     }
   }
   if (head_done) {
   } else
   if (dff <= 256 && p.bo2 == p.wo2 + dff) {  // one pass: G1 = d oh [T, dff] (ReLU mask fused), d wo2 | d bo2 partials
-    float* hpart = part_scratch(ws + p.ws_part, (int64_t)p.n_cs * (dff + 1));
+    float* hpart = folds.scratch(ws + p.ws_part, (int64_t)p.n_cs * (dff + 1));
     hipLaunchKernelGGL(sr_head_bwd_kernel, dim3(p.n_cs), dim3(256), 0, st, dscores, (const float*)(sv + p.sv_oh), params + p.wo2, T, (int)dff,
                        G1, hpart);
-    fold(hpart, (int64_t)dff + 1, p.n_cs, (int)dff + 1, grads + p.wo2, st);
+    folds.add(hpart, (int64_t)dff + 1, p.n_cs, (int)dff + 1, grads + p.wo2, st);
   } else {
-    SR_CHECK(gemm_dyTx(p, dscores, sv + p.sv_oh, grads + p.wo2, T, dff, 1, ws, st));
-    colsum(p, dscores, nullptr, nullptr, nullptr, 1, 0, ws, grads + p.bo2, st);
-    SR_CHECK(gemm_dyw(dscores, params + p.wo2, G1, sv + p.sv_oh, T, dff, 1, 0, st));  // G1 = d oh  [T, dff], ReLU mask fused
+    SR_CHECK(gemm_dyTx(c, dscores, sv + p.sv_oh, grads + p.wo2, dff, 1));
+    colsum(c, dscores, nullptr, nullptr, nullptr, 1, 0, grads + p.bo2);
+    SR_CHECK(gemm_dyw(c, dscores, p.wo2, G1, sv + p.sv_oh, dff, 1, 0));  // G1 = d oh  [T, dff], ReLU mask fused
   }
   if (!head_done) {
-    SR_CHECK(wgrad(p, G1, sv + p.sv_x[p.nl], grads + p.wo1, grads + p.bo1, T, d, dff, ws, st));
-    SR_CHECK(gemm_dyw(G1, params + p.wo1, G0, nullptr, T, d, dff, 0, st));     // G0 = d x_nl  [T, d]
+    SR_CHECK(wgrad(c, G1, sv + p.sv_x[p.nl], grads + p.wo1, grads + p.bo1, d, dff));
+    SR_CHECK(gemm_dyw(c, G1, p.wo1, G0, nullptr, d, dff, 0));     // G0 = d x_nl  [T, d]
   }
   for (int l = p.nl - 1; l >= 0; --l) {
     const SrLayer& y = p.lay[l];
-    if (fused && (g_sr_knob_bwd_fused & 1)) {
-      const SrPlan::SplitMat* md = sr_find_split(params + y.wd, d, d);
-      const SrPlan::SplitMat* m1 = sr_find_split(params + y.wf1, dff, d);
-      const SrPlan::SplitMat* m2 = sr_find_split(params + y.wf2, d, dff);
+    if (fused && (c.knobs.bwd_fused & 1)) {
+      const SrPlan::SplitMat* md = c.split(y.wd, d, d);
+      const SrPlan::SplitMat* m1 = c.split(y.wf1, dff, d);
+      const SrPlan::SplitMat* m2 = c.split(y.wf2, d, dff);
       const int64_t sa = (int64_t)d * dff + 3 * d, sb = (int64_t)dff * d + dff + 3 * d;
       float* pa = nullptr;
       float* pb = nullptr;
       if (md && m1 && m2 && md->gt_off >= 0 && m1->gt_off >= 0 && m2->gt_off >= 0 && y.bf2 == y.wf2 + (int64_t)d * dff && y.b2 == y.g2 + d &&
-          y.bf1 == y.wf1 + (int64_t)dff * d && y.b1 == y.g1 + d && (pa = arena_piece(fz_nwg * sa)) != nullptr &&
-          (pb = arena_piece(fz_nwg * sb)) != nullptr) {
+          y.bf1 == y.wf1 + (int64_t)dff * d && y.b1 == y.g1 + d && (pa = folds.piece(fz_nwg * sa)) != nullptr &&
+          (pb = folds.piece(fz_nwg * sb)) != nullptr) {
         SrBwdFfnArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.R = fz_R; fa.d = d; fa.dff = dff; fa.ntiles = fz_tiles; fa.T = T;
@@ -2253,9 +2253,9 @@ int setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t ba
         fa.s = p.sv_s2[l]; fa.mean = p.sv_m2[l]; fa.rstd = p.sv_r2[l]; fa.f = p.sv_f[l];
         fa.gamma = y.g2; fa.gt2 = m2->gt_off; fa.gt1 = m1->gt_off;
         fa.part = pa - ws; fa.part_stride = sa;
-        SR_CHECK(sr_bwd_ffn_launch(fa, fz_nwg, params, g_sr_h3.planes, sv, ws, st));  // G1 = d f, G2 = d out1
-        fold(pa, sa, fz_nwg, d * dff + d, grads + y.wf2, st);            // d Wf2 | d bf2
-        fold(pa + (int64_t)d * dff + d, sa, fz_nwg, 2 * d, grads + y.g2, st);  // d g2 | d b2
+        SR_CHECK(sr_bwd_ffn_launch(fa, fz_nwg, params, c.planes, sv, ws, st));  // G1 = d f, G2 = d out1
+        folds.add(pa, sa, fz_nwg, d * dff + d, grads + y.wf2, st);                 // d Wf2 | d bf2
+        folds.add(pa + (int64_t)d * dff + d, sa, fz_nwg, 2 * d, grads + y.g2, st);  // d g2 | d b2
         SrBwdProjArgs pr;
         memset(&pr, 0, sizeof(pr));
         pr.R = fz_R; pr.d = d; pr.dff = dff; pr.ntiles = fz_tiles; pr.T = T;
@@ -2263,11 +2263,11 @@ int setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t ba
         pr.s = p.sv_s1[l]; pr.mean = p.sv_m1[l]; pr.rstd = p.sv_r1[l];
         pr.gamma = y.g1; pr.beta = y.b1; pr.gtd = md->gt_off;
         pr.part = pb - ws; pr.part_stride = sb;
-        SR_CHECK(sr_bwd_proj_launch(pr, fz_nwg, params, g_sr_h3.planes, sv, ws, st));  // G0 = d s1 (= d x_l through the residual), G2 = d A
-        fold(pb, sb, fz_nwg, dff * d + dff, grads + y.wf1, st);                           // d Wf1 | d bf1
-        fold(pb + (int64_t)dff * d + dff, sb, fz_nwg, d, grads + y.bd, st);               // d bd
-        fold(pb + (int64_t)dff * d + dff + d, sb, fz_nwg, 2 * d, grads + y.g1, st);       // d g1 | d b1
-        SR_CHECK(wgrad(p, G0, sv + p.sv_A[l], grads + y.wd, nullptr, T, d, d, ws, st));
+        SR_CHECK(sr_bwd_proj_launch(pr, fz_nwg, params, c.planes, sv, ws, st));  // G0 = d s1 (= d x_l through the residual), G2 = d A
+        folds.add(pb, sb, fz_nwg, dff * d + dff, grads + y.wf1, st);                      // d Wf1 | d bf1
+        folds.add(pb + (int64_t)dff * d + dff, sb, fz_nwg, d, grads + y.bd, st);          // d bd
+        folds.add(pb + (int64_t)dff * d + dff + d, sb, fz_nwg, 2 * d, grads + y.g1, st);  // d g1 | d b1
+        SR_CHECK(wgrad(c, G0, sv + p.sv_A[l], grads + y.wd, nullptr, d, d));
         // G0 += attention path -> d x_l
         SR_CHECK(sr_attn_backward(ash, attn_split_half(l), sv + p.sv_x[l], G2, sv + p.sv_A[l], sv + p.sv_lse[l], batch, L, G0, st));
         continue;
@@ -2275,79 +2275,79 @@ int setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t ba
     }
     // (the forward did not write out1 when it expected the fused launches: sr_block_fwd_kernel's skip_out1 - same predicate)
     // (a dropout step's forward ran the separate launches and wrote out1)
-    if (!drop && sr_bwd_blocks_fused(p) && g_sr_knob_block != 0) return ULTR_E_UNSUPPORTED;
+    if (!drop && sr_bwd_blocks_fused(c) && c.knobs.block != 0) return ULTR_E_UNSUPPORTED;
     // a dropout site: the branch gradient d(b + bias) = keep * scale * ds goes to DM with its column sums (the bias gradient); the
     // residual keeps the unmasked ds
     auto masked_branch = [&](int site, const float* ds, float* dst_bias) {
       float* part = dpart + (int64_t)(site - 1) * dpart_floats;
       sr_drop_mask_launch(da, site, ds, DM, part, T, d, st);
-      fold(part, (int64_t)d, (int)sr_drop_parts(T), d, dst_bias, st, /*own_buffer=*/true);
+      folds.add(part, (int64_t)d, (int)sr_drop_parts(T), d, dst_bias, st, /*own_buffer=*/true);
     };
     // x_{l+1} = LN2(s2),  s2 = out1 + ffn
     if (d <= 1024) {  // g2 | b2, G2 = d s2 = d out1 (residual) = d ffn, bf2: one pass
-      SR_CHECK(ln_bwd_cs(p, G0, sv + p.sv_s2[l], sv + p.sv_m2[l], sv + p.sv_r2[l], params + y.g2, d, G2, ws, grads + y.g2,
-                         drop ? nullptr : grads + y.bf2, st));
+      SR_CHECK(ln_bwd_cs(c, G0, sv + p.sv_s2[l], sv + p.sv_m2[l], sv + p.sv_r2[l], params + y.g2, d, G2, grads + y.g2,
+                         drop ? nullptr : grads + y.bf2));
     } else {
-      colsum_ln(p, G0, sv + p.sv_s2[l], sv + p.sv_m2[l], sv + p.sv_r2[l], d, ws, grads + y.g2, st);
+      colsum_ln(c, G0, sv + p.sv_s2[l], sv + p.sv_m2[l], sv + p.sv_r2[l], d, grads + y.g2);
       hipLaunchKernelGGL(sr_ln_bwd_kernel, dim3(rblk), dim3(SR_ROWS * 64), 0, st, (const float*)G0, sv + p.sv_s2[l], sv + p.sv_m2[l],
                          sv + p.sv_r2[l], params + y.g2, T, d, G2);
-      if (!drop) colsum(p, G2, nullptr, nullptr, nullptr, d, 0, ws, grads + y.bf2, st);
+      if (!drop) colsum(c, G2, nullptr, nullptr, nullptr, d, 0, grads + y.bf2);
     }
     if (drop) masked_branch(2 + 2 * l, G2, grads + y.bf2);
     const float* dffn = drop ? DM : G2;  // d (f Wf2^T + bf2)
-    SR_CHECK(wgrad(p, dffn, sv + p.sv_f[l], grads + y.wf2, nullptr, T, dff, d, ws, st));
-    SR_CHECK(gemm_dyw(dffn, params + y.wf2, G1, sv + p.sv_f[l], T, dff, d, 0, st));  // G1 = d f  [T, dff], ReLU mask fused
-    SR_CHECK(wgrad(p, G1, sv + p.sv_out1[l], grads + y.wf1, grads + y.bf1, T, d, dff, ws, st));
-    SR_CHECK(gemm_dyw(G1, params + y.wf1, G2, nullptr, T, d, dff, 1, st));   // G2 = d out1 (both paths): accumulated
+    SR_CHECK(wgrad(c, dffn, sv + p.sv_f[l], grads + y.wf2, nullptr, dff, d));
+    SR_CHECK(gemm_dyw(c, dffn, y.wf2, G1, sv + p.sv_f[l], dff, d, 0));  // G1 = d f  [T, dff], ReLU mask fused
+    SR_CHECK(wgrad(c, G1, sv + p.sv_out1[l], grads + y.wf1, grads + y.bf1, d, dff));
+    SR_CHECK(gemm_dyw(c, G1, y.wf1, G2, nullptr, d, dff, 1));   // G2 = d out1 (both paths): accumulated
     // out1 = LN1(s1),  s1 = x_l + o
     if (d <= 1024) {  // g1 | b1, G0 = d s1 = d x_l (residual) = d o, bd
-      SR_CHECK(ln_bwd_cs(p, G2, sv + p.sv_s1[l], sv + p.sv_m1[l], sv + p.sv_r1[l], params + y.g1, d, G0, ws, grads + y.g1,
-                         drop ? nullptr : grads + y.bd, st));
+      SR_CHECK(ln_bwd_cs(c, G2, sv + p.sv_s1[l], sv + p.sv_m1[l], sv + p.sv_r1[l], params + y.g1, d, G0, grads + y.g1,
+                         drop ? nullptr : grads + y.bd));
     } else {
-      colsum_ln(p, G2, sv + p.sv_s1[l], sv + p.sv_m1[l], sv + p.sv_r1[l], d, ws, grads + y.g1, st);
+      colsum_ln(c, G2, sv + p.sv_s1[l], sv + p.sv_m1[l], sv + p.sv_r1[l], d, grads + y.g1);
       hipLaunchKernelGGL(sr_ln_bwd_kernel, dim3(rblk), dim3(SR_ROWS * 64), 0, st, (const float*)G2, sv + p.sv_s1[l], sv + p.sv_m1[l],
                          sv + p.sv_r1[l], params + y.g1, T, d, G0);
-      if (!drop) colsum(p, G0, nullptr, nullptr, nullptr, d, 0, ws, grads + y.bd, st);
+      if (!drop) colsum(c, G0, nullptr, nullptr, nullptr, d, 0, grads + y.bd);
     }
     if (drop) masked_branch(1 + 2 * l, G0, grads + y.bd);
     const float* dproj = drop ? DM : G0;  // d (A Wd^T + bd)
-    SR_CHECK(wgrad(p, dproj, sv + p.sv_A[l], grads + y.wd, nullptr, T, d, d, ws, st));
-    SR_CHECK(gemm_dyw(dproj, params + y.wd, G1, nullptr, T, d, d, 0, st));      // G1 = d A  [T, d]
+    SR_CHECK(wgrad(c, dproj, sv + p.sv_A[l], grads + y.wd, nullptr, d, d));
+    SR_CHECK(gemm_dyw(c, dproj, y.wd, G1, nullptr, d, d, 0));      // G1 = d A  [T, d]
     // G0 += attention path -> d x_l
     SR_CHECK(sr_attn_backward(ash, attn_split_half(l), sv + p.sv_x[l], G1, sv + p.sv_A[l], sv + p.sv_lse[l], batch, L, G0, st));
   }
   // ---- embedding FFN and the input LayerNorm's parameters -------------------------------------------------------------
   bool embed_done = false;
   if (drop) sr_drop_mask_launch(da, 0, G0, G0, nullptr, T, d, st);  // x0 has no residual: d embedding = D'(d x0) in place; wgrad sums d b2
-  if (fused && (g_sr_knob_bwd_fused & 4) && F % 4 == 0 && F <= SR_BWD_D && p.b_in == p.g_in + F && p.w1 == p.b_in + F && p.b1 == p.w1 + (int64_t)dff * F &&
+  if (fused && (c.knobs.bwd_fused & 4) && F % 4 == 0 && F <= SR_BWD_D && p.b_in == p.g_in + F && p.w1 == p.b_in + F && p.b1 == p.w1 + (int64_t)dff * F &&
       p.w2 == p.b1 + dff && p.b2 == p.w2 + (int64_t)d * dff) {
-    const SrPlan::SplitMat* m1 = sr_find_split(params + p.w1, dff, F);
-    const SrPlan::SplitMat* m2 = sr_find_split(params + p.w2, d, dff);
+    const SrPlan::SplitMat* m1 = c.split(p.w1, dff, F);
+    const SrPlan::SplitMat* m2 = c.split(p.w2, d, dff);
     const int64_t se = (int64_t)2 * F + (int64_t)dff * F + dff + (int64_t)d * dff + d;
     float* pe = nullptr;
-    if (m1 && m2 && m1->gt_off >= 0 && m2->gt_off >= 0 && (pe = arena_piece(fz_nwg * se)) != nullptr) {
+    if (m1 && m2 && m1->gt_off >= 0 && m2->gt_off >= 0 && (pe = folds.piece(fz_nwg * se)) != nullptr) {
       SrBwdEmbedArgs ea;
       memset(&ea, 0, sizeof(ea));
       ea.R = fz_R; ea.d = d; ea.dff = dff; ea.F = F; ea.ntiles = fz_tiles; ea.T = T;
       ea.dy = p.ws_g[0]; ea.h0 = p.sv_h0; ea.xg = p.sv_xg; ea.mean = p.sv_mean_in; ea.rstd = p.sv_rstd_in;
       ea.g_in = p.g_in; ea.b_in = p.b_in; ea.gt2 = m2->gt_off; ea.gt1 = m1->gt_off;
       ea.part = pe - ws; ea.part_stride = se;
-      SR_CHECK(sr_bwd_embed_launch(ea, fz_nwg, params, g_sr_h3.planes, sv, ws, st));
-      fold(pe, se, fz_nwg, (int)se, grads + p.g_in, st);  // d g_in | d b_in | d W1 | d b1 | d W2 | d b2
+      SR_CHECK(sr_bwd_embed_launch(ea, fz_nwg, params, c.planes, sv, ws, st));
+      folds.add(pe, se, fz_nwg, (int)se, grads + p.g_in, st);  // d g_in | d b_in | d W1 | d b1 | d W2 | d b2
       embed_done = true;
     }
   }
   if (!embed_done) {
-  SR_CHECK(wgrad(p, G0, sv + p.sv_h0, grads + p.w2, grads + p.b2, T, dff, d, ws, st));
-  SR_CHECK(gemm_dyw(G0, params + p.w2, G1, sv + p.sv_h0, T, dff, d, 0, st));  // ReLU mask fused
-  SR_CHECK(wgrad(p, G1, sv + p.sv_xn0, grads + p.w1, grads + p.b1, T, F, dff, ws, st));
-  SR_CHECK(gemm_dyw(G1, params + p.w1, G2, nullptr, T, F, dff, 0, st));      // G2 = d xn0  [T, F]
-  colsum_ln(p, G2, sv + p.sv_xg, sv + p.sv_mean_in, sv + p.sv_rstd_in, F, ws, grads + p.g_in, st);  // g_in | b_in
+  SR_CHECK(wgrad(c, G0, sv + p.sv_h0, grads + p.w2, grads + p.b2, dff, d));
+  SR_CHECK(gemm_dyw(c, G0, p.w2, G1, sv + p.sv_h0, dff, d, 0));  // ReLU mask fused
+  SR_CHECK(wgrad(c, G1, sv + p.sv_xn0, grads + p.w1, grads + p.b1, F, dff));
+  SR_CHECK(gemm_dyw(c, G1, p.w1, G2, nullptr, F, dff, 0));      // G2 = d xn0  [T, F]
+  colsum_ln(c, G2, sv + p.sv_xg, sv + p.sv_mean_in, sv + p.sv_rstd_in, F, grads + p.g_in);  // g_in | b_in
   }
   // ---- step tail: fold the loss partials behind the gradient ----------------------------------------------------------
   if (loss_ws != nullptr && n_loss_parts > 0) {
     const int tail = (int)ultr_tail_len(list_size);
-    fold((const float*)loss_ws, (int64_t)tail, (int)n_loss_parts, tail, grads + p.P, st, /*own_buffer=*/true);
+    folds.add((const float*)loss_ws, (int64_t)tail, (int)n_loss_parts, tail, grads + p.P, st, /*own_buffer=*/true);
   }
   folds.flush(st);
   return (int)hipGetLastError();
