@@ -126,6 +126,9 @@ int32_t ultr_dnn_forward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows, int32
 /* ... and the row-local backward kernel of ultr_train_step (aligned operands, dscores from a loss kernel): 16 / 32 = dnn_bwd2_kernel /
  * dnn_bwd_kernel, 1000 + R = the wide-tile kernel dnn_bwdw_kernel, 0 = the per-layer path. */
 int32_t ultr_dnn_backward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows);
+/* ... and whether a softmax / IPW training step of `batch` lists of `list_size` takes the fused forward + loss + backward kernel
+ * dnn_fb_kernel (aligned operands): 0 = no (the separate kernels), 8 / 16 = yes, with that many waves per workgroup (ULTR_FB_NW). */
+int32_t ultr_fused_fb_waves(const ultr_dnn_desc* d, int32_t batch, int32_t list_size);
 
 /* ---- a5 (backward half): what loss.backward() does for the DNN ----------------------
  * Replaces autograd through DNN.sequential (called from BaseAlgorithm.opt_step,

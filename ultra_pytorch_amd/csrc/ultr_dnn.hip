@@ -58,6 +58,8 @@ static void knobs_load() {
   k.big_bwd = env_read("ULTR_BIG_BWD", 1);
   // fused small-batch kernel: products as three fp16 MFMAs on hi / lo operand splits (1, default) or fp32 MFMAs (0)
   k.fb_h3 = env_read("ULTR_FB_H3", 1);
+  // ... on 8 or 16 waves per workgroup (16 only where fused_fb_waves qualifies the shape); 0 / unset: the default, FB_NW_DEFAULT
+  k.fb_nw = env_read("ULTR_FB_NW", 0);
   k.fwd_h3 = env_read("ULTR_FWD_H3", 1);
   k.bwd_h3 = env_read("ULTR_BWD_H3", 1);
   k.wg_h3 = env_read("ULTR_WG_H3", 1);                    // weight gradients on the fp16 matrix cores (split-half operands); 2: any batch size
@@ -949,6 +951,40 @@ int ultr_dnn_backward_softmax_ctx(const ultr_dnn_desc* d, const float* params, c
   return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, nullptr, loss_ws, bwd_ws, grads, stream, fl, ctx);
 }
 
+// Does a step of `batch` lists of L take dnn_fb_kernel, and on how many waves per workgroup?  0 = no (the separate kernels), 8 / 16.
+// `vm` as vecmask_for gives it, wt_aligned = the weight copies sit on a 16-byte boundary.  The 16-wave build (ULTR_FB_NW) covers
+// split-half products with every tile at most 256 wide (the split-half copies need widths >= 256, so every hidden layer is exactly
+// 256 wide: each of the 16 waves owns exactly one 16-column tile of every product), where its 16 column-partial rows still fit the LDS.
+#ifndef FB_NW_DEFAULT
+#define FB_NW_DEFAULT 16
+#endif
+static int fused_fb_waves(const DnnPlan& p, int vm, bool wt_aligned, int64_t batch, int L, int64_t n_docs, size_t* lds_out) {
+  if (knobs().no_fused_fb != 0 || batch <= 0 || L <= 0 || L > 16) return 0;
+  const int64_t N = batch * L;
+  const int lpb = 16 / L;
+  const int64_t nblk = (batch + lpb - 1) / lpb;
+  const size_t lds = fb_lds_floats(p, 8) * sizeof(float);
+  const bool ok = all_vec(p, vm, N, n_docs) && knobs().no_vec == 0 && wt_aligned &&
+                  p.nl >= 2 && p.maxdim <= 512 && p.pv_total <= 3 * 512 * 4 && lds <= 160 * 1024 &&
+                  nblk <= (int64_t)knobs().fb_max_wg_per_cu * dnn_device_cus() &&  // one round of workgroups (tools/fused_threshold.py:
+                                                                                   // B=256 62 vs 68 us, B=288 94 vs 70 us)
+                  nblk <= (N + 8) / 9 + 1 &&                                       // vector-slab allocation (>= 9 live rows / block)
+                  p.sv_total * 4 < ((int64_t)1 << 31) && p.P * 4 < ((int64_t)1 << 31);
+  if (!ok) return 0;
+  const int want = knobs().fb_nw == 8 || knobs().fb_nw == 16 ? knobs().fb_nw : FB_NW_DEFAULT;
+  // static LDS of the kernel: the layer records and the 16 per-row output scales
+  const size_t lds16 = fb_lds_floats(p, 16) * sizeof(float), stat = (size_t)ULTR_MAXL * FbPlan::NFIELD * sizeof(int) + 16 * sizeof(float);
+  const bool nw16 = want == 16 && p.fb_h3 != 0 && p.maxdim <= 256 && lds16 + stat <= 160 * 1024;
+  if (lds_out) *lds_out = nw16 ? lds16 : lds;
+  return nw16 ? 16 : 8;
+}
+extern "C" int32_t ultr_fused_fb_waves(const ultr_dnn_desc* d, int32_t batch, int32_t list_size) {
+  DnnPlan p;
+  if (batch <= 0 || list_size <= 0 || !ultr_make_dnn_plan(d, (int64_t)batch * list_size, &p)) return -1;
+  const float* aligned = reinterpret_cast<const float*>((uintptr_t)16);  // (vecmask_for only looks at the address)
+  return fused_fb_waves(p, vecmask_for(p, aligned, aligned), true, batch, list_size, 0, nullptr);
+}
+
 // internal (ultr_train_step): forward + NA/IPW loss + backward for a small batch through dnn_fb_kernel, then the weight
 // gradients + reduction.  Returns ULTR_E_UNSUPPORTED when the shape does not qualify - the caller then issues the
 // separate forward / backward calls.
@@ -959,30 +995,17 @@ int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const f
   if (!params || !wt || !docids || !scores || !saved || !labels || !loss_ws || !bwd_ws || !grads || batch <= 0 ||
       list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features) || (ipw_table && n_ipw <= 0))
     return ULTR_E_BADARG;
-  if (knobs().no_fused_fb != 0) return ULTR_E_UNSUPPORTED;
   const int L = list_size;
-  if (L > 16) return ULTR_E_UNSUPPORTED;
+  if (knobs().no_fused_fb != 0 || L > 16) return ULTR_E_UNSUPPORTED;
   const int64_t N = (int64_t)batch * L;
   DnnPlan p;
   BwdPlan bp;
   if (!ultr_make_dnn_plan(d, N, &p) || !ultr_make_bwd_plan(p, N, &bp)) return ULTR_E_BADARG;
   const int lpb = 16 / L, rb = lpb * L;
   const int64_t nblk = (batch + lpb - 1) / lpb;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int vm = vecmask_for(p, params, features);
-  const size_t lds = fb_lds_floats(p) * sizeof(float);
-  const bool ok = all_vec(p, vm, N, n_docs) && knobs().no_vec == 0 && ((uintptr_t)wt & 15) == 0 &&
-                  p.nl >= 2 && p.maxdim <= 512 && p.pv_total <= 3 * 512 * 4 && lds <= 160 * 1024 &&
-                  nblk <= (int64_t)knobs().fb_max_wg_per_cu * cus &&  // one round of workgroups (tools/fused_threshold.py:
-                                                                          // B=256 62 vs 68 us, B=288 94 vs 70 us)
-                  nblk <= (N + 8) / 9 + 1 &&                               // vector-slab allocation (>= 9 live rows / block)
-                  p.sv_total * 4 < ((int64_t)1 << 31) && p.P * 4 < ((int64_t)1 << 31);
-  if (!ok) return ULTR_E_UNSUPPORTED;
+  size_t lds = 0;
+  const int fb_nw = fused_fb_waves(p, vecmask_for(p, params, features), ((uintptr_t)wt & 15) == 0, batch, L, n_docs, &lds);
+  if (fb_nw == 0) return ULTR_E_UNSUPPORTED;
   bp.nrb = (int)nblk;
   bp.l0g = p.nl >= 2 ? 1 : 0;  // must match backward_impl's choice
   bp.wg_prenorm = 1;
@@ -1006,7 +1029,7 @@ int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const f
   hipError_t e;
   {
     UltrProfScope prof(ULTR_K_FUSED, st);
-    const int rcf = ultr_launch_dnn_fb(prof, p, bp, lds, nblk, st, params, wt, features, n_docs, docids, (int)batch, L, lpb, scores, (float*)saved, ws,
+    const int rcf = ultr_launch_dnn_fb(prof, p, bp, fb_nw, lds, nblk, st, params, wt, features, n_docs, docids, (int)batch, L, lpb, scores, (float*)saved, ws,
                                        fl, fp);
     if (rcf) return rcf;
   }

@@ -15,16 +15,24 @@
 // Chosen only when the grid is at most ONE workgroup per CU (measured, tools/fused_threshold.py: B = 256 lists of 10 -> 62 vs
 // 68 us per step; B = 288 -> 94 vs 70 us, a second round of long workgroups); larger batches use the separate kernels,
 // whose 16-row tiles are completely live.
-
-template <int XC, bool H3>
-__global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, const float* __restrict__ params,
+//
+// NW = 16 (ULTR_FB_NW, split-half products with every tile at most 256 wide; ultr_fused_fb_waves): one row per wave in the row-wise
+// phases and ONE 16-column tile per wave in the products (chunk w >> 1, tile w & 1: PipeH3T), 128 VGPRs per wave.  On its own that is
+// no faster - the row-wise phases are VALU instruction streams, not latency chains (profiles/fb_nw16.md) - but it makes two things
+// cheap: a wave whose row is dead sits out the row-wise phases behind one branch (`row_live`), and a product's first weight steps are
+// requested in front of the phase that makes its A tile (`pf16`).  Same bits as NW = 8: rows, lanes, reductions and k-order are
+// unchanged; where the 8-wave build folds rows w and w + 8 in one wave (column partials, loss partials), waves 8..15 leave the
+// OPERANDS of their row's contribution and `finalize` applies them to wave w - 8's partial with the expression the 8-wave row pass uses.
+template <int XC, bool H3, int NW>
+__global__ __launch_bounds__(64 * NW) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, const float* __restrict__ params,
                                                      const float* __restrict__ wt, const float* __restrict__ features,
                                                      int64_t n_docs, const int32_t* __restrict__ docids, int B, int L,
                                                      int LPB, float* __restrict__ scores, float* __restrict__ saved,
                                                      float* __restrict__ ws, FusedSoftmax fl, FbPlan fp) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ int sm_plan[ULTR_MAXL * FbPlan::NFIELD];
-  constexpr int R = 16, NW = 8, RT = 1, NT = NW * 64, RPW = R / NW;
+  static_assert(NW == 8 || (NW == 16 && H3 && XC == 1), "the 16-wave build covers split-half products at maxdim <= 256");
+  constexpr int R = 16, RT = 1, NT = NW * 64, RPW = R / NW;
   const int64_t N = (int64_t)B * L;
   const int ld = fwd_ld(p.maxdim), ldu = bwd_ldu(p.maxdim), ldz = ld;
   const int cpw = bwd2_cp_stride(p);
@@ -71,9 +79,25 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
     if constexpr (KA_LINES > 64) ka_pf += ka[(lane + 64 < KA_LINES ? lane + 64 : 0) * 16];
   }
 
+  // NW = 16: one weight pipe for every product of the kernel, and a product's stream is begun a phase EARLY (FB_PF16): the first
+  // FB_SWD16 - 1 steps of a wave's tile are requested in front of the phase that produces the product's A tile (a LayerNorm, a backward
+  // row pass) - the weights do not depend on it, the phase itself loads nothing from memory (so no wait in it queues behind the
+  // stream), and at 128 registers per wave the steps fit next to the row arithmetic.  pf16(fwd, jj) requests layer jj's forward
+  // (W_jj^T fragments) / dgrad (W_jj fragments) stream for this wave's tile.  (Requested any earlier - in front of the prologue, or
+  // behind the previous product - the stream delays the loads that phase waits for: profiles/fb_nw16.md.)
+  [[maybe_unused]] PipeH3T<FB_SWD16> ph16;
+  [[maybe_unused]] auto pf16 = [&](bool fwd, int jj) {
+    const int rvp = rec_of(jj);
+    const int K_ = FBF(rvp, FbPlan::K), M_ = FBF(rvp, FbPlan::M);
+    // forward: contraction K_ (padded to 32), output columns M_; dgrad: contraction M_, output columns K_
+    const int nks = (fwd ? round_up(K_, 32) : round_up(M_, 32)) >> 5, ncol = fwd ? M_ : K_;
+    const Src Wh = make_src(wt + (fwd ? FBF64(rvp, FbPlan::WHF_OFF) : FBF64(rvp, FbPlan::WHB_OFF)), (int64_t)round_up(K_, 32) * round_up(M_, 32));
+    ph16.begin(Wh, wave >> 1, wave & 1, nks, (wave >> 1) * 32 < ncol, lane);
+  };
+
   // ---- prologue: ids, loss inputs of this wave's list, parameter image, feature rows - all issued back to back -----
   {
-    constexpr int PVR = 3, FCH = XC;
+    constexpr int PVR = (3 * 512 + NT - 1) / NT, FCH = XC;  // pv_total <= 3 * 512 * 4 floats (ultr_fused_step_softmax)
     const int F = p.K[0];
     const int rme = wave + NW * (lane < RPW ? lane : 0);
     const bool idok = lane < RPW && rme < rows_valid;
@@ -112,6 +136,29 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
     if (tid < R) sm_ds[tid] = 0.f;
     if (lane < 2) sm_lt[wave * 2 + lane] = 0.f;
   }
+  // NW = 16: a wave whose row is past the block's live rows (rows 10..15 at list size 10) sits out the row-wise phases - a branch per
+  // wave, where the 8-wave build would have to mask half of a wave's unrolled work.  What the others read of its row is written here
+  // once, as the zeros the arithmetic on an absent row gives: statistics, score, column partials; the product operands' planes too.
+  const bool row_live = (NW == 8) || wave < rows_valid;
+  if constexpr (NW == 16) {
+    if (!row_live) {
+      const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      const fbh4 zh = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+      for (int c = 4 * lane; c < cpw; c += 256) st4(CP + wave * cpw + c, z4);
+      for (int c = 4 * lane; c < ldh; c += 256) {
+        *reinterpret_cast<fbh4*>(AH + wave * ldh + c) = zh;
+        *reinterpret_cast<fbh4*>(AL + wave * ldh + c) = zh;
+      }
+      if (lane < p.nl) {
+        sm_mean[lane * R + wave] = 0.f;
+        sm_rstd[lane * R + wave] = 0.f;
+      }
+      if (lane == 0) {
+        sm_s[wave] = 0.f;
+        sm_os[wave] = 0.f;
+      }
+    }
+  }
   // loss inputs of the wave's first list (lane = position), in flight during the whole forward
   const int li0 = wave;  // list index inside the block handled by this wave (then + NW)
   const bool lact0 = li0 < LPB && b_first + li0 < B && lane < L;
@@ -142,8 +189,11 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
     const float* bias = bs + K;
     const float* wlp = PV + p.pv_wlast;
     const float invK = 1.0f / (float)K;
+    if constexpr (NW == 16 && FB_PF16 != 0) {
+      if (!last) pf16(true, j);
+    }
     // ---- LayerNorm_j: XS_j -> UZ (zero-padded to a multiple of 32 columns); the scorer folded into the last one ----
-    {
+    if (row_live) {
       float4 x[RPW][XC], g4[XC], b4[XC];
       float s[RPW];
       const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -280,6 +330,19 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
       if constexpr (H3) {
         const int nks = K32 >> 5;
         const Src Wh = make_src(wt + FBF64(rv, FbPlan::WHF_OFF), (int64_t)K32 * M);
+        if constexpr (NW == 16) {
+          PipeH3T<FB_SWD16>& ph = ph16;
+          const int tile = wave & 1, c0 = (wave >> 1) * 32;
+          if constexpr (FB_PF16 == 0) ph.begin(Wh, wave >> 1, tile, nks, c0 < M, lane);
+          for (int cc = c0; cc < M; cc += (NW / 2) * 32) {
+            f32x4 acc[RT][1], accx;
+            acc[0][0] = accx = (f32x4){0.f, 0.f, 0.f, 0.f};
+            ph.run(AH, AL, ldh, Wh, nks, acc[0][0], accx, lane);
+            if (cc + (NW / 2) * 32 < M) ph.begin(Wh, (cc + (NW / 2) * 32) >> 5, tile, nks, true, lane);
+            fb_h3_finish(acc, accx, sm_os, lane);
+            finish_fwd_nn<RT, 1, 2>(acc, Y, ld, M, cc + tile, lane, bias, p.act, gout, rows_valid);
+          }
+        } else {
         PipeH3<FB_SWD> ph;
         const int c0 = wave * 32;
         ph.begin(Wh, wave, nks, c0 < M, lane);
@@ -291,6 +354,7 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
           if (cc + NW * 32 < M) ph.begin(Wh, (cc + NW * 32) >> 5, nks, true, lane);
           fb_h3_finish(acc, accx, sm_os, lane);
           finish_fwd_nn<RT, 2>(acc, Y, ld, M, cc, lane, bias, p.act, gout, rows_valid);
+        }
         }
       } else if (FB_SW && p.sw_ok && ksplit == 1) {
         const int ntr = K32 >> 5;
@@ -385,7 +449,10 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
     for (int t = tid; t < tail; t += NT) {
       float v = 0.f;
       if (t < 2)
-        for (int w = 0; w < NW; ++w) v += sm_lt[w * 2 + t];
+        for (int w = 0; w < 8; ++w) {
+          if constexpr (NW == 16) v += sm_lt[w * 2 + t] + sm_lt[(w + 8) * 2 + t];  // lists w and w + 8, as one 8-wave wave adds them
+          else v += sm_lt[w * 2 + t];
+        }
       fl.loss_part[(int64_t)blockIdx.x * tail + t] = v;
     }
   }
@@ -400,10 +467,26 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
     for (int c = tid; c < K; c += NT) {
       float pg = 0.f, pb = 0.f, pw = 0.f;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        pg += CP[w * cpw + c];
-        pb += CP[w * cpw + K4 + c];
-        if (lastl) pw += CP[w * cpw + 2 * K4 + c];
+      for (int w = 0; w < 8; ++w) {
+        if constexpr (NW == 16) {
+          // wave w + 8 left xhat | du | gamma xhat + beta of row w + 8: the second term of the 8-wave wave's two-row partial
+          const float* hi = CP + (w + 8) * cpw;
+          const float xh = hi[c], du = hi[K4 + c];
+          float g1 = CP[w * cpw + c], b1 = CP[w * cpw + K4 + c];
+          g1 += du * xh;
+          b1 += du;
+          pg += g1;
+          pb += b1;
+          if (lastl) {
+            float w1 = CP[w * cpw + 2 * K4 + c];
+            w1 += sm_ds[w + 8] * hi[2 * K4 + c];
+            pw += w1;
+          }
+        } else {
+          pg += CP[w * cpw + c];
+          pb += CP[w * cpw + K4 + c];
+          if (lastl) pw += CP[w * cpw + 2 * K4 + c];
+        }
       }
       vslab[vg + c] = pg;
       vslab[vb + c] = pb;
@@ -427,7 +510,22 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
       finalize(j + 1);
       const Src Wsrc = make_src(params + FBF64(rv, FbPlan::OFF_W), (int64_t)M * K);
       const int nch = FBF(rv, FbPlan::BWD_NCH), msplit = FBF(rv, FbPlan::BWD_MSPLIT), mode = FBF(rv, FbPlan::BWD_MODE);
-      if (H3 && j >= 1) {
+      if constexpr (NW == 16) {
+        // (the fused kernel always takes the layer-0 shortcut: j >= 1 here)  one tile per wave, as in the forward
+        const int nks = (M + 31) >> 5;
+        const Src Wh = make_src(wt + FBF64(rv, FbPlan::WHB_OFF), (int64_t)round_up(M, 32) * round_up(K, 32));
+        PipeH3T<FB_SWD16>& ph = ph16;
+        const int tile = wave & 1;
+        if constexpr (FB_PF16 == 0) ph.begin(Wh, wave >> 1, tile, nks, (wave >> 1) * 32 < K, lane);
+        for (int ch = wave >> 1; ch * 32 < K; ch += NW / 2) {
+          f32x4 acc[RT][1], accx;
+          acc[0][0] = accx = (f32x4){0.f, 0.f, 0.f, 0.f};
+          ph.run(AH, AL, ldh, Wh, nks, acc[0][0], accx, lane);
+          if ((ch + NW / 2) * 32 < K) ph.begin(Wh, ch + NW / 2, tile, nks, true, lane);
+          acc[0][0] += accx;
+          store_nn<RT, 1, 2>(acc, DU, ldu, K, ch * 32 + tile, lane, false);
+        }
+      } else if (H3 && j >= 1) {
         // du_j = dz_j . W_j on the fp16 matrix cores: the row pass left dz_j as hi / lo planes with per-row scales
         const int nks = (M + 31) >> 5;
         const Src Wh = make_src(wt + FBF64(rv, FbPlan::WHB_OFF), (int64_t)round_up(M, 32) * round_up(K, 32));
@@ -496,7 +594,10 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
       lds_barrier();
     }
     TRACE_STAMP(18 + 4 * (top - j));
-    {
+    if constexpr (NW == 16 && FB_PF16 != 0) {
+      if (j - 1 >= jlow) pf16(false, j - 1);  // the next dgrad product's stream, in flight during this layer's row pass
+    }
+    if (row_live) {
       const float* XS = XSall + (size_t)j * R * ld;
       const float* gs = PV + FBF(rv, FbPlan::PV_OFF);
       const float* bs = gs + K;
@@ -537,9 +638,24 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
           const float4 xh = make_float4((x4.x - mean[k]) * rstd[k], (x4.y - mean[k]) * rstd[k],
                                         (x4.z - mean[k]) * rstd[k], (x4.w - mean[k]) * rstd[k]);
           const float4 gx = make_float4(du4.x * g4.x, du4.y * g4.y, du4.z * g4.z, du4.w * g4.w);
-          red[k] += (gx.x + gx.y) + (gx.z + gx.w);
-          red[RPW + k] += (gx.x * xh.x + gx.y * xh.y) + (gx.z * xh.z + gx.w * xh.w);
-          if (act) {
+          // The contraction of these sums of two products is spelled out: which product is rounded before the add is otherwise
+          // hipcc's pick per unrolled copy, and the 8- and 16-wave builds must agree bit for bit.  The forms are the ones the
+          // 8-wave build has always computed for its first (rows 0..7) and second (rows 8..15) row; the builds without a 16-wave form
+          // keep the plain expressions.
+          if constexpr (XC == 1 && H3) {
+            const bool row_hi = (NW == 16) ? (wave >= 8) : (k == 1);
+            red[k] += (row_hi ? fmaf(du4.x, g4.x, gx.y) : fmaf(du4.y, g4.y, gx.x)) + fmaf(du4.z, g4.z, gx.w);
+            red[RPW + k] += fmaf(gx.x, xh.x, gx.y * xh.y) + fmaf(gx.z, xh.z, gx.w * xh.w);
+          } else {
+            red[k] += (gx.x + gx.y) + (gx.z + gx.w);
+            red[RPW + k] += (gx.x * xh.x + gx.y * xh.y) + (gx.z * xh.z + gx.w * xh.w);
+          }
+          if (NW == 16 && wave >= 8) {
+            // rows 8..15: the operands, not the products - finalize() adds them to row (wave - 8)'s partial in the 8-wave order
+            pg = xh;
+            pb = du4;
+            pw = make_float4(g4.x * xh.x + be4.x, g4.y * xh.y + be4.y, g4.z * xh.z + be4.z, g4.w * xh.w + be4.w);
+          } else if (act) {
             pg.x += du4.x * xh.x; pg.y += du4.y * xh.y; pg.z += du4.z * xh.z; pg.w += du4.w * xh.w;
             pb.x += du4.x; pb.y += du4.y; pb.z += du4.z; pb.w += du4.w;
             if (last) {
@@ -628,25 +744,28 @@ __global__ __launch_bounds__(512) void dnn_fb_kernel(DnnPlan p, BwdPlan bp, cons
 
 ULTR_TRACE_READER(ultr_trace_read_fb)
 
-int ultr_launch_dnn_fb(UltrProfScope& prof, const DnnPlan& p, const BwdPlan& bp, size_t lds, int64_t nblk, hipStream_t st, const float* params,
+int ultr_launch_dnn_fb(UltrProfScope& prof, const DnnPlan& p, const BwdPlan& bp, int nw, size_t lds, int64_t nblk, hipStream_t st, const float* params,
                        const float* wt, const float* features, int64_t n_docs, const int32_t* docids, int batch, int L, int lpb, float* scores,
                        float* saved, float* ws, const FusedSoftmax& fl, const FbPlan& fp) {
   hipError_t e = hipSuccess;
-#define LAUNCH_FB(XX, HH)                                                                                                      \
+#define LAUNCH_FB(XX, HH, WW)                                                                                                  \
   do {                                                                                                                         \
-    e = set_lds(dnn_fb_kernel<XX, HH>, lds);                                                                                   \
+    e = set_lds(dnn_fb_kernel<XX, HH, WW>, lds);                                                                               \
     if (e != hipSuccess) return (int)e;                                                                                        \
-    ULTR_LAUNCH(prof, (dnn_fb_kernel<XX, HH>), dim3((unsigned)nblk), dim3(512), lds, st, p, bp, params, wt, features, n_docs,  \
-                docids, batch, L, lpb, scores, saved, ws, fl, fp);                                                             \
+    ULTR_LAUNCH(prof, (dnn_fb_kernel<XX, HH, WW>), dim3((unsigned)nblk), dim3(64 * WW), lds, st, p, bp, params, wt, features,  \
+                n_docs, docids, batch, L, lpb, scores, saved, ws, fl, fp);                                                     \
   } while (0)
   // products on the fp16 matrix cores with split operands where the plan has the split-half copies (ULTR_FB_H3=0: fp32 MFMAs)
   const bool h3 = p.fb_h3 != 0;
-  if (p.maxdim <= 256) {
-    if (h3) LAUNCH_FB(1, true);
-    else LAUNCH_FB(1, false);
+  if (nw == 16) {
+    if (!h3 || p.maxdim > 256) return ULTR_E_UNSUPPORTED;  // (ultr_fused_fb_waves never plans it)
+    LAUNCH_FB(1, true, 16);
+  } else if (p.maxdim <= 256) {
+    if (h3) LAUNCH_FB(1, true, 8);
+    else LAUNCH_FB(1, false, 8);
   } else {
-    if (h3) LAUNCH_FB(2, true);
-    else LAUNCH_FB(2, false);
+    if (h3) LAUNCH_FB(2, true, 8);
+    else LAUNCH_FB(2, false, 8);
   }
 #undef LAUNCH_FB
   return (int)hipGetLastError();

@@ -550,15 +550,87 @@ __device__ __forceinline__ void fb_h3_finish(f32x4 (&acc)[1][2], const f32x4 (&a
     for (int r = 0; r < 4; ++r) acc[0][t][r] = (acc[0][t][r] + accx[t][r]) * o[r];
 }
 
+// ONE-tile form for the 16-wave build of dnn_fb_kernel: a wave owns tile `tile` (0 / 1) of a 32-column chunk and loads that tile's two
+// 1-KiB fragments (hi, lo) of every 32-deep step - the same copy, the same products in the same order per output element as PipeH3,
+// half the registers per step in flight (depth 4 costs what depth 2 costs there).
+template <int D>
+struct PipeH3T {
+  static_assert(D >= 2 && D <= 8, "pipeline depth");
+  float4 b[D][2];
+  unsigned of;
+  int left;
+  template <int S>
+  __device__ __forceinline__ void fetch(const Src& W) {
+    const bool ok = left > 0;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) b[S][u] = buf_ld4(W, ok ? (of + (unsigned)u * 1024u) : ULTR_OOB);
+    --left;
+    of += 4096u;
+  }
+  template <int... I>
+  __device__ __forceinline__ void fetch_all(const Src& W, std::integer_sequence<int, I...>) {
+    (fetch<I>(W), ...);
+  }
+  // requests the first D - 1 steps; !valid (or past nks): no traffic
+  __device__ __forceinline__ void begin(const Src& W, int chunk, int tile, int nks, bool valid, int lane) {
+    of = ((unsigned)chunk * (unsigned)nks * 256u + (unsigned)lane) * 16u + (unsigned)tile * 2048u;
+    left = valid ? nks : 0;
+    fetch_all(W, std::make_integer_sequence<int, D - 1>());
+  }
+  template <int S>
+  __device__ __forceinline__ void consume(const _Float16* __restrict__ ah_p, const _Float16* __restrict__ al_p, f32x4& acc, f32x4& accx,
+                                          f32x4& accy) {
+    const fbh8 ah = *reinterpret_cast<const fbh8*>(ah_p), al = *reinterpret_cast<const fbh8*>(al_p);
+    const fbh8 wh = fb_as_h8(b[S][0]), wl = fb_as_h8(b[S][1]);
+    acc = fb_mfma_h(ah, wh, acc);
+    accx = fb_mfma_h(ah, wl, accx);
+    accy = fb_mfma_h(al, wh, accy);
+  }
+  template <int... I>
+  __device__ __forceinline__ void steps(const _Float16*& ph, const _Float16*& pl, const Src& W, f32x4& acc, f32x4& accx, f32x4& accy,
+                                        std::integer_sequence<int, I...>) {
+    ((fetch<(I + D - 1) % D>(W), __builtin_amdgcn_sched_barrier(0), consume<I>(ph, pl, acc, accx, accy), ph += 32, pl += 32), ...);
+  }
+  template <int... I>
+  __device__ __forceinline__ void tail(const _Float16*& ph, const _Float16*& pl, int n, f32x4& acc, f32x4& accx, f32x4& accy,
+                                       std::integer_sequence<int, I...>) {
+    ((I < n ? (consume<I>(ph, pl, acc, accx, accy), ph += 32, pl += 32, 0) : 0), ...);
+  }
+  __device__ __forceinline__ void run(const _Float16* __restrict__ Ah, const _Float16* __restrict__ Al, int ldh, const Src& W, int nks,
+                                      f32x4& acc, f32x4& accx, int lane) {
+    const int i = lane & 15, q = lane >> 4;
+    const _Float16* ph = Ah + i * ldh + 8 * q;
+    const _Float16* pl = Al + i * ldh + 8 * q;
+    f32x4 accy = (f32x4){0.f, 0.f, 0.f, 0.f};
+    int t = 0;
+    for (; t + D <= nks; t += D) steps(ph, pl, W, acc, accx, accy, std::make_integer_sequence<int, D>());
+    tail(ph, pl, nks - t, acc, accx, accy, std::make_integer_sequence<int, D - 1>());  // (< D steps, already in flight)
+    accx += accy;
+  }
+};
+#ifndef FB_SWD16
+#define FB_SWD16 3  // steps in flight per wave of the one-tile pipeline (profiles/fb_nw16.md: 2 loses 2.6k cycles per workgroup, 3 and 4 tie)
+#endif
+#ifndef FB_PF16
+#define FB_PF16 1   // the 16-wave build begins a product's weight stream one phase early (0: when the product starts)
+#endif
+__device__ __forceinline__ void fb_h3_finish(f32x4 (&acc)[1][1], const f32x4& accx, const float* __restrict__ os, int lane) {
+  const float4 o4 = ld4(os + 4 * (lane >> 4));
+  const float o[4] = {o4.x, o4.y, o4.z, o4.w};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[0][0][r] = (acc[0][0][r] + accx[r]) * o[r];
+}
+
 // forward epilogue of the last contraction slice: (+ partial sums of earlier slices) + bias, activation; to LDS
-// (next layer's input) and, when training, to HBM — 4*CT-byte stores, the lane owns CT consecutive output columns
-template <int RT, int CT>
+// (next layer's input) and, when training, to HBM — 4*CT-byte stores, the lane owns CT consecutive output columns (lanes CS columns
+// apart: CT = 1, CS = 2 and c0 + t is tile t of a two-tile chunk on its own)
+template <int RT, int CT, int CS = CT>
 __device__ __forceinline__ void finish_fwd_nn(const f32x4 (&acc)[RT][CT], float* __restrict__ Ys, int ldy, int M, int c0,
                                               int lane, const float* __restrict__ bias, int act,
                                               float* __restrict__ gout, int rows_valid) {
   // VEC path only: M % 4 == 0, so a lane's CT columns are all inside or all outside
   const int i = lane & 15, q = lane >> 4;
-  const int col = c0 + CT * i;
+  const int col = c0 + CS * i;
   if (col >= M) return;
   float bv[CT];
 #pragma unroll
@@ -573,21 +645,23 @@ __device__ __forceinline__ void finish_fwd_nn(const f32x4 (&acc)[RT][CT], float*
 #pragma unroll
       for (int t = 0; t < CT; ++t) v[t] = act_fwd(acc[rt][t][r] + bv[t], act);
       if constexpr (CT == 4) st4(dst, make_float4(v[0], v[1], v[2], v[3]));
-      else *reinterpret_cast<float2*>(dst) = make_float2(v[0], v[1]);
+      else if constexpr (CT == 2) *reinterpret_cast<float2*>(dst) = make_float2(v[0], v[1]);
+      else dst[0] = v[0];
       if (gout != nullptr && row < rows_valid) {
         float* g = gout + (int64_t)row * M + col;
         if constexpr (CT == 4) st4_out(g, make_float4(v[0], v[1], v[2], v[3]));
-        else st2_out(g, make_float2(v[0], v[1]));
+        else if constexpr (CT == 2) st2_out(g, make_float2(v[0], v[1]));
+        else g[0] = v[0];
       }
     }
 }
 
 // epilogue of gemm_nn: lane holds D_t[row = 4q + r][j = i] = DU[row][c0 + CT*i + t]
-template <int RT, int CT>
+template <int RT, int CT, int CS = CT>
 __device__ __forceinline__ void store_nn(const f32x4 (&acc)[RT][CT], float* __restrict__ DUs, int ldu, int K, int c0,
                                          int lane, bool add) {
   const int i = lane & 15, q = lane >> 4;
-  const int col = c0 + CT * i;
+  const int col = c0 + CS * i;
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -596,7 +670,7 @@ __device__ __forceinline__ void store_nn(const f32x4 (&acc)[RT][CT], float* __re
       float vv[CT];
 #pragma unroll
       for (int t = 0; t < CT; ++t) vv[t] = acc[rt][t][r];
-      if (col + CT - 1 < K) {
+      if (CT > 1 && col + CT - 1 < K) {
         if constexpr (CT == 4) {
           float4 v = make_float4(vv[0], vv[1], vv[2], vv[3]);
           if (add) {
@@ -604,7 +678,7 @@ __device__ __forceinline__ void store_nn(const f32x4 (&acc)[RT][CT], float* __re
             v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
           }
           st4(dst, v);
-        } else {
+        } else if constexpr (CT == 2) {
           float2 v = make_float2(vv[0], vv[1]);
           if (add) {
             const float2 o = *reinterpret_cast<const float2*>(dst);
@@ -729,10 +803,10 @@ struct WideBwd {
 };
 
 // dnn_fb_kernel (ultr_dnn_fb.hip)
-__host__ __device__ static inline size_t fb_lds_floats(const DnnPlan& p) {
+__host__ __device__ static inline size_t fb_lds_floats(const DnnPlan& p, int nw) {
   const size_t ld = fwd_ld(p.maxdim), ldu = bwd_ldu(p.maxdim);
-  return (size_t)16 * ld * (p.nl + 1) + 16 * ldu + (size_t)8 * bwd2_cp_stride(p) + (size_t)p.pv_total + 2 * 16 * (size_t)p.nl +
-         2 * 16 + 2 * 8 + 8 +
+  return (size_t)16 * ld * (p.nl + 1) + 16 * ldu + (size_t)nw * bwd2_cp_stride(p) + (size_t)p.pv_total + 2 * 16 * (size_t)p.nl +
+         2 * 16 + 2 * (size_t)nw + 8 +
          (p.h3_ok ? (size_t)16 * (round_up(p.maxdim, 32) + 8) + 8 : 0);  // two fp16 planes [16][ldh] (4 bytes per element)
 }
 
@@ -751,7 +825,7 @@ __host__ __device__ static inline size_t fb_lds_floats(const DnnPlan& p) {
 
 // ---- knobs (ultr_dnn.hip: read once, re-read by ultr_config_reload) ----------------------------------------------------------------
 struct Knobs {
-  int fwd_r, bwd_r, wgrad_wgs, fwd_nw, bwd_nw, no_vec, no_fused_fb, fb_max_wg_per_cu, fwd_q4, big_fwd, big_bwd, fb_h3, fwd_h3, bwd_h3, wg_h3, wg_h3_min_rows, wg_h3_wgs, fwd_wide, bwd_wide, fwd_wide_rmax;
+  int fwd_r, bwd_r, wgrad_wgs, fwd_nw, bwd_nw, no_vec, no_fused_fb, fb_max_wg_per_cu, fwd_q4, big_fwd, big_bwd, fb_h3, fb_nw, fwd_h3, bwd_h3, wg_h3, wg_h3_min_rows, wg_h3_wgs, fwd_wide, bwd_wide, fwd_wide_rmax;
   bool loaded;
 };
 const Knobs& ultr_knobs();
@@ -779,7 +853,7 @@ int ultr_launch_dnn_bwd2(UltrProfScope& prof, const DnnPlan& p, const BwdPlan& b
 int ultr_launch_dnn_bwdw(UltrProfScope& prof, const DnnPlan& p, const BwdPlan& bp, const WideBwd& wb, size_t wblds, hipStream_t st,
                          const float* saved, const float* dscores, float* ws, const float* wt);
 // ultr_dnn_fb.hip
-int ultr_launch_dnn_fb(UltrProfScope& prof, const DnnPlan& p, const BwdPlan& bp, size_t lds, int64_t nblk, hipStream_t st, const float* params,
+int ultr_launch_dnn_fb(UltrProfScope& prof, const DnnPlan& p, const BwdPlan& bp, int nw, size_t lds, int64_t nblk, hipStream_t st, const float* params,
                        const float* wt, const float* features, int64_t n_docs, const int32_t* docids, int batch, int L, int lpb, float* scores,
                        float* saved, float* ws, const FusedSoftmax& fl, const FbPlan& fp);
 // ultr_dnn_wgrad.hip
