@@ -437,7 +437,9 @@ int ultr_dnn_forward_ndcg(const ultr_dnn_desc* d, const float* params, const flo
  * means, ws [batch][n_metrics][n_topn] per-list values.  host_report (may be NULL): a pinned, device-mapped page of >= 8 * 16 + 1 floats -
  * the n_metrics * n_topn means, then the word host_report[128] = seq.  counter as for ultr_ndcg_report (the two may share one).
  * ULTR_E_BADARG: a missing pointer, n_metrics outside 1 .. 8, an unknown or repeated id, max_label not finite, topn[k] <= 0, n_topn
- * outside 1 .. 16.  ULTR_E_UNSUPPORTED: list_size beyond 64 KiB of LDS with one more array per list (every list_size <= 800 fits). */
+ * outside 1 .. 16.  A list whose five arrays fit 64 KiB of LDS four lists at a time (list_size <= 813) takes the kernel of one wave per
+ * list; a longer one takes the long-list kernel - one workgroup of 16 waves per list, its arrays in up to 160 KiB of LDS, the same
+ * contract - up to ultr_metrics_max_list() documents.  ULTR_E_UNSUPPORTED: list_size beyond that. */
 #define ULTR_METRIC_NDCG 0
 #define ULTR_METRIC_DCG 1
 #define ULTR_METRIC_MRR 2
@@ -451,7 +453,18 @@ int ultr_metrics_report(const float* scores, const float* labels, const int32_t*
                         int32_t list_size, const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics,
                         float max_label, float* out /*[n_metrics][n_topn]*/, int32_t* order_out, float* masked_out,
                         float* ws /*[batch][n_metrics][n_topn]*/, uint32_t* counter, float* host_report, uint32_t seq, void* stream);
-/* validation() with those metrics as ONE host call: ultr_dnn_forward (saved = NULL), then ultr_metrics_report of its scores. */
+/* ABI 8 (additive): ultr_metrics_report with the long-list kernel at EVERY list_size from 1 to ultr_metrics_max_list() - the same
+ * arguments, errors and results; where ultr_metrics_report takes its one-wave kernel the two agree bit for bit (the ranks and the pair
+ * count are integers, the float sums run in one wave in the same order). */
+int ultr_metrics_long(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,
+                      int32_t list_size, const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics,
+                      float max_label, float* out /*[n_metrics][n_topn]*/, int32_t* order_out, float* masked_out,
+                      float* ws /*[batch][n_metrics][n_topn]*/, uint32_t* counter, float* host_report, uint32_t seq, void* stream);
+/* The longest list ultr_metrics_report / ultr_metrics_long take: what 160 KiB of LDS hold of five float arrays and a validity bit per
+ * document (host only, no launch). */
+int32_t ultr_metrics_max_list(void);
+/* validation() with those metrics as ONE host call: ultr_dnn_forward (saved = NULL), then ultr_metrics_report of its scores (lists up to
+ * ultr_metrics_max_list(), as there). */
 int ultr_dnn_forward_metrics(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features, int64_t n_docs,
                              const int32_t* docids, const float* labels, int32_t batch, int32_t list_size, float* scores,
                              const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics, float max_label,
@@ -723,6 +736,7 @@ int ultr_history_pw(const ultr_history_pw_args* a, void* stream);
  *                         may be NULL): every chunk's scores / per-list metric values written straight to their offset; otherwise
  *                         they go to scores_ws [batch, L] / ws and only the last chunk's remain.  The launches of a chunk are exactly
  *                         the ones validation() issues for that batch: the merged figures are the per-batch loop's, bit for bit.
+ *                         list_size up to ultr_metrics_max_list(), as ultr_metrics_report (ULTR_E_UNSUPPORTED beyond).
  *                         Does not synchronise, does not allocate, stops at the first non-zero return. */
 #define ULTR_EVAL_RESET 1
 #define ULTR_EVAL_FINISH 2

@@ -184,6 +184,9 @@ SIGNATURES = {
                                       c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint32, c_vp]),
     "ultr_metrics_report": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_i32), c_i32,
                                     ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint32, c_vp]),
+    "ultr_metrics_long": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_i32), c_i32,
+                                  ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint32, c_vp]),
+    "ultr_metrics_max_list": (c_i32, []),
     "ultr_dnn_forward_metrics": (c_i32, [ctypes.POINTER(DnnDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp,
                                          ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_i32), c_i32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp,
                                          c_vp, c_vp, ctypes.c_uint32, c_vp]),

@@ -6,6 +6,7 @@
 // One wavefront per list; the descending sort is rank-by-counting from LDS (stable: ties keep index order,
 // which is what torch's CPU sort yields for the all-equal padding scores).  A NaN score ranks above every number, as in torch's
 // descending sort, and a NaN in a list becomes the row minimum that its invalid labels take, as torch.min does.
+// Lists beyond the 64 KiB of LDS that four such lists share (813 documents) take metrics_long_kernel: one workgroup of 16 waves per list.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,6 +52,28 @@ struct MetricSel {
 static size_t ndcg_lds_bytes(int L, bool all) {
   return all ? ((size_t)NDCG_LPW * 5 * L + (size_t)NDCG_LPW * 2 * ((L + 63) / 64) + 4) * sizeof(float)
              : ((size_t)NDCG_LPW * 4 * L + 4) * sizeof(float);
+}
+
+// ultr_metrics_report's batch means, by the ONE wave that arrived last at tail.counter: lanes stride the lists, fixed-order wave reduction
+// per value; then the counter is reset and, with a host report, the values and after them the sequence word go to host-mapped memory
+__device__ __forceinline__ void metrics_means(const float* __restrict__ per_list, int B, int width, int lane, const NdcgTail& tail) {
+  const Src pl = make_src(per_list, (int64_t)B * width);
+  for (int w = 0; w < width; ++w) {
+    float s = 0.f;
+    for (int bb = lane; bb < B; bb += 64) s += coh_ld1(pl, (unsigned)(((int64_t)bb * width + w) * 4));  // served from the coherence point
+    s = wave_sum(s) / (float)B;
+    if (lane == 0) {
+      tail.out[w] = s;
+      if (tail.host != nullptr) __hip_atomic_store(tail.host + w, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+  if (lane == 0) {
+    __hip_atomic_store(tail.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch on this stream
+    if (tail.host != nullptr) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store(reinterpret_cast<uint32_t*>(tail.host) + METRICS_SEQ_WORD, tail.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
 }
 
 // ALL = false: NDCG@topn (ultr_ndcg, ultr_ndcg_report).  ALL = true: the same ranking, the same NDCG arithmetic, and the other metrics
@@ -237,23 +260,7 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
   old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
   if (old + (unsigned)lists_here != (unsigned)B) return;
   if constexpr (ALL) {
-    const Src pl = make_src(per_list, (int64_t)B * width);
-    for (int w = 0; w < width; ++w) {
-      float s = 0.f;
-      for (int bb = lane; bb < B; bb += 64) s += coh_ld1(pl, (unsigned)(((int64_t)bb * width + w) * 4));  // served from the coherence point
-      s = wave_sum(s) / (float)B;
-      if (lane == 0) {
-        tail.out[w] = s;
-        if (tail.host != nullptr) __hip_atomic_store(tail.host + w, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-    if (lane == 0) {
-      __hip_atomic_store(tail.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch on this stream
-      if (tail.host != nullptr) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(reinterpret_cast<uint32_t*>(tail.host) + METRICS_SEQ_WORD, tail.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
+    metrics_means(per_list, B, width, lane, tail);
     return;
   }
   const Src pl = make_src(per_list, (int64_t)B * topn.n);
@@ -273,6 +280,202 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
       __hip_atomic_store(reinterpret_cast<uint32_t*>(tail.host) + NDCG_MAX_TOPN, tail.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
+}
+
+// ---- lists beyond the 64 KiB that four single-wave lists share: ONE workgroup of METRICS_LONG_WAVES waves per list, that list's arrays
+// in up to the whole 160 KiB of LDS.  ndcg_list_kernel<true>'s contract and, wherever both take a list, its bits: the row minimum is a
+// min (no order), the ranks and the pair count are integers, and every float sum is formed by wave 0 alone in that kernel's loop order.
+#define METRICS_LONG_WAVES 16
+#define METRICS_LONG_THREADS (METRICS_LONG_WAVES * 64)
+#define METRICS_LDS_MAX (160 * 1024)
+
+// LDS bytes of a workgroup: five [L rounded up to 4] float arrays (the counting loop reads 16 bytes at a time), one validity bit per
+// document, and per wave the minimum, the NaN flag and the pair count
+static constexpr size_t metrics_long_lds_bytes(int L) {
+  return ((size_t)5 * ((L + 3) & ~3) + (size_t)2 * ((L + 63) / 64) + 3 * METRICS_LONG_WAVES) * sizeof(float);
+}
+// THE length bound of the metric launch (ultr_metrics_max_list): the longest list whose arrays fit 160 KiB
+static constexpr int metrics_long_max_list() {
+  int L = METRICS_LDS_MAX / (5 * (int)sizeof(float));
+  while (metrics_long_lds_bytes(L) > METRICS_LDS_MAX) --L;
+  return L;
+}
+static_assert(metrics_long_max_list() >= 4096, "the long metric kernel takes every list up to 4096 documents");
+
+__global__ __launch_bounds__(METRICS_LONG_THREADS) void metrics_long_kernel(const float* __restrict__ scores, const float* __restrict__ labels,
+                                                                            const int32_t* __restrict__ docids, int64_t n_docs, int B, int L,
+                                                                            TopN topn, float* __restrict__ per_list,
+                                                                            int32_t* __restrict__ order_out, float* __restrict__ masked_out,
+                                                                            NdcgTail tail, MetricSel sel) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int Lp = (L + 3) & ~3;
+  float* ms = smem;     // [Lp] masked + validated predictions (then their order keys, then the ERR terms by rank)
+  float* my = ms + Lp;  // [Lp] validated labels
+  float* md = my + Lp;  // [Lp] discounted gains by predicted rank
+  float* mi = md + Lp;  // [Lp] discounted gains by ideal rank
+  float* ml = mi + Lp;  // [Lp] validated labels by predicted rank
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x;
+  const int nch = (L + 63) >> 6;
+  unsigned long long* mv = reinterpret_cast<unsigned long long*>(ml + Lp);  // [nch] 64-bit masks of the documents whose label was valid
+  float* w_min = reinterpret_cast<float*>(mv + nch);                        // [waves] each wave's minimum
+  int* w_nan = reinterpret_cast<int*>(w_min + METRICS_LONG_WAVES);          // [waves] whether it saw a NaN
+  int* w_opa = w_nan + METRICS_LONG_WAVES;                                  // [waves] its correctly ordered pairs
+  // pad mask, row minimum (ndcg_list_kernel's first loop, all waves striding the list)
+  float mn = INFINITY;
+  bool nan_seen = false;
+  for (int l = tid; l < L; l += METRICS_LONG_THREADS) {
+    float s = scores[(int64_t)b * L + l];
+    const float y = labels[(int64_t)l * B + b];
+    if (docids != nullptr && (int64_t)docids[(int64_t)l * B + b] == n_docs) s = ULTR_PAD_SCORE;
+    if (masked_out != nullptr) masked_out[(int64_t)b * L + l] = s;
+    ms[l] = s;
+    my[l] = y;
+    mn = fminf(mn, s);
+    nan_seen = nan_seen || s != s;
+  }
+  mn = -wave_max(-mn);
+  const unsigned long long nan_lanes = __ballot(nan_seen);
+  if (lane == 0) {
+    w_min[wave] = mn;
+    w_nan[wave] = nan_lanes != 0 ? 1 : 0;
+  }
+  __syncthreads();
+  int any_nan = 0;
+#pragma unroll
+  for (int w = 0; w < METRICS_LONG_WAVES; ++w) {
+    mn = fminf(mn, w_min[w]);
+    any_nan |= w_nan[w];
+  }
+  if (any_nan != 0) mn = __builtin_nanf("");  // torch.min propagates a NaN (fminf drops it)
+  // label validation, a 64-document chunk per wave at a time
+  unsigned* mk = reinterpret_cast<unsigned*>(ms);  // the validated predictions, from here on as order keys (score_key)
+  for (int c = wave; c < nch; c += METRICS_LONG_WAVES) {
+    const int l = c * 64 + lane;
+    bool ok = false;
+    if (l < L) {
+      const float y = my[l];
+      ok = y >= 0.f;
+      my[l] = ok ? y : 0.f;
+      mk[l] = score_key(ok ? ms[l] : -1e-6f + mn);
+    }
+    const unsigned long long okm = __ballot(ok);
+    if (lane == 0) mv[c] = okm;
+  }
+  __syncthreads();
+  // rank by counting: document i of a thread against every j, four j per 16-byte LDS read (one address per wave: a broadcast)
+  int opa = 0;
+  const int L4 = L & ~3;
+  for (int i = tid; i < L; i += METRICS_LONG_THREADS) {
+    const unsigned ki = mk[i];
+    const float yi = my[i];
+    int rs = 0, ry = 0, pairs = 0;
+    unsigned long long vj = 0;
+    auto count = [&](int j, unsigned kj, float yj) {
+      rs += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
+      ry += (yj > yi || (yj == yi && j < i)) ? 1 : 0;
+      pairs += (yi > yj && ki > kj && ((vj >> (j & 63)) & 1ull)) ? 1 : 0;  // ordered_pair_accuracy, as ndcg_list_kernel counts it
+    };
+    for (int j = 0; j < L4; j += 4) {
+      const uint4 k4 = *reinterpret_cast<const uint4*>(mk + j);
+      const float4 y4 = *reinterpret_cast<const float4*>(my + j);
+      if ((j & 63) == 0) vj = mv[j >> 6];
+      count(j, k4.x, y4.x);
+      count(j + 1, k4.y, y4.y);
+      count(j + 2, k4.z, y4.z);
+      count(j + 3, k4.w, y4.w);
+    }
+    for (int j = L4; j < L; ++j) {
+      if ((j & 63) == 0) vj = mv[j >> 6];
+      count(j, mk[j], my[j]);
+    }
+    if (((mv[i >> 6] >> (i & 63)) & 1ull) && ki != 0xFFFFFFFFu) opa += pairs;
+    ml[rs] = yi;
+    const float gain = exp2f(yi) - 1.0f;  // weights = 1: gains = 2^label - 1 (metrics.py:213)
+    md[rs] = gain * (1.0f / log2f((float)rs + 2.0f));
+    mi[ry] = gain * (1.0f / log2f((float)ry + 2.0f));
+    if (order_out != nullptr) order_out[(int64_t)b * L + rs] = i;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) opa += __shfl_xor(opa, d);
+  if (lane == 0) w_opa[wave] = opa;
+  __syncthreads();  // the last barrier: every wave is still here
+  if (wave != 0) return;
+  // ---- wave 0 alone: ndcg_list_kernel<true>'s scans and sums over the ranked arrays, statement for statement -------------------------
+  int opa_all = 0;  // an integer up to L * L / 2 < 2^31, converted once
+#pragma unroll
+  for (int w = 0; w < METRICS_LONG_WAVES; ++w) opa_all += w_opa[w];
+  float whole[ULTR_MAX_METRICS] = {};
+  float* me = ms;  // the ERR terms by rank (over the order keys, which nothing reads any more)
+  {
+    float carry = 1.f, ap = 0.f, pos_sum = 0.f, lab_sum = 0.f;
+    int hits = 0, first = L;
+    for (int r0 = 0; r0 < L; r0 += 64) {
+      const int r = r0 + lane;
+      const float y = r < L ? ml[r] : 0.f;
+      const bool hit = r < L && y >= 1.f;
+      const float rel = (exp2f(y) - 1.0f) / sel.pow_max;
+      float p = 1.0f - rel;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const float t = __shfl_up(p, d);
+        if (lane >= d) p *= t;
+      }
+      float excl = __shfl_up(p, 1);
+      if (lane == 0) excl = 1.f;
+      excl *= carry;
+      carry *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), 63));
+      if (r < L) me[r] = rel * excl * (1.0f / (float)(r + 1));
+      const unsigned long long hm = __ballot(hit);
+      if (hit) ap += (float)(hits + __popcll(hm & ((2ull << lane) - 1ull))) / (float)(r + 1);
+      if (first == L && hm != 0) first = r0 + __ffsll((long long)hm) - 1;
+      hits += __popcll(hm);
+      pos_sum += (float)(r + 1) * y;
+      lab_sum += y;
+    }
+    float sums[4] = {ap, pos_sum, lab_sum, lane == 0 ? (float)opa_all : 0.f};
+    wave_sum_n<4>(sums);
+    whole[ULTR_METRIC_MRR] = first < L ? 1.0f / (float)(first + 1) : 0.f;
+    whole[ULTR_METRIC_MAP] = hits > 0 ? sums[0] / (float)hits : 0.f;
+    whole[ULTR_METRIC_ARP] = sums[2] == 0.f ? 0.f : sums[1] / sums[2];  // _safe_div
+    whole[ULTR_METRIC_PRECISION] = (float)hits / (float)L;
+    whole[ULTR_METRIC_OPA] = sums[3] / ((float)L * (float)L);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  const int width = sel.n * topn.n;
+  for (int k = 0; k < topn.n; ++k) {
+    const int n = topn.v[k] < L ? topn.v[k] : L;  // topn clipped to the list size (metrics.py:249)
+    float d = 0.f, id = 0.f, e = 0.f;
+    for (int r = lane; r < n; r += 64) {
+      d += md[r];
+      id += mi[r];
+      e += me[r];
+    }
+    d = wave_sum(d);
+    id = wave_sum(id);
+    e = wave_sum(e);
+    if (lane == 0) {
+      whole[ULTR_METRIC_NDCG] = (id == 0.f) ? 0.f : d / id;  // _safe_div
+      whole[ULTR_METRIC_DCG] = d;
+      whole[ULTR_METRIC_ERR] = e;
+      const Src pl = make_src(per_list, (int64_t)B * width);
+      for (int m = 0; m < sel.n; ++m) {
+        float x = 0.f;
+#pragma unroll
+        for (int q = 0; q < ULTR_MAX_METRICS; ++q) x = sel.id[m] == q ? whole[q] : x;  // (registers: no indexed private array)
+        coh_st1(pl, (unsigned)(((int64_t)b * width + m * topn.n + k) * 4), x);
+      }
+    }
+  }
+  // the list that arrives last forms the batch means (no workgroup waits for another)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  unsigned old = 0;
+  if (lane == 0) old = __hip_atomic_fetch_add(tail.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
+  if (old + 1u != (unsigned)B) return;
+  metrics_means(per_list, B, width, lane, tail);
 }
 
 __global__ void ndcg_mean_kernel(const float* __restrict__ per_list, int B, int n_topn, float* __restrict__ out) {
@@ -333,11 +536,13 @@ extern "C" int ultr_ndcg_report(const float* scores, const float* labels, const 
   return (int)hipGetLastError();
 }
 
-// ONE launch for any of the eight metrics of utils/metrics.py: out [n_metrics][n_topn] in the order of metric_ids (include/ultr_hip.h)
-extern "C" int ultr_metrics_report(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,
-                                   int32_t list_size, const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics,
-                                   float max_label, float* out, int32_t* order_out, float* masked_out, float* ws, uint32_t* counter,
-                                   float* host_report, uint32_t seq, void* stream) {
+// ONE launch for any of the eight metrics of utils/metrics.py: out [n_metrics][n_topn] in the order of metric_ids (include/ultr_hip.h).
+// long_only: metrics_long_kernel at every list size (ultr_metrics_long); otherwise ndcg_list_kernel<true> wherever its LDS fits - the
+// routing threshold of ultr_metrics_report - and metrics_long_kernel above
+static int metrics_launch(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch, int32_t list_size,
+                          const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics, float max_label, float* out,
+                          int32_t* order_out, float* masked_out, float* ws, uint32_t* counter, float* host_report, uint32_t seq, void* stream,
+                          bool long_only) {
   if (!scores || !labels || !topn || !metric_ids || !out || !ws || !counter || batch <= 0 || list_size <= 0 || n_topn <= 0 ||
       n_topn > NDCG_MAX_TOPN || n_metrics <= 0 || n_metrics > ULTR_MAX_METRICS || !(fabsf(max_label) < INFINITY))
     return ULTR_E_BADARG;
@@ -357,12 +562,40 @@ extern "C" int ultr_metrics_report(const float* scores, const float* labels, con
     seen |= 1u << id;
     sel.id[m] = id;
   }
-  const size_t lds = ndcg_lds_bytes(list_size, true);
   // (the per-list block is addressed with 32-bit byte offsets through a buffer descriptor)
-  if (lds > 64 * 1024 || (int64_t)batch * n_metrics * n_topn * 4 > INT32_MAX) return ULTR_E_UNSUPPORTED;
+  if (list_size > metrics_long_max_list() || (int64_t)batch * n_metrics * n_topn * 4 > INT32_MAX) return ULTR_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
+  const size_t lds = ndcg_lds_bytes(list_size, true);
+  if (!long_only && lds <= 64 * 1024) {
+    UltrProfScope prof(ULTR_K_NDCG, st);
+    ULTR_LAUNCH(prof, ndcg_list_kernel<true>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
+                n_docs, (int)batch, (int)list_size, t, ws, order_out, masked_out, NdcgTail{counter, out, host_report, seq}, sel);
+    return (int)hipGetLastError();
+  }
+  const size_t lds_long = metrics_long_lds_bytes(list_size);
+  if (lds_long > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(metrics_long_kernel),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_long) != hipSuccess)
+    return ULTR_E_UNSUPPORTED;
   UltrProfScope prof(ULTR_K_NDCG, st);
-  ULTR_LAUNCH(prof, ndcg_list_kernel<true>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
-              n_docs, (int)batch, (int)list_size, t, ws, order_out, masked_out, NdcgTail{counter, out, host_report, seq}, sel);
+  ULTR_LAUNCH(prof, metrics_long_kernel, dim3((unsigned)batch), dim3(METRICS_LONG_THREADS), lds_long, st, scores, labels, docids, n_docs,
+              (int)batch, (int)list_size, t, ws, order_out, masked_out, NdcgTail{counter, out, host_report, seq}, sel);
   return (int)hipGetLastError();
 }
+
+extern "C" int ultr_metrics_report(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,
+                                   int32_t list_size, const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics,
+                                   float max_label, float* out, int32_t* order_out, float* masked_out, float* ws, uint32_t* counter,
+                                   float* host_report, uint32_t seq, void* stream) {
+  return metrics_launch(scores, labels, docids, n_docs, batch, list_size, topn, n_topn, metric_ids, n_metrics, max_label, out, order_out,
+                        masked_out, ws, counter, host_report, seq, stream, false);
+}
+
+extern "C" int ultr_metrics_long(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,
+                                 int32_t list_size, const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics,
+                                 float max_label, float* out, int32_t* order_out, float* masked_out, float* ws, uint32_t* counter,
+                                 float* host_report, uint32_t seq, void* stream) {
+  return metrics_launch(scores, labels, docids, n_docs, batch, list_size, topn, n_topn, metric_ids, n_metrics, max_label, out, order_out,
+                        masked_out, ws, counter, host_report, seq, stream, true);
+}
+
+extern "C" int32_t ultr_metrics_max_list(void) { return metrics_long_max_list(); }

@@ -334,10 +334,21 @@ METRIC_IDS = {"ndcg": 0, "dcg": 1, "mrr": 2, "err": 3, "map": 4, "arp": 5, "prec
 _METRICS_SEQ_WORD = 8 * 16  # ultr_metrics_report's sequence word in the host report (ultr_ndcg_report's is 16)
 
 
-def metrics_fit(list_size):
-    """Whether ultr_metrics_report takes this list size (csrc/ultr_metrics.hip ndcg_lds_bytes: 64 KiB of LDS for four lists)."""
+def metrics_fit_short(list_size):
+    """Whether the metric launch's kernel of one wave per list takes this list size (csrc/ultr_metrics.hip ndcg_lds_bytes: 64 KiB of LDS
+    for four lists) - the routing threshold of ultr_metrics_report, 813 documents."""
     L = int(list_size)
     return (4 * 5 * L + 4 * 2 * ((L + 63) // 64) + 4) * 4 <= 64 * 1024
+
+
+def ndcg_fit(list_size):
+    """Whether ultr_ndcg_report / ultr_dnn_forward_ndcg take this list size (four arrays per list: 1023 documents)."""
+    return (4 * 4 * int(list_size) + 4) * 4 <= 64 * 1024
+
+
+def metrics_fit(list_size):
+    """Whether the metric launch (ultr_metrics_report) takes this list size, with either of its kernels: up to ultr_metrics_max_list()."""
+    return 1 <= int(list_size) <= int(_lib.load().ultr_metrics_max_list())
 
 
 class EvalEngine:
@@ -364,7 +375,8 @@ class EvalEngine:
         self._topn_arr = (ctypes.c_int32 * len(self.topn))(*self.topn)
         self._lib = shape.lib
         self.metrics = tuple(metrics)
-        self._all = self.metrics != ("ndcg",)
+        # ("ndcg",) beyond the NDCG launch's 1023 documents: the metric launch with the one id (the same arithmetic in the same order)
+        self._all = self.metrics != ("ndcg",) or not ndcg_fit(self.L)
         if self._all:
             unknown = [m for m in self.metrics if m not in METRIC_IDS]
             if unknown or len(set(self.metrics)) != len(self.metrics) or not self.metrics:
@@ -420,6 +432,11 @@ class EvalEngine:
                    "ultr_dnn_forward_ndcg")
         return self.scores, self.ndcg
 
+    def forward(self, params, features, n_docs, docids):
+        """The forward alone into self.scores - for a list no metric launch takes (validation() then computes on the host)."""
+        hip_ops.dnn_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores)
+        return self.scores
+
     def read_ndcg(self, timeout_s=60.0):
         """NDCG@topn of the LAST run() as a numpy array - the reference's `.item()` per metric (ipw_rank.py:204-210) without a stream
         synchronisation: waits for the launch's report in host-mapped memory."""
@@ -469,7 +486,7 @@ class EvalSetEngine:
         if unknown or len(set(self.metrics)) != len(self.metrics) or not self.metrics:
             raise ValueError("metrics must be distinct keys of %s, got %r" % (sorted(METRIC_IDS), self.metrics))
         if not metrics_fit(self.L):
-            raise ValueError("list size %d is beyond the metric launch's LDS budget (engine.metrics_fit)" % self.L)
+            raise ValueError("list size %d is beyond the metric launch's bound (engine.metrics_fit)" % self.L)
         self._lib = shape.lib
         B, L, nm, nt = self.B, self.L, len(self.metrics), len(self.topn)
         self.n_values = nm * nt
@@ -665,6 +682,11 @@ class SetRankEvalEngine(EvalEngine):
             hip_ops.setrank_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.saved)
         self._ndcg(labels, docids, n_docs)
         return self.scores, self.ndcg
+
+    def forward(self, params, features, n_docs, docids):
+        _setrank_draw(self.L)
+        hip_ops.setrank_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.saved)
+        return self.scores
 
 
 class DbgdEngine:

@@ -185,6 +185,12 @@ class BaseAlgorithm(object):
             raise NotImplementedError("loss_func=%r raises in the reference too (base_algorithm.py:267,307)" % lf)
 
     # ---- validation (a12/a13: e.g. ipw_rank.py:184-211) ----------------------------------------------
+    def _labels_BL_host(self, labels_host):
+        """This batch's labels [B, L] as a CPU tensor, for utils.metrics on the host."""
+        if labels_host is None:  # device feed: the labels live in HBM
+            return self.labels_LB.t().contiguous().cpu()
+        return torch.from_numpy(np.ascontiguousarray(labels_host.T.astype(np.float32)))
+
     def validation(self, input_feed, is_online_simulation=False):
         if self.model.training:
             self.model.eval()
@@ -192,11 +198,13 @@ class BaseAlgorithm(object):
         labels_host = self.create_input_feed(input_feed, L)
         B = self.batch_size
         topn = [int(t) for t in self.exp_settings["metrics_topn"]]
-        # every key of utils.metrics' table comes out of the ONE metric launch (ultr_metrics_report).  What that launch does not take -
-        # a list beyond its LDS budget, a key outside the table - keeps the NDCG launch + utils.metrics on the host, as does
-        # ["ndcg"] alone (and online simulation, which reads no metric)
+        # every key of utils.metrics' table comes out of the ONE metric launch (ultr_metrics_report: lists up to engine.metrics_fit, its
+        # long-list kernel beyond 813 documents).  A key outside the table keeps the NDCG launch (beyond its 1023 documents the metric
+        # launch with the one id) + utils.metrics on the host, as does ["ndcg"] alone (and online simulation, which reads no metric);
+        # a list beyond the metric launch's bound runs the forward alone and computes every key on the host
         wanted = tuple(dict.fromkeys(self.exp_settings["metrics"]))
-        on_device = (not is_online_simulation and wanted != ("ndcg",) and len(wanted) > 0 and engine.metrics_fit(L)
+        fits = engine.metrics_fit(L)
+        on_device = (not is_online_simulation and wanted != ("ndcg",) and len(wanted) > 0 and fits
                      and all(m in engine.METRIC_IDS for m in wanted))
         names = wanted if on_device else ("ndcg",)
         key = (B, L, tuple(topn), names)
@@ -208,6 +216,19 @@ class BaseAlgorithm(object):
         else:
             self._eval_engines.move_to_end(key)
         ev = self._eval_engines[key]
+        if not fits:
+            scores = ev.forward(self.model.flat_params, self.letor_features, self.n_docs, self.docid_inputs)
+            self.output = scores.clone()
+            if not is_online_simulation:
+                # one copy each of the scores, the doc ids and (device feed) the labels; remove_padding_for_metric_eval on the host
+                pad = self.docid_inputs.t().cpu() == self.n_docs
+                masked = torch.where(pad, torch.full((), float(self.PADDING_SCORE)), self.output.cpu())
+                lab_BL = self._labels_BL_host(labels_host)
+                for metric in self.exp_settings["metrics"]:
+                    values = metrics_mod.make_ranking_metric_fn(metric, topn)(lab_BL, masked, None)
+                    for n, v in zip(topn, values):
+                        self.eval_summary["%s_%d" % (metric, n)] = float(v)
+            return None, self.output, self.eval_summary
         scores, ndcg = ev.run(self.model.flat_params, self.letor_features, self.n_docs, self.docid_inputs, self.labels_LB)
         self.output = scores.clone()  # the UNMASKED scores are what callers get (base_algorithm.py / main.py:266)
         if on_device:
@@ -223,10 +244,7 @@ class BaseAlgorithm(object):
                 else:
                     if masked is None:
                         masked = ev.masked.cpu()
-                        if labels_host is None:  # device feed: the labels live in HBM
-                            lab_BL = self.labels_LB.t().contiguous().cpu()
-                        else:
-                            lab_BL = torch.from_numpy(np.ascontiguousarray(labels_host.T.astype(np.float32)))
+                        lab_BL = self._labels_BL_host(labels_host)
                     values = metrics_mod.make_ranking_metric_fn(metric, topn)(lab_BL, masked, None)
                 for n, v in zip(topn, values):
                     self.eval_summary["%s_%d" % (metric, n)] = float(v)
@@ -241,7 +259,8 @@ class BaseAlgorithm(object):
 
         With a feed that keeps the dataset in HBM (input_layer.DeviceDirectLabelFeed) the set is queued from one call
         (engine.EvalSetEngine): per batch the launches validation() issues, the merge in double on the device, ONE host read - the same
-        figures, bit for bit.  A list beyond the metric launch's LDS budget (engine.metrics_fit), a metric key outside
+        figures, bit for bit, at every list the metric launch takes (engine.metrics_fit: ultr_metrics_max_list() documents, the
+        long-list kernel beyond 813).  A list beyond that bound, a metric key outside
         engine.METRIC_IDS or any other feed keep the per-batch loop over feed.get_next_batch + validation() (per_query is None there)."""
         if self.model.training:
             self.model.eval()

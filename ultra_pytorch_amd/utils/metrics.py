@@ -2,8 +2,8 @@
 
 validation() computes every metric of this table on the GPU, in its one metric launch (ultr_metrics_report, csrc/ultr_metrics.hip).
 This module is the reference's factory interface for callers that hold host tensors, and validation()'s path for a list longer than
-that launch takes (engine.metrics_fit).  weights=None semantics only (what every validation() call passes).  Pinned to the
-reference's own outputs: tests/golden/metrics_host.npz.
+that launch takes (engine.metrics_fit: ultr_metrics_max_list() documents).  weights=None semantics only (what every validation() call
+passes).  Pinned to the reference's own outputs: tests/golden/metrics_host.npz.
 Two places where this module is usable and the reference is not: `dcg` (the reference's raises: it gathers a `weights` of None,
 metrics.py:519-523 -> :191-221) and `precision` (the reference returns ONE scalar whatever topn is, metrics.py:373-405, which
 validation()'s zip over metrics_topn cannot iterate; here the same value is repeated per cut-off).
