@@ -239,17 +239,23 @@ int ultr_pdgd_loss(const float* scores, const float* labels, const int32_t* doci
  * params: flat vector in SetRank.state_dict() order (Encoder_layer.input_layer_norm, input_embedding.{0,2},
  * output_layer.{0,2}, then per encoder: mha.dense, ffn.{0,2}, layernorm1, layernorm2).
  * forward: scores [B, L]; `saved` (ultr_setrank_saved_bytes) receives every activation the backward needs and is
- * required for validation too (it doubles as scratch).  list_size <= 256.
+ * required for validation too (it doubles as scratch).  Any list_size: up to 256 documents the one-pass attention kernels run,
+ * beyond them (ULTR_SR_ATTN_LONG_MIN, default 257, lowers the hand-over) the keys stream through LDS in tiles with a running row
+ * maximum and sum (fp32 matrix cores at head depth 16 / 32 / 64, a scalar kernel at every other up to 420: its rows sit in LDS,
+ * as the one-pass scalar kernel's do - beyond, ULTR_E_UNSUPPORTED before anything is launched); what bounds the forward is
+ * batch * list_size <= 0x7fffffff / 4 and the size of `saved`.
  * backward: dscores [B, L] from any ultr_*_loss kernel (x D convention), loss_ws/n_loss_parts = that kernel's
  * partials; writes grads [P + step tail]; follow with ultr_grad_sumsq + ultr_apply_update(wt = NULL).
- * list_size <= 128 on the matrix-core attention path (head depth 16 / 32 / 64), <= 120 otherwise. */
+ * list_size <= 128 on the matrix-core attention path (head depth 16 / 32 / 64), <= 120 otherwise: there is no streaming
+ * attention backward, so a forward at a longer list is an evaluation (ULTR_E_UNSUPPORTED from the backward). */
 enum ultr_attention_dtype { ULTR_ATTN_FP32 = 0, ULTR_ATTN_FP16 = 1 };
 typedef struct ultr_setrank_desc {
   int32_t feature_size, d_model, num_heads, num_layers, dff;
   /* operand type of the self-attention products (ABI 2).  ULTR_ATTN_FP32 (default): exact fp32 matrix cores, the 1e-5
    * parity path.  ULTR_ATTN_FP16: fp16 operands with fp32 accumulation on v_mfma_f32_16x16x32_f16 (what BASELINE
    * config 5 names); scores / softmax / gradients algebra stay fp32; parity is ORDERING-level (~1e-3 relative), so it is
-   * opt-in.  Needs head depth 32 or 64 and list_size <= 128, otherwise the fp32 kernels run. */
+   * opt-in.  Needs head depth 32 or 64 and list_size <= 128, otherwise the fp32 kernels run (the streaming kernels of the long
+   * lists are fp32 only: ULTR_ATTN_FP16 at list_size 300 runs them). */
   int32_t attention_dtype;
   int32_t flags;  /* ABI 6: ULTR_MODEL_FP32_PRODUCTS - the Linear products and d x d weight gradients of this model on the fp32 matrix cores */
 } ultr_setrank_desc;
@@ -264,6 +270,19 @@ int ultr_setrank_forward(const ultr_setrank_desc* c, const float* params, const 
 int ultr_setrank_backward(const ultr_setrank_desc* c, const float* params, int32_t batch, int32_t list_size, const void* saved,
                           const float* dscores, const void* loss_ws, int32_t n_loss_parts, void* workspace, float* grads,
                           void* stream);
+/* Which attention kernel family a shape takes (additive within ABI 8; host-only, launches nothing): the value of THE dispatch the
+ * forward (backward = 0) / the backward (backward = 1; the split-half knobs as for layer 0) goes through at list_size, under the knobs
+ * as last read (ultr_config_reload), or ULTR_E_UNSUPPORTED where the call itself would refuse; ULTR_E_BADARG on a bad desc. */
+enum ultr_setrank_attn_path_id {
+  ULTR_SR_ATTN_SCALAR = 0,       /* one wave per query row, the head slice in LDS */
+  ULTR_SR_ATTN_MFMA = 1,         /* fp32 matrix cores, the score row in registers (list_size <= 128) */
+  ULTR_SR_ATTN_F16 = 2,          /* fp16 operands (ULTR_ATTN_FP16) */
+  ULTR_SR_ATTN_SPLIT_HALF = 3,   /* hi / lo fp16 operands (backward only) */
+  ULTR_SR_ATTN_LONG_MFMA = 4,    /* keys streamed in tiles, fp32 matrix cores (forward only) */
+  ULTR_SR_ATTN_LONG_SCALAR = 5   /* keys streamed in tiles, scalar (forward only) */
+};
+int32_t ultr_setrank_attn_path(const ultr_setrank_desc* c, int32_t list_size, int32_t backward);
+
 /* SetRank's dropout.  Replaces the nn.Dropout(rate) calls of EncoderLayer.forward and Encoder.forward (ranking_model/SetRank.py:103-117,
  * 141-153) at 1 + 2 num_layers sites: 0 behind input_embedding, 1 + 2 l behind encoder l's mha.dense, 2 + 2 l behind its ffn - each on
  * the Linear's output with its bias, before the residual is added; the output FFN has none.

@@ -93,6 +93,10 @@ class SetRankDesc(ctypes.Structure):
                 ("attention_dtype", c_i32), ("flags", c_i32)]
 
 
+# include/ultr_hip.h: ultr_setrank_attn_path_id - the attention kernel family a shape takes (ultr_setrank_attn_path)
+SR_ATTN_PATHS = ("scalar", "mfma", "f16", "split_half", "long_mfma", "long_scalar")
+
+
 class SetRankDropout(ctypes.Structure):  # ultr_setrank_dropout
     _fields_ = [("rate", c_f32), ("seed", ctypes.c_uint64), ("step", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("scratch", c_vp),
                 ("scratch_bytes", c_i64)]
@@ -145,6 +149,7 @@ SIGNATURES = {
     "ultr_setrank_forward": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_setrank_backward": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
                                       c_vp]),
+    "ultr_setrank_attn_path": (c_i32, [ctypes.POINTER(SetRankDesc), c_i32, c_i32]),
     "ultr_setrank_dropout_workspace_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
     "ultr_setrank_forward_dropout": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp,
                                              ctypes.POINTER(SetRankDropout), c_vp]),

@@ -1064,6 +1064,8 @@ struct SrKnobs {
   int wg_h3;      // ULTR_SR_WG_H3 (default 1): square-ish weight gradients on the DNN's split-half weight-gradient kernel
   int bwd_fused;  // ULTR_SR_BWD_FUSED bits (default 7 = all): 1 the row-local chain of a block's backward as two launches (ultr_sr_bwd.hip)
                   // instead of seven, 2 the output FFN's backward as one instead of three, 4 the embedding FFN's
+  int attn_long_min;  // ULTR_SR_ATTN_LONG_MIN (default 257): the forward's attention streams its keys (ultr_sr_attn_long.hip) from this list size on;
+                      // tests and measurement only - it lowers the hand-over point, beyond 256 documents the keys are streamed whatever it says
   int block;      // ULTR_SR_BLOCK 0: off; 1: one 16-wave workgroup per CU; 2: two 8-wave workgroups per CU; 3 (default): the persistent kernel of round 6 where its widths apply, 2 elsewhere
 };
 SrKnobs g_knobs = {};
@@ -1075,6 +1077,7 @@ void sr_knobs_load() {
   k.attn_mask = num(getenv("ULTR_SR_ATTN_H3_MASK"), -1);
   k.wg_h3 = num(getenv("ULTR_SR_WG_H3"), 1);
   k.bwd_fused = num(getenv("ULTR_SR_BWD_FUSED"), 7);
+  k.attn_long_min = num(getenv("ULTR_SR_ATTN_LONG_MIN"), SR_ATTN_ONE_PASS_MAX + 1);
   k.block = num(getenv("ULTR_SR_BLOCK"), 3);
   k.loaded = true;
   g_knobs = k;
@@ -2019,6 +2022,14 @@ bool embed_fwd(const SrCall& c, const float* feats, const int32_t* docids, int64
 
 void ultr_setrank_knobs_reload() { sr_knobs_load(); }
 
+extern "C" int32_t ultr_setrank_attn_path(const ultr_setrank_desc* c, int32_t list_size, int32_t backward) {
+  SrPlan p;
+  if (list_size <= 0 || !make_plan(c, list_size, &p)) return ULTR_E_BADARG;
+  const SrKnobs& k = sr_knobs();
+  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, k.attn_long_min};
+  return sr_attn_path(ash, list_size, backward != 0, k.attn_h3 >= 1 && ((k.attn_mask >> 1) & 1) != 0);
+}
+
 extern "C" int64_t ultr_setrank_param_count(const ultr_setrank_desc* c) {
   SrPlan p;
   return make_plan(c, 0, &p) ? p.P : 0;
@@ -2063,7 +2074,7 @@ int setrank_forward(const ultr_setrank_desc* desc, const float* params, const fl
   const int drop_rc = sr_dropout_plan(dropout, batch, list_size, &da);
   if (drop_rc < 0) return drop_rc;
   const bool drop = drop_rc == 1;
-  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16};
+  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, sr_knobs().attn_long_min};
   SR_CHECK(sr_attn_supported(ash, L, 0));
   if (T > 0x7fffffff / 4) return ULTR_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
@@ -2181,7 +2192,7 @@ int setrank_backward(const ultr_setrank_desc* desc, const float* params, int32_t
     dpart = DM + ((T * p.d + 3) & ~(int64_t)3);
     dpart_floats = (sr_drop_parts(T) * p.d + 3) & ~(int64_t)3;
   }
-  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16};
+  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, sr_knobs().attn_long_min};
   SR_CHECK(sr_attn_supported(ash, L, 1));
   hipStream_t st = (hipStream_t)stream;
   const float* sv = (const float*)saved;

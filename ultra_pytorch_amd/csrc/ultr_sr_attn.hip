@@ -4,6 +4,8 @@
 // the split-half BACKWARD (`sr_attn_bwd_h3_kernel`: hi / lo f16 operands, scores unchanged bit for bit; default at head depth 32 / 64),
 // plain-f16 operands on request (`*_f16_kernel`: ultr_setrank_desc.attention_dtype = ULTR_ATTN_FP16, ordering-level parity) and scalar
 // kernels for head depths the matrix cores do not take.  Split out of ultr_setrank.hip in round 6 (launch interface: ultr_sr_attn.h).
+// These are ONE-PASS kernels (a whole score row in registers, the whole head slice in LDS): lists up to 256 documents.  Beyond, the forward
+// streams the keys (ultr_sr_attn_long.hip); sr_attn_path below is the one dispatch for both files.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -172,21 +174,6 @@ __device__ __forceinline__ void sr_stage_head(const float* __restrict__ x, const
     st4(xs + r * LDX + c4, r < L ? ld4(x + base + (int64_t)r * d + c4) : z4);
     if (WITH_DA) st4(das + r * LDX + c4, r < L ? ld4(dA + base + (int64_t)r * d + c4) : z4);
   }
-}
-
-// tile  D[row = 16 ta + (4 q + r)][col = block of bf] = sum_k  a[16 ta + i][k] * bf[i][k]   (a from LDS, bf = fragments)
-template <int DH>
-__device__ __forceinline__ f32x4 sr_tile_nt(const float* arow, const float4 (&bf)[DH / 16]) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int f = 0; f < DH / 16; ++f) {
-    const float4 a4 = ld4(arow + 4 * f);
-    acc = mfma16(a4.x, bf[f].x, acc);
-    acc = mfma16(a4.y, bf[f].y, acc);
-    acc = mfma16(a4.z, bf[f].z, acc);
-    acc = mfma16(a4.w, bf[f].w, acc);
-  }
-  return acc;
 }
 
 template <int DH>
@@ -867,19 +854,12 @@ __global__ __launch_bounds__(SR_MAXT * 64) void sr_attn_bwd_h3_kernel(const floa
 
 // matrix-core attention: list_size <= 128 (one wave per 16-token block), head depth 16 / 32 / 64, 16-byte aligned head
 // slices; ULTR_SR_SCALAR_ATTN=1 forces the scalar kernels
-bool attn_mfma_ok(const SrAttnShape& p, int L) {
+bool attn_mfma_shape_ok(const SrAttnShape& p) {  // (the streaming forward of ultr_sr_attn_long.hip takes the same shapes at any list size)
   const char* v = getenv("ULTR_SR_SCALAR_ATTN");
   if (v != nullptr && v[0] == '1') return false;
-  return L <= 16 * SR_MAXT && (p.dh == 16 || p.dh == 32 || p.dh == 64) && p.d % 4 == 0;
+  return (p.dh == 16 || p.dh == 32 || p.dh == 64) && p.d % 4 == 0;
 }
-template <typename K>
-int set_dyn_lds(K kernel, size_t bytes) {
-  if (bytes > 160 * 1024) return ULTR_E_UNSUPPORTED;
-  if (bytes > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    return ULTR_E_UNSUPPORTED;
-  return 0;
-}
+bool attn_mfma_ok(const SrAttnShape& p, int L) { return L <= 16 * SR_MAXT && attn_mfma_shape_ok(p); }
 int attn_fwd_mfma(const SrAttnShape& p, const float* x, int batch, int L, float* A, float* lse, hipStream_t st) {
   const int Lp = round_up(L, 16);
   const size_t lds = (size_t)Lp * (p.dh + 4) * sizeof(float);
@@ -969,16 +949,48 @@ int attn_bwd_mfma(const SrAttnShape& p, const float* x, const float* dA, const f
 
 bool sr_attn_mfma_ok(const SrAttnShape& s, int L) { return attn_mfma_ok(s, L); }
 
+static_assert(SR_ATTN_ONE_PASS_MAX == 64 * SR_KPL, "the scalar forward holds SR_KPL keys per lane");
+
+// LDS requests of the scalar one-pass kernels: ONE expression for the gate and the launch
+static size_t attn_fwd_scalar_lds(const SrAttnShape& s, int L) { return ((size_t)L * (s.dh + 1) + 4 * (size_t)L) * sizeof(float); }
+static size_t attn_bwd_scalar_lds(const SrAttnShape& s, int L) { return ((size_t)2 * L * (s.dh + 1) + 2 * (size_t)L * L) * sizeof(float); }
+constexpr size_t SR_LDS_MAX = 160 * 1024;
+
+int sr_attn_path(const SrAttnShape& s, int L, int backward, bool split_half) {
+  if (L <= 0) return ULTR_E_UNSUPPORTED;
+  if (backward) {  // no streaming backward: what the one-pass kernels take, whichever kernel ran the forward (A and lse have one layout)
+    if (L > SR_ATTN_ONE_PASS_MAX) return ULTR_E_UNSUPPORTED;
+    if (attn_f16_ok(s, L)) return ULTR_SR_ATTN_F16;
+    if (split_half && attn_h3_ok(s, L)) return ULTR_SR_ATTN_SPLIT_HALF;
+    if (attn_mfma_ok(s, L)) return ULTR_SR_ATTN_MFMA;
+    // the scalar attention backward keeps two [L, L] matrices and two head slices in LDS
+    return (L <= 120 && attn_bwd_scalar_lds(s, L) <= SR_LDS_MAX) ? ULTR_SR_ATTN_SCALAR : ULTR_E_UNSUPPORTED;
+  }
+  // ULTR_SR_ATTN_LONG_MIN only LOWERS the hand-over point: beyond the one-pass kernels' bound the keys are always streamed
+  if (L > SR_ATTN_ONE_PASS_MAX || (s.long_min > 0 && L >= s.long_min)) {
+    if (attn_mfma_shape_ok(s)) return ULTR_SR_ATTN_LONG_MFMA;
+    return sr_attn_long_scalar_fits(s.dh) ? ULTR_SR_ATTN_LONG_SCALAR : ULTR_E_UNSUPPORTED;  // (head depths beyond about 420)
+  }
+  if (attn_f16_ok(s, L)) return ULTR_SR_ATTN_F16;
+  if (attn_mfma_ok(s, L)) return ULTR_SR_ATTN_MFMA;
+  return attn_fwd_scalar_lds(s, L) <= SR_LDS_MAX ? ULTR_SR_ATTN_SCALAR : ULTR_E_UNSUPPORTED;  // the whole head slice sits in LDS
+}
+
 int sr_attn_supported(const SrAttnShape& s, int L, int backward) {
-  if (L > 64 * SR_KPL) return ULTR_E_UNSUPPORTED;
-  if (backward && !attn_mfma_ok(s, L) && L > 120) return ULTR_E_UNSUPPORTED;  // the scalar attention backward keeps two [L, L] matrices in LDS
-  return 0;
+  // (the split-half kernel only ever replaces the fp32 matrix-core backward: it does not change what is supported)
+  return sr_attn_path(s, L, backward, false) < 0 ? ULTR_E_UNSUPPORTED : 0;
 }
 
 int sr_attn_forward(const SrAttnShape& s, const float* x, int batch, int L, float* A, float* lse, hipStream_t st) {
-  if (attn_f16_ok(s, L)) return attn_fwd_f16(s, x, batch, L, A, lse, st);
-  if (attn_mfma_ok(s, L)) return attn_fwd_mfma(s, x, batch, L, A, lse, st);
-  const size_t lds = ((size_t)L * (s.dh + 1) + 4 * (size_t)L) * sizeof(float);
+  switch (sr_attn_path(s, L, 0, false)) {
+    case ULTR_SR_ATTN_F16: return attn_fwd_f16(s, x, batch, L, A, lse, st);
+    case ULTR_SR_ATTN_MFMA: return attn_fwd_mfma(s, x, batch, L, A, lse, st);
+    case ULTR_SR_ATTN_LONG_MFMA: return sr_attn_forward_long(s, true, x, batch, L, A, lse, st);
+    case ULTR_SR_ATTN_LONG_SCALAR: return sr_attn_forward_long(s, false, x, batch, L, A, lse, st);
+    case ULTR_SR_ATTN_SCALAR: break;
+    default: return ULTR_E_UNSUPPORTED;
+  }
+  const size_t lds = attn_fwd_scalar_lds(s, L);
   SR_CHECK(set_dyn_lds(sr_attn_fwd_kernel, lds));
   hipLaunchKernelGGL(sr_attn_fwd_kernel, dim3(batch, s.H), dim3(256), lds, st, x, L, s.d, s.dh, A);
   return 0;
@@ -986,10 +998,14 @@ int sr_attn_forward(const SrAttnShape& s, const float* x, int batch, int L, floa
 
 int sr_attn_backward(const SrAttnShape& s, bool split_half, const float* x, const float* dA, const float* Aout, const float* lse, int batch, int L,
                      float* dx, hipStream_t st) {
-  if (attn_f16_ok(s, L)) return attn_bwd_f16(s, x, dA, Aout, lse, batch, L, dx, st);
-  if (split_half && attn_h3_ok(s, L)) return attn_bwd_h3(s, x, dA, Aout, lse, batch, L, dx, st);
-  if (attn_mfma_ok(s, L)) return attn_bwd_mfma(s, x, dA, Aout, lse, batch, L, dx, st);
-  const size_t lds = ((size_t)2 * L * (s.dh + 1) + 2 * (size_t)L * L) * sizeof(float);
+  switch (sr_attn_path(s, L, 1, split_half)) {
+    case ULTR_SR_ATTN_F16: return attn_bwd_f16(s, x, dA, Aout, lse, batch, L, dx, st);
+    case ULTR_SR_ATTN_SPLIT_HALF: return attn_bwd_h3(s, x, dA, Aout, lse, batch, L, dx, st);
+    case ULTR_SR_ATTN_MFMA: return attn_bwd_mfma(s, x, dA, Aout, lse, batch, L, dx, st);
+    case ULTR_SR_ATTN_SCALAR: break;
+    default: return ULTR_E_UNSUPPORTED;
+  }
+  const size_t lds = attn_bwd_scalar_lds(s, L);
   SR_CHECK(set_dyn_lds(sr_attn_bwd_kernel, lds));
   hipLaunchKernelGGL(sr_attn_bwd_kernel, dim3(batch, s.H), dim3(256), lds, st, x, dA, L, s.d, s.dh, dx);
   return 0;

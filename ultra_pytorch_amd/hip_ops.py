@@ -179,6 +179,16 @@ def setrank_backward(shape, params, B, L, saved, dscores, loss_ws, n_loss_parts,
                                           int(n_loss_parts), _p(ws), _p(grads), _stream()), "ultr_setrank_backward")
 
 
+def setrank_attn_path(shape, L, backward=False):
+    """The attention kernel family SetRank's forward (or, backward=True, its backward) takes at list size L, under the knobs as the
+    library last read them: one of _lib.SR_ATTN_PATHS - "scalar", "mfma" (fp32 matrix cores), "f16", "split_half" (backward only),
+    "long_mfma" / "long_scalar" (the streaming forward beyond 256 documents, or from ULTR_SR_ATTN_LONG_MIN on).  Host-only: needs no
+    GPU and launches nothing.  A refused shape raises UltrHipError, as the call itself would."""
+    rc = int(shape.lib.ultr_setrank_attn_path(ctypes.byref(shape.desc), int(L), 1 if backward else 0))
+    check(min(rc, 0), "ultr_setrank_attn_path")
+    return _lib.SR_ATTN_PATHS[rc]
+
+
 def tail_floats(L):
     return int(_lib.load().ultr_step_tail_floats(int(L)))
 

@@ -58,7 +58,9 @@ class SetRank(nn.Module):
         super().__init__()
         print("build SetRank")
         # attention_dtype is this package's one extension of the reference's hparams: "fp32" (default, the 1e-5 parity
-        # path) or "fp16" (fp16 matrix-core operands in the self-attention, ordering-level parity; BASELINE config 5)
+        # path) or "fp16" (fp16 matrix-core operands in the self-attention, ordering-level parity; BASELINE config 5).  The fp16
+        # kernels take head depth 32 / 64 and lists up to 128 documents; everywhere else - the streaming kernels of lists beyond 256
+        # documents included - "fp16" runs the fp32 path
         self.hparams = HParams(d_model=256, num_heads=8, num_layers=2, diff=64, rate=0.0, initializer=None,
                                attention_dtype="fp32")
         self.hparams.parse(hparams_str)
