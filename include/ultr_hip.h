@@ -76,6 +76,13 @@ typedef struct ultr_dnn_desc {
   int32_t flags;
 } ultr_dnn_desc;
 #define ULTR_MODEL_FP32_PRODUCTS 1
+/* ultr_setrank_desc::flags only: train this SetRank model at any list size.  Where the one-pass attention backward refuses (beyond 128
+ * documents on the matrix cores, 120 on the scalar kernel; and from ULTR_SR_ATTN_LONG_MIN on) the backward streams partner tiles through
+ * LDS, and the FORWARD streams at the same list sizes - the streaming backward reads the forward's row statistic, which the one-pass
+ * scalar forward of 129 .. 256 documents does not write.  That range is the one place where the scores of a model with the flag differ
+ * in bits from one without; below the hand-over both run the one-pass kernels.  ultr_setrank_workspace_bytes grows by
+ * n_rows x num_heads floats for such a descriptor. */
+#define ULTR_MODEL_SR_STREAM_BWD 2
 
 /* ---- host-only queries ------------------------------------------------------------- */
 int ultr_abi_version(void);
@@ -246,8 +253,10 @@ int ultr_pdgd_loss(const float* scores, const float* labels, const int32_t* doci
  * batch * list_size <= 0x7fffffff / 4 and the size of `saved`.
  * backward: dscores [B, L] from any ultr_*_loss kernel (x D convention), loss_ws/n_loss_parts = that kernel's
  * partials; writes grads [P + step tail]; follow with ultr_grad_sumsq + ultr_apply_update(wt = NULL).
- * list_size <= 128 on the matrix-core attention path (head depth 16 / 32 / 64), <= 120 otherwise: there is no streaming
- * attention backward, so a forward at a longer list is an evaluation (ULTR_E_UNSUPPORTED from the backward). */
+ * list_size <= 128 on the matrix-core attention path (head depth 16 / 32 / 64), <= 120 otherwise - a forward at a longer list is an
+ * evaluation (ULTR_E_UNSUPPORTED from the backward) - unless the descriptor carries ULTR_MODEL_SR_STREAM_BWD: then any list_size,
+ * through the streaming attention backward (fp32 matrix cores at head depth 16 / 32 / 64, a scalar kernel at every other up to 228;
+ * deterministic, no atomics). */
 enum ultr_attention_dtype { ULTR_ATTN_FP32 = 0, ULTR_ATTN_FP16 = 1 };
 typedef struct ultr_setrank_desc {
   int32_t feature_size, d_model, num_heads, num_layers, dff;
@@ -257,7 +266,8 @@ typedef struct ultr_setrank_desc {
    * opt-in.  Needs head depth 32 or 64 and list_size <= 128, otherwise the fp32 kernels run (the streaming kernels of the long
    * lists are fp32 only: ULTR_ATTN_FP16 at list_size 300 runs them). */
   int32_t attention_dtype;
-  int32_t flags;  /* ABI 6: ULTR_MODEL_FP32_PRODUCTS - the Linear products and d x d weight gradients of this model on the fp32 matrix cores */
+  int32_t flags;  /* ABI 6: ULTR_MODEL_FP32_PRODUCTS - the Linear products and d x d weight gradients of this model on the fp32 matrix cores;
+                   * ULTR_MODEL_SR_STREAM_BWD - streaming attention backward beyond the one-pass bounds (see the define) */
 } ultr_setrank_desc;
 int64_t ultr_setrank_param_count(const ultr_setrank_desc* c);
 int64_t ultr_setrank_saved_bytes(const ultr_setrank_desc* c, int64_t n_rows);
@@ -278,8 +288,8 @@ enum ultr_setrank_attn_path_id {
   ULTR_SR_ATTN_MFMA = 1,         /* fp32 matrix cores, the score row in registers (list_size <= 128) */
   ULTR_SR_ATTN_F16 = 2,          /* fp16 operands (ULTR_ATTN_FP16) */
   ULTR_SR_ATTN_SPLIT_HALF = 3,   /* hi / lo fp16 operands (backward only) */
-  ULTR_SR_ATTN_LONG_MFMA = 4,    /* keys streamed in tiles, fp32 matrix cores (forward only) */
-  ULTR_SR_ATTN_LONG_SCALAR = 5   /* keys streamed in tiles, scalar (forward only) */
+  ULTR_SR_ATTN_LONG_MFMA = 4,    /* keys / partner tokens streamed in tiles, fp32 matrix cores */
+  ULTR_SR_ATTN_LONG_SCALAR = 5   /* keys / partner tokens streamed in tiles, scalar */
 };
 int32_t ultr_setrank_attn_path(const ultr_setrank_desc* c, int32_t list_size, int32_t backward);
 

@@ -25,6 +25,7 @@ class DnnDesc(ctypes.Structure):
 
 
 MODEL_FP32_PRODUCTS = 1  # ultr_dnn_desc / ultr_setrank_desc ::flags (include/ultr_hip.h, ABI 6)
+MODEL_SR_STREAM_BWD = 2  # ultr_setrank_desc::flags: the streaming attention backward beyond the one-pass kernels' list bounds
 ABI_VERSION = 8          # include/ultr_hip.h: ULTR_ABI_VERSION - load() refuses a library that reports another one
 
 

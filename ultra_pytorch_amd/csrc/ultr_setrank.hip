@@ -77,6 +77,7 @@ struct SrPlan {
   int64_t sv_planes, planes_halves;
   int64_t sv_flag;   // float offset in `saved` of the range word behind the planes (ULTR_H3_FLAG_*: raised by sr_split_planes_kernel)
   int no_h3;         // ultr_setrank_desc::flags & ULTR_MODEL_FP32_PRODUCTS
+  int stream_bwd;    // ultr_setrank_desc::flags & ULTR_MODEL_SR_STREAM_BWD: the streaming attention backward where the one-pass kernels refuse
   struct SplitMat { int64_t off; int M, K, ldK, ldM; int64_t f_off, t_off, g_off, gt_off; };  // g_off: fragment-major forward copy (sr_block_fwd_kernel), -1: none
                                                                                             // gt_off: fragment-major copy of W^T (out K, contraction M: the dgrad
                                                                                             // products of ultr_sr_bwd.hip), -1: none
@@ -94,6 +95,7 @@ struct SrPlan {
   // the backward queues every partial-sum fold and runs them as ONE launch at its end (sr_fold_all_kernel): partials then
   // cannot share scratch, each producer takes a fresh piece of this arena
   int64_t ws_arena, arena_floats;
+  int64_t ws_attn_t; // [T, H] t = dA . A of the streaming attention backward (stream_bwd only: other descriptors keep their size); else -1
   int64_t ws_total;
   int bwd_fused;     // the widths ultr_sr_bwd.hip takes: transposed fragment copies exist, the arena holds its per-workgroup partials
 };
@@ -120,6 +122,7 @@ bool make_plan(const ultr_setrank_desc* c, int64_t T, SrPlan* p) {
   p->dh = p->d / p->H;
   p->att_f16 = (c->attention_dtype == ULTR_ATTN_FP16) ? 1 : 0;
   p->no_h3 = (c->flags & ULTR_MODEL_FP32_PRODUCTS) ? 1 : 0;
+  p->stream_bwd = (c->flags & ULTR_MODEL_SR_STREAM_BWD) ? 1 : 0;
   p->T = T;
   const int64_t F = p->F, d = p->d, dff = p->dff;
   int64_t o = 0;
@@ -216,6 +219,11 @@ bool make_plan(const ultr_setrank_desc* c, int64_t T, SrPlan* p) {
     p->arena_floats += (int64_t)(2 * p->nl + 1) * SR_BWD_MAXWG * (d * dff + dff + 3 * d + 4) + (int64_t)SR_BWD_MAXWG * (2 * F + dff * F + dff + d * dff + d + 4);
   w = (w + 3) & ~(int64_t)3;  // 16-byte pieces (the vector form of sr_fold_all_kernel)
   p->ws_arena = w; w += p->arena_floats;
+  p->ws_attn_t = -1;
+  if (p->stream_bwd) {
+    w = (w + 3) & ~(int64_t)3;
+    p->ws_attn_t = w; w += (T * p->H + 3) & ~(int64_t)3;
+  }
   p->ws_total = w;
   return true;
 }
@@ -2026,7 +2034,7 @@ extern "C" int32_t ultr_setrank_attn_path(const ultr_setrank_desc* c, int32_t li
   SrPlan p;
   if (list_size <= 0 || !make_plan(c, list_size, &p)) return ULTR_E_BADARG;
   const SrKnobs& k = sr_knobs();
-  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, k.attn_long_min};
+  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, k.attn_long_min, p.stream_bwd};
   return sr_attn_path(ash, list_size, backward != 0, k.attn_h3 >= 1 && ((k.attn_mask >> 1) & 1) != 0);
 }
 
@@ -2074,7 +2082,7 @@ int setrank_forward(const ultr_setrank_desc* desc, const float* params, const fl
   const int drop_rc = sr_dropout_plan(dropout, batch, list_size, &da);
   if (drop_rc < 0) return drop_rc;
   const bool drop = drop_rc == 1;
-  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, sr_knobs().attn_long_min};
+  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, sr_knobs().attn_long_min, p.stream_bwd};
   SR_CHECK(sr_attn_supported(ash, L, 0));
   if (T > 0x7fffffff / 4) return ULTR_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
@@ -2192,7 +2200,7 @@ int setrank_backward(const ultr_setrank_desc* desc, const float* params, int32_t
     dpart = DM + ((T * p.d + 3) & ~(int64_t)3);
     dpart_floats = (sr_drop_parts(T) * p.d + 3) & ~(int64_t)3;
   }
-  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, sr_knobs().attn_long_min};
+  const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, sr_knobs().attn_long_min, p.stream_bwd};
   SR_CHECK(sr_attn_supported(ash, L, 1));
   hipStream_t st = (hipStream_t)stream;
   const float* sv = (const float*)saved;
@@ -2200,6 +2208,7 @@ int setrank_backward(const ultr_setrank_desc* desc, const float* params, int32_t
   float* G0 = ws + p.ws_g[0];
   float* G1 = ws + p.ws_g[1];
   float* G2 = ws + p.ws_g[2];
+  float* attn_t = p.ws_attn_t >= 0 ? ws + p.ws_attn_t : nullptr;  // the streaming attention backward's t = dA . A
   const unsigned rblk = (unsigned)((T + SR_ROWS - 1) / SR_ROWS);
   const int F = p.F, d = p.d, dff = p.dff;
   FoldQueue folds(ws + p.ws_arena, p.arena_floats);  // every fold below is queued; ONE launch at the end
@@ -2280,7 +2289,7 @@ int setrank_backward(const ultr_setrank_desc* desc, const float* params, int32_t
         folds.add(pb + (int64_t)dff * d + dff + d, sb, fz_nwg, 2 * d, grads + y.g1, st);  // d g1 | d b1
         SR_CHECK(wgrad(c, G0, sv + p.sv_A[l], grads + y.wd, nullptr, d, d));
         // G0 += attention path -> d x_l
-        SR_CHECK(sr_attn_backward(ash, attn_split_half(l), sv + p.sv_x[l], G2, sv + p.sv_A[l], sv + p.sv_lse[l], batch, L, G0, st));
+        SR_CHECK(sr_attn_backward(ash, attn_split_half(l), sv + p.sv_x[l], G2, sv + p.sv_A[l], sv + p.sv_lse[l], batch, L, G0, attn_t, st));
         continue;
       }
     }
@@ -2325,7 +2334,7 @@ int setrank_backward(const ultr_setrank_desc* desc, const float* params, int32_t
     SR_CHECK(wgrad(c, dproj, sv + p.sv_A[l], grads + y.wd, nullptr, d, d));
     SR_CHECK(gemm_dyw(c, dproj, y.wd, G1, nullptr, d, d, 0));      // G1 = d A  [T, d]
     // G0 += attention path -> d x_l
-    SR_CHECK(sr_attn_backward(ash, attn_split_half(l), sv + p.sv_x[l], G1, sv + p.sv_A[l], sv + p.sv_lse[l], batch, L, G0, st));
+    SR_CHECK(sr_attn_backward(ash, attn_split_half(l), sv + p.sv_x[l], G1, sv + p.sv_A[l], sv + p.sv_lse[l], batch, L, G0, attn_t, st));
   }
   // ---- embedding FFN and the input LayerNorm's parameters -------------------------------------------------------------
   bool embed_done = false;

@@ -4,8 +4,9 @@
 // the split-half BACKWARD (`sr_attn_bwd_h3_kernel`: hi / lo f16 operands, scores unchanged bit for bit; default at head depth 32 / 64),
 // plain-f16 operands on request (`*_f16_kernel`: ultr_setrank_desc.attention_dtype = ULTR_ATTN_FP16, ordering-level parity) and scalar
 // kernels for head depths the matrix cores do not take.  Split out of ultr_setrank.hip in round 6 (launch interface: ultr_sr_attn.h).
-// These are ONE-PASS kernels (a whole score row in registers, the whole head slice in LDS): lists up to 256 documents.  Beyond, the forward
-// streams the keys (ultr_sr_attn_long.hip); sr_attn_path below is the one dispatch for both files.
+// These are ONE-PASS kernels (a whole score row in registers, the whole head slice in LDS): lists up to 256 documents forward, 128 / 120
+// backward.  Beyond, the forward streams the keys and - for a model with ULTR_MODEL_SR_STREAM_BWD - the backward streams partner tiles
+// (ultr_sr_attn_long.hip); sr_attn_path below is the one dispatch for both files.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -854,7 +855,7 @@ __global__ __launch_bounds__(SR_MAXT * 64) void sr_attn_bwd_h3_kernel(const floa
 
 // matrix-core attention: list_size <= 128 (one wave per 16-token block), head depth 16 / 32 / 64, 16-byte aligned head
 // slices; ULTR_SR_SCALAR_ATTN=1 forces the scalar kernels
-bool attn_mfma_shape_ok(const SrAttnShape& p) {  // (the streaming forward of ultr_sr_attn_long.hip takes the same shapes at any list size)
+bool attn_mfma_shape_ok(const SrAttnShape& p) {  // (the streaming kernels of ultr_sr_attn_long.hip take the same shapes at any list size)
   const char* v = getenv("ULTR_SR_SCALAR_ATTN");
   if (v != nullptr && v[0] == '1') return false;
   return (p.dh == 16 || p.dh == 32 || p.dh == 64) && p.d % 4 == 0;
@@ -956,18 +957,33 @@ static size_t attn_fwd_scalar_lds(const SrAttnShape& s, int L) { return ((size_t
 static size_t attn_bwd_scalar_lds(const SrAttnShape& s, int L) { return ((size_t)2 * L * (s.dh + 1) + 2 * (size_t)L * L) * sizeof(float); }
 constexpr size_t SR_LDS_MAX = 160 * 1024;
 
+// the one-pass backward of a shape, or ULTR_E_UNSUPPORTED: what the matrix-core kernels take up to 128 documents, the scalar kernel up to 120
+static int attn_bwd_one_pass(const SrAttnShape& s, int L, bool split_half) {
+  if (L > SR_ATTN_ONE_PASS_MAX) return ULTR_E_UNSUPPORTED;
+  if (attn_f16_ok(s, L)) return ULTR_SR_ATTN_F16;
+  if (split_half && attn_h3_ok(s, L)) return ULTR_SR_ATTN_SPLIT_HALF;
+  if (attn_mfma_ok(s, L)) return ULTR_SR_ATTN_MFMA;
+  // the scalar attention backward keeps two [L, L] matrices and two head slices in LDS
+  return (L <= 120 && attn_bwd_scalar_lds(s, L) <= SR_LDS_MAX) ? ULTR_SR_ATTN_SCALAR : ULTR_E_UNSUPPORTED;
+}
+// ULTR_SR_ATTN_LONG_MIN only LOWERS the hand-over point: beyond the one-pass kernels' bound the keys are always streamed
+static bool attn_fwd_streams(const SrAttnShape& s, int L) { return L > SR_ATTN_ONE_PASS_MAX || (s.long_min > 0 && L >= s.long_min); }
+// a model with ULTR_MODEL_SR_STREAM_BWD streams BOTH directions where its one-pass backward refuses (beyond 128 documents at matrix-core
+// shapes, 120 otherwise) and wherever the forward streams anyway: the streaming backward reads lse, which the one-pass scalar forward
+// of 129 .. 256 documents does not write - so the two directions hand over at the same list size
+static bool attn_train_streams(const SrAttnShape& s, int L) { return attn_fwd_streams(s, L) || attn_bwd_one_pass(s, L, false) < 0; }
+
 int sr_attn_path(const SrAttnShape& s, int L, int backward, bool split_half) {
   if (L <= 0) return ULTR_E_UNSUPPORTED;
-  if (backward) {  // no streaming backward: what the one-pass kernels take, whichever kernel ran the forward (A and lse have one layout)
-    if (L > SR_ATTN_ONE_PASS_MAX) return ULTR_E_UNSUPPORTED;
-    if (attn_f16_ok(s, L)) return ULTR_SR_ATTN_F16;
-    if (split_half && attn_h3_ok(s, L)) return ULTR_SR_ATTN_SPLIT_HALF;
-    if (attn_mfma_ok(s, L)) return ULTR_SR_ATTN_MFMA;
-    // the scalar attention backward keeps two [L, L] matrices and two head slices in LDS
-    return (L <= 120 && attn_bwd_scalar_lds(s, L) <= SR_LDS_MAX) ? ULTR_SR_ATTN_SCALAR : ULTR_E_UNSUPPORTED;
+  if (backward) {
+    if (s.stream_bwd && attn_train_streams(s, L)) {
+      if (attn_mfma_shape_ok(s)) return ULTR_SR_ATTN_LONG_MFMA;
+      return sr_attn_bwd_long_scalar_fits(s.dh) ? ULTR_SR_ATTN_LONG_SCALAR : ULTR_E_UNSUPPORTED;  // (head depths beyond about 228)
+    }
+    // no flag, no streaming backward: what the one-pass kernels take, whichever kernel ran the forward (A and lse have one layout)
+    return attn_bwd_one_pass(s, L, split_half);
   }
-  // ULTR_SR_ATTN_LONG_MIN only LOWERS the hand-over point: beyond the one-pass kernels' bound the keys are always streamed
-  if (L > SR_ATTN_ONE_PASS_MAX || (s.long_min > 0 && L >= s.long_min)) {
+  if (attn_fwd_streams(s, L) || (s.stream_bwd && attn_train_streams(s, L))) {
     if (attn_mfma_shape_ok(s)) return ULTR_SR_ATTN_LONG_MFMA;
     return sr_attn_long_scalar_fits(s.dh) ? ULTR_SR_ATTN_LONG_SCALAR : ULTR_E_UNSUPPORTED;  // (head depths beyond about 420)
   }
@@ -997,8 +1013,10 @@ int sr_attn_forward(const SrAttnShape& s, const float* x, int batch, int L, floa
 }
 
 int sr_attn_backward(const SrAttnShape& s, bool split_half, const float* x, const float* dA, const float* Aout, const float* lse, int batch, int L,
-                     float* dx, hipStream_t st) {
+                     float* dx, float* tws, hipStream_t st) {
   switch (sr_attn_path(s, L, 1, split_half)) {
+    case ULTR_SR_ATTN_LONG_MFMA: return sr_attn_backward_long(s, true, x, dA, Aout, lse, batch, L, dx, tws, st);
+    case ULTR_SR_ATTN_LONG_SCALAR: return sr_attn_backward_long(s, false, x, dA, Aout, lse, batch, L, dx, tws, st);
     case ULTR_SR_ATTN_F16: return attn_bwd_f16(s, x, dA, Aout, lse, batch, L, dx, st);
     case ULTR_SR_ATTN_SPLIT_HALF: return attn_bwd_h3(s, x, dA, Aout, lse, batch, L, dx, st);
     case ULTR_SR_ATTN_MFMA: return attn_bwd_mfma(s, x, dA, Aout, lse, batch, L, dx, st);

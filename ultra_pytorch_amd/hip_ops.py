@@ -79,9 +79,18 @@ class SetRankShape:
     `rate` is the dropout rate of TRAINING forwards (SetRank.py:103-117, 141-153).  It lives beside the descriptor, not in it: the
     parameter layout, the buffer sizes and every evaluation are those of the rate-0 model.  The dropout key rides along:
     `dropout_seed` (the owner of the shape sets it; ranking_model.SetRank captures torch.initial_seed()) and `dropout_step`, the count
-    of training forwards so far - engines are cached and evicted, so the counter is the model's, shared through this object."""
+    of training forwards so far - engines are cached and evicted, so the counter is the model's, shared through this object.
 
-    def __init__(self, feature_size, d_model=256, num_heads=8, num_layers=2, dff=64, attention_dtype="fp32", rate=0.0):
+    `attention_backward`: "one_pass" (default) trains lists up to 128 documents on the matrix-core attention kernels (head depth
+    16 / 32 / 64) and up to 120 elsewhere; "streaming" sets ULTR_MODEL_SR_STREAM_BWD in the descriptor: beyond those bounds the backward
+    AND the forward run the streaming kernels (csrc/ultr_sr_attn_long.hip), so the model trains at any list size.  Below the hand-over
+    point nothing changes; at 129 .. 256 documents a streaming model's scores come from the streaming forward instead of the one-pass
+    scalar kernel (same values to the 1e-5 bar, other bits)."""
+
+    ATTENTION_BACKWARD = ("one_pass", "streaming")
+
+    def __init__(self, feature_size, d_model=256, num_heads=8, num_layers=2, dff=64, attention_dtype="fp32", rate=0.0,
+                 attention_backward="one_pass"):
         rate = float(rate)
         if not 0.0 <= rate < 1.0:
             raise ValueError("rate must be in [0, 1) (got %r)" % rate)
@@ -92,8 +101,13 @@ class SetRankShape:
         if attention_dtype not in _lib.ATTN_DTYPE:
             raise ValueError("attention_dtype must be one of %s (got %r)" % (sorted(_lib.ATTN_DTYPE), attention_dtype))
         self.attention_dtype = attention_dtype
+        if attention_backward not in self.ATTENTION_BACKWARD:
+            raise ValueError("attention_backward must be one of %s (got %r)" % (list(self.ATTENTION_BACKWARD), attention_backward))
+        self.attention_backward = attention_backward
         self.desc = _lib.SetRankDesc(self.feature_size, self.d_model, self.num_heads, self.num_layers, self.dff,
                                      _lib.ATTN_DTYPE[attention_dtype])
+        if attention_backward == "streaming":
+            self.desc.flags = int(self.desc.flags) | _lib.MODEL_SR_STREAM_BWD
         self.n_params = int(self.lib.ultr_setrank_param_count(ctypes.byref(self.desc)))
         if self.n_params <= 0:
             raise ValueError("bad SetRank description (d_model must be a multiple of num_heads, 1..8 layers)")
@@ -182,7 +196,8 @@ def setrank_backward(shape, params, B, L, saved, dscores, loss_ws, n_loss_parts,
 def setrank_attn_path(shape, L, backward=False):
     """The attention kernel family SetRank's forward (or, backward=True, its backward) takes at list size L, under the knobs as the
     library last read them: one of _lib.SR_ATTN_PATHS - "scalar", "mfma" (fp32 matrix cores), "f16", "split_half" (backward only),
-    "long_mfma" / "long_scalar" (the streaming forward beyond 256 documents, or from ULTR_SR_ATTN_LONG_MIN on).  Host-only: needs no
+    "long_mfma" / "long_scalar" (the streaming kernels: the forward beyond 256 documents or from ULTR_SR_ATTN_LONG_MIN on; both
+    directions of a model with attention_backward="streaming" beyond its one-pass backward's bound).  Host-only: needs no
     GPU and launches nothing.  A refused shape raises UltrHipError, as the call itself would."""
     rc = int(shape.lib.ultr_setrank_attn_path(ctypes.byref(shape.desc), int(L), 1 if backward else 0))
     check(min(rc, 0), "ultr_setrank_attn_path")

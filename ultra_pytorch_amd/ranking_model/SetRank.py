@@ -60,9 +60,14 @@ class SetRank(nn.Module):
         # attention_dtype is this package's one extension of the reference's hparams: "fp32" (default, the 1e-5 parity
         # path) or "fp16" (fp16 matrix-core operands in the self-attention, ordering-level parity; BASELINE config 5).  The fp16
         # kernels take head depth 32 / 64 and lists up to 128 documents; everywhere else - the streaming kernels of lists beyond 256
-        # documents included - "fp16" runs the fp32 path
+        # documents included - "fp16" runs the fp32 path.
+        # attention_backward is the second: "one_pass" (default) trains lists up to 128 documents (120 off the matrix cores) and
+        # refuses longer ones; "streaming" trains at any list size (rank_list_size 300, Istella's 439, MSLR-WEB30K's 1251 under
+        # DirectLabelFeed) through the streaming attention kernels.  Below the one-pass backward's bound a streaming model runs the
+        # one-pass kernels with the default's bits; its scores at 129 .. 256 documents come from the streaming forward (the one-pass
+        # scalar forward there leaves no row statistic for the backward): the same values to the 1e-5 bar, not the same bits
         self.hparams = HParams(d_model=256, num_heads=8, num_layers=2, diff=64, rate=0.0, initializer=None,
-                               attention_dtype="fp32")
+                               attention_dtype="fp32", attention_backward="one_pass")
         self.hparams.parse(hparams_str)
         rate = float(self.hparams.rate)
         if not 0.0 <= rate < 1.0:
@@ -70,7 +75,8 @@ class SetRank(nn.Module):
         self.feature_size = int(feature_size)
         self.shape = hip_ops.SetRankShape(self.feature_size, self.hparams.d_model, self.hparams.num_heads,
                                           self.hparams.num_layers, self.hparams.diff,
-                                          attention_dtype=str(self.hparams.attention_dtype), rate=rate)
+                                          attention_dtype=str(self.hparams.attention_dtype), rate=rate,
+                                          attention_backward=str(self.hparams.attention_backward))
         self.shape.dropout_seed = int(torch.initial_seed())  # as DBGD keys its noise
         self._bind(init_setrank_params(self.shape))
         self._fwd_saved = {}
