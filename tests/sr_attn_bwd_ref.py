@@ -18,9 +18,10 @@ def gather(features, docids):
     return torch.from_numpy(np.ascontiguousarray(x.transpose(1, 0, 2)))
 
 
-def setrank_forward(params, F, d, H, nl, dff, features, docids):
+def setrank_forward(params, F, d, H, nl, dff, features, docids, detach_probabilities=False):
     """scores [B, L] (torch float64, differentiable in `params`): oracle.setrank_forward operation for operation, every number a
-    float64 - the root of the head depth included."""
+    float64 - the root of the head depth included.  detach_probabilities: the softmax output is a constant of the graph, so a gradient
+    taken through these scores lacks the logit path (dS = P (dP - t) / sqrt(dh) and the dq + dk chain behind it); the scores are the same."""
     from oracle import ultr_oracle as O
     params = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, np.float64))
     W = {n: params[o:o + int(np.prod(sh))].reshape(sh) for n, sh, o in O.setrank_layout(F, d, nl, dff)}
@@ -35,7 +36,8 @@ def setrank_forward(params, F, d, H, nl, dff, features, docids):
     for i in range(nl):
         l = e + "enc_layers.encoder%d." % i
         q = x.reshape(B, L, H, depth).permute(0, 2, 1, 3)
-        att = torch.softmax((q @ q.transpose(-1, -2)) / math.sqrt(depth), dim=-1) @ q
+        prob = torch.softmax((q @ q.transpose(-1, -2)) / math.sqrt(depth), dim=-1)
+        att = (prob.detach() if detach_probabilities else prob) @ q
         att = att.permute(0, 2, 1, 3).reshape(B, L, d)
         o = att @ W[l + "mha.dense.weight"].T + W[l + "mha.dense.bias"]
         out1 = ln(x + o, (d,), W[l + "layernorm1.weight"], W[l + "layernorm1.bias"], 1e-6)
@@ -55,12 +57,13 @@ def softmax_loss(scores, labels, pw=None):
     return torch.sum(loss) / torch.sum(w)
 
 
-def train_step(params, cfg, features, docids, labels_LB, ipw_list=None):
+def train_step(params, cfg, features, docids, labels_LB, ipw_list=None, detach_probabilities=False):
     """Scores, loss and gradient of one NA (ipw_list None) / IPW step: dict(scores [B, L], loss, grads [P]) in float64.  The
-    propensity weights are the float32 numbers IPWrank builds (oracle.ipw_weights), widened."""
+    propensity weights are the float32 numbers IPWrank builds (oracle.ipw_weights), widened.  detach_probabilities: the gradient without
+    the logit path of every attention (setrank_forward); the difference to the default gradient is that path's contribution."""
     from oracle import ultr_oracle as O
     p = torch.as_tensor(np.asarray(params), dtype=torch.float64).clone().requires_grad_(True)
-    scores = setrank_forward(p, *cfg, features, docids)
+    scores = setrank_forward(p, *cfg, features, docids, detach_probabilities=detach_probabilities)
     labels = torch.from_numpy(np.ascontiguousarray(np.transpose(labels_LB))).double()
     pw = None if ipw_list is None else O.ipw_weights(labels_LB, ipw_list).double()
     loss = softmax_loss(scores, labels, pw)
