@@ -451,7 +451,7 @@ def _setrank_shapes():
 
 SR_SHAPES = _setrank_shapes()
 SR_RAGGED, SR_PADDED = (3, 37, 20, 48, 6, 1, 20), SR_SHAPES[7]  # a ragged last token block; (37, 30, ...) with PAD documents
-SR_SETTINGS = ([("ULTR_SR_BLOCK", v) for v in "0123"] + [("ULTR_SR_BWD_FUSED", v) for v in ("0", "6", "7")]
+SR_SETTINGS = ([("ULTR_SR_BLOCK", v) for v in "023"] + [("ULTR_SR_BWD_FUSED", v) for v in ("0", "6", "7")]
                + [("ULTR_SR_ATTN_H3", v) for v in "01"] + [("attention_dtype", "fp16")])
 
 

@@ -1,4 +1,5 @@
-"""GPU box: phase cycles of sr_block_fwd_kernel (SetRank's fused encoder block, config 5's shape) from a -DULTR_TRACE build:
+"""GPU box: phase cycles of sr_block_fwd_kernel (ultr_sr_block.hip: SetRank's fused encoder block of round 5, config 5's shape; run with
+ULTR_SR_BLOCK=2 - by default that shape takes the persistent kernel) from a -DULTR_TRACE build:
    ULTR_TRACE_LIB=ultra_pytorch_amd/lib/variants/libultr_trace.so python tools/trace_sr_block.py
 Wave 0 of every 8th workgroup (the first 64 of them); the forward's LAST block launch wins (the slots are shared with the GEMM kernels'
 stamps: 20 start, 21 prologue done, 22 product Wd done, 23 barrier, 24 LayerNorm 1 done, 25 barrier, 26 f done, 27 barrier, 28 product

@@ -1,5 +1,5 @@
 // ultr_h3.h - split-half (fp16 hi / lo) product building blocks shared by the DNN kernels (ultr_dnn.hip) and SetRank's fused block
-// kernel (ultr_setrank.hip): operand split, the wide-tile weight pipeline PipeH3W, stores through buffer resources.
+// kernels (ultr_sr_block.hip, ultr_sr_fwd.hip, ultr_sr_bwd.hip): operand split, the wide-tile weight pipeline PipeH3W, stores through buffer resources.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

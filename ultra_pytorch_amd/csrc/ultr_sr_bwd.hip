@@ -17,7 +17,7 @@
 //
 // HBM traffic per block: reads d x', s2, f | d out1, s1, d f; writes d f, d out1 | d s1, d A  = 0.81 GB.  Column sums (LayerNorm
 // gamma / beta, the three biases) ride along in registers; one partial per workgroup leaves at the end (256 partials of 17 k floats
-// instead of a 64 KB slab per 800 rows), folded by sr_fold_all_kernel in fixed order: deterministic, no atomics.
+// instead of a 64 KB slab per 800 rows), folded by sr_fold_all_kernel (ultr_sr_rows.hip) in fixed order: deterministic, no atomics.
 // Shapes: d_model 256, dff 64 (BASELINE config 5); ultr_setrank_backward keeps the separate launches for everything else.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
 // sr_bwd_head_kernel: the output FFN's backward (SetRank.py:136, 153 backwards): score = oh . wo2 + bo2, oh = relu(x Wo1^T + bo1)
 //   d oh = d score wo2 o [oh > 0],  d wo2 = sum d score oh,  d bo2 = sum d score,  d Wo1 += d oh^T x,  d bo1 = sum d oh,  d x = d oh Wo1
-// (was: sr_head_bwd_kernel + a thin weight-gradient launch + a dgrad GEMM - d oh written and read twice, x read once: 315 MB; here
+// (was: sr_head_bwd_kernel, ultr_sr_rows.hip, + a thin weight-gradient launch + a dgrad GEMM - d oh written and read twice, x read once: 315 MB; here
 // 236 MB, and d oh never leaves the chip).  Partial per workgroup: [d Wo1 (dff x d) | d bo1 (dff) | d wo2 (dff) | d bo2 | pad].
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void sr_bwd_head_kernel(SrBwdHeadArgs a, const float* __restrict__ params,
                                                                                               const _Float16* __restrict__ planes,

@@ -1,6 +1,6 @@
 // ultr_sr_dropout.hip - the row kernels of SetRank's dropout steps (ultr_sr_dropout.h has the mask law).  A dropout step runs the
-// separate-launch paths of ultr_setrank.hip in both directions; these kernels stand where ln_residual_fwd / the bias column sums of
-// ln_bwd_cs stand at rate 0.  One Philox call covers four neighbouring columns of one token, so every kernel walks rows in quads.
+// separate-launch paths of ultr_setrank.hip in both directions; these kernels stand where sr_ln_residual_fwd / the bias column sums of
+// sr_ln_bwd_cs (ultr_sr_rows.hip) stand at rate 0.  One Philox call covers four neighbouring columns of one token, so every kernel walks rows in quads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -8,7 +8,7 @@
 #include "ultr_device.h"
 #include "ultr_sr_dropout.h"
 
-#define SR_DROP_EPS 1e-6f  // nn.LayerNorm(eps=1e-6), as ultr_setrank.hip's SR_EPS
+#define SR_DROP_EPS 1e-6f  // nn.LayerNorm(eps=1e-6), as ultr_sr_plan.h's SR_EPS
 #define SR_DROP_WAVES 4    // rows per workgroup of the LayerNorm kernels (one wavefront per row)
 
 namespace {
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(SR_DROP_WAVES * 64) void sr_drop_ln_fwd_kernel(SrDr
   }
 }
 
-// W = NV * 256 with 16-byte accesses, as sr_ln_fwd_v4_kernel: lane owns columns 4 lane .. 4 lane + 3 (+ 256 k) = quad lane + 64 k
+// W = NV * 256 with 16-byte accesses, as sr_ln_fwd_v4_kernel (ultr_sr_rows.hip): lane owns columns 4 lane .. 4 lane + 3 (+ 256 k) = quad lane + 64 k
 template <int NV>
 __global__ __launch_bounds__(SR_DROP_WAVES * 64) void sr_drop_ln_fwd_v4_kernel(SrDropArgs a, uint32_t c1, const float* x, const float* b /* may alias y */,
                                                                               const float* __restrict__ bias, int64_t T,

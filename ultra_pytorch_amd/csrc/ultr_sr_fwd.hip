@@ -3,7 +3,7 @@
 // Reference: ultra/ranking_model/SetRank.py:92-111 (+ the output FFN :136, :153 on the last block):
 //   s1 = x + (A Wd^T + bd),  out1 = LN1(s1),  f = relu(out1 Wf1^T + bf1),  s2 = out1 + (f Wf2^T + bf2),  x' = LN2(s2)
 //   [last block: oh = relu(x' Wo1^T + bo1),  score = oh . wo2 + bo2]
-// sr_block_fwd_kernel (round 5, ultr_setrank.hip) does the same with two 8-wave workgroups per compute unit and R <= 30 rows each: every
+// sr_block_fwd_kernel (round 5, ultr_sr_block.hip) does the same with two 8-wave workgroups per compute unit and R <= 30 rows each: every
 // workgroup streams the block's 384 KB of weight fragments for 30 rows (1.36 GB of L2 -> CU traffic per launch), and its 3 500 workgroups
 // start and drain their HBM traffic in lock step (3.3 TB/s over the launch).  Here - the geometry of the backward's fused launches,
 // ultr_sr_bwd.hip - ONE workgroup per compute unit walks over tiles of 60 rows: four 16-row MFMA tiles behind one weight stream per wave

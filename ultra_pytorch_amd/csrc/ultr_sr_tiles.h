@@ -26,7 +26,7 @@ __device__ __forceinline__ float2 ld2(const float* p) { return *reinterpret_cast
 __device__ __forceinline__ float max4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 
 // LayerNorm backward of four rows per wave (rows wave + 8 (4 half + k), lane = columns 4 lane .. + 3; d = 256):
-//   xh = (s - mean) rstd,  g = dy gamma,  v = rstd (g - mean(g) - xh mean(g xh))         (same expressions as sr_ln_bwd_cs_v4_kernel)
+//   xh = (s - mean) rstd,  g = dy gamma,  v = rstd (g - mean(g) - xh mean(g xh))         (same expressions as sr_ln_bwd_cs_v4_kernel, ultr_sr_rows.hip)
 // v goes to the fp16 plane pair in P0 scaled per row (OS[row] = the inverse scale x 2^-8: the weights are stored x 2^8) and, by MODE,
 //   MODE 0: to P1 as fp32 rows (the residual and the weight-gradient operand of the FFN kernel)
 //   MODE 1: to global memory (d s1), while P1 receives out1 = xh gamma + beta (the weight-gradient operand of the projection kernel)
