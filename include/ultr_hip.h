@@ -245,8 +245,9 @@ int ultr_pdgd_loss(const float* scores, const float* labels, const int32_t* doci
  * hand-written: the Linear layers run on the library's LDS-tiled matrix-core GEMM with fused bias / ReLU epilogues.
  * params: flat vector in SetRank.state_dict() order (Encoder_layer.input_layer_norm, input_embedding.{0,2},
  * output_layer.{0,2}, then per encoder: mha.dense, ffn.{0,2}, layernorm1, layernorm2).
- * forward: scores [B, L]; `saved` (ultr_setrank_saved_bytes) receives every activation the backward needs and is
- * required for validation too (it doubles as scratch).  Any list_size: up to 256 documents the one-pass attention kernels run,
+ * forward: scores [B, L]; `saved` (ultr_setrank_saved_bytes) receives every activation the backward needs (it doubles as
+ * scratch); a forward that no backward follows - validation - takes ultr_setrank_score and its smaller buffer.
+ * Any list_size: up to 256 documents the one-pass attention kernels run,
  * beyond them (ULTR_SR_ATTN_LONG_MIN, default 257, lowers the hand-over) the keys stream through LDS in tiles with a running row
  * maximum and sum (fp32 matrix cores at head depth 16 / 32 / 64, a scalar kernel at every other up to 420: its rows sit in LDS,
  * as the one-pass scalar kernel's do - beyond, ULTR_E_UNSUPPORTED before anything is launched); what bounds the forward is
@@ -292,6 +293,19 @@ enum ultr_setrank_attn_path_id {
   ULTR_SR_ATTN_LONG_SCALAR = 5   /* keys / partner tokens streamed in tiles, scalar */
 };
 int32_t ultr_setrank_attn_path(const ultr_setrank_desc* c, int32_t list_size, int32_t backward);
+/* The evaluation forward (additive within ABI 8): the scores of ultr_setrank_forward, bit for bit on every route and attention family,
+ * and no record for a backward.  `work` (ultr_setrank_score_bytes; about F + dff + 4 d_model floats per row whatever num_layers, plus
+ * the split-half planes) holds only what one launch hands to the next: x_l / x_{l+1} alternate between two buffers, the attention's
+ * output has one, the separate launches share one buffer per row width; statistics rows, lse and - on the fused launches - every
+ * row the backward alone reads are not stored.  The planes are rebuilt per call and the range word raised as in the training
+ * forward, at float offset ultr_setrank_score_range_flag_offset of `work` (-1 on a bad desc).  No dropout.
+ * work_bytes < ultr_setrank_score_bytes(c, batch * list_size): ULTR_E_WORKSPACE, nothing launched; every other refusal is
+ * ultr_setrank_forward's. */
+int64_t ultr_setrank_score_bytes(const ultr_setrank_desc* c, int64_t n_rows);
+int64_t ultr_setrank_score_range_flag_offset(const ultr_setrank_desc* c, int64_t n_rows);
+int ultr_setrank_score(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
+                       const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* work, int64_t work_bytes,
+                       void* stream);
 
 /* SetRank's dropout.  Replaces the nn.Dropout(rate) calls of EncoderLayer.forward and Encoder.forward (ranking_model/SetRank.py:103-117,
  * 141-153) at 1 + 2 num_layers sites: 0 behind input_embedding, 1 + 2 l behind encoder l's mha.dense, 2 + 2 l behind its ffn - each on

@@ -150,6 +150,9 @@ SIGNATURES = {
     "ultr_setrank_forward": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_setrank_backward": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
                                       c_vp]),
+    "ultr_setrank_score_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
+    "ultr_setrank_score_range_flag_offset": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
+    "ultr_setrank_score": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "ultr_setrank_attn_path": (c_i32, [ctypes.POINTER(SetRankDesc), c_i32, c_i32]),
     "ultr_setrank_dropout_workspace_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
     "ultr_setrank_forward_dropout": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp,

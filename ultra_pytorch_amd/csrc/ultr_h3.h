@@ -121,6 +121,11 @@ __device__ __forceinline__ Dst make_dst(float* base, int64_t nfloats) {
   d.rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)(nfloats * 4), 0x00020000);
   return d;
 }
+// rows a launch may leave unwritten (float offset `off` into `base` < 0, a kernel argument: wave-uniform): an EMPTY extent - the bounds
+// check drops every store through it, nothing reaches memory; else `nfloats` floats from base + off + at
+__device__ __forceinline__ Dst make_dst_opt(float* base, int64_t off, int64_t at, int64_t nfloats) {
+  return off < 0 ? make_dst(base, 0) : make_dst(base + off + at, nfloats);
+}
 __device__ __forceinline__ void buf_st4(const Dst& d, unsigned voff, unsigned soff, float4 v) {
   const u32x4 x = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
   __builtin_amdgcn_raw_buffer_store_b128(x, d.rs, voff, soff, 0);

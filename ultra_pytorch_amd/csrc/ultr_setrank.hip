@@ -438,6 +438,9 @@ int wgrad(const SrCall& c, const float* dY, const float* X, float* dW, float* db
 
 void ultr_setrank_knobs_reload() { sr_knobs_load(); }
 
+// bytes of `saved` (sr_make_plan) or of the scoring buffer (sr_make_score_plan): activations, planes, four floats with the range word
+static int64_t sr_saved_bytes(const SrPlan& p) { return (p.sv_planes + (p.planes_halves + 1) / 2 + 4) * (int64_t)sizeof(float); }
+
 extern "C" int32_t ultr_setrank_attn_path(const ultr_setrank_desc* c, int32_t list_size, int32_t backward) {
   SrPlan p;
   if (list_size <= 0 || !sr_make_plan(c, list_size, &p)) return ULTR_E_BADARG;
@@ -452,11 +455,20 @@ extern "C" int64_t ultr_setrank_param_count(const ultr_setrank_desc* c) {
 }
 extern "C" int64_t ultr_setrank_saved_bytes(const ultr_setrank_desc* c, int64_t n_rows) {
   SrPlan p;
-  return (n_rows >= 0 && sr_make_plan(c, n_rows, &p)) ? (p.sv_planes + (p.planes_halves + 1) / 2 + 4) * (int64_t)sizeof(float) : 0;
+  return (n_rows >= 0 && sr_make_plan(c, n_rows, &p)) ? sr_saved_bytes(p) : 0;
 }
 extern "C" int64_t ultr_setrank_range_flag_offset(const ultr_setrank_desc* c, int64_t n_rows) {
   SrPlan p;
   return (n_rows >= 0 && sr_make_plan(c, n_rows, &p)) ? p.sv_flag : -1;
+}
+// the scoring entry's buffer (ultr_setrank_score): the live activations of sr_make_score_plan, the planes, the range word
+extern "C" int64_t ultr_setrank_score_bytes(const ultr_setrank_desc* c, int64_t n_rows) {
+  SrPlan p;
+  return (n_rows >= 0 && sr_make_score_plan(c, n_rows, &p)) ? sr_saved_bytes(p) : 0;
+}
+extern "C" int64_t ultr_setrank_score_range_flag_offset(const ultr_setrank_desc* c, int64_t n_rows) {
+  SrPlan p;
+  return (n_rows >= 0 && sr_make_score_plan(c, n_rows, &p)) ? p.sv_flag : -1;
 }
 extern "C" int64_t ultr_setrank_workspace_bytes(const ultr_setrank_desc* c, int64_t n_rows) {
   SrPlan p;
@@ -479,12 +491,12 @@ int64_t sr_dropout_ws_floats(const SrPlan& p) {
 
 int setrank_forward(const ultr_setrank_desc* desc, const float* params, const float* features, int64_t n_docs,
                     const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
-                    const ultr_setrank_dropout* dropout, void* stream) {
+                    const ultr_setrank_dropout* dropout, void* stream, bool score = false, int64_t saved_bytes = 0) {
   if (!params || !docids || !scores || !saved || batch <= 0 || list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features))
     return ULTR_E_BADARG;
   const int64_t T = (int64_t)batch * list_size;
   SrPlan p;
-  if (!sr_make_plan(desc, T, &p)) return ULTR_E_BADARG;
+  if (!sr_make_plan_any(desc, T, &p, score)) return ULTR_E_BADARG;
   const int L = list_size;
   SrDropArgs da;
   const int drop_rc = sr_dropout_plan(dropout, batch, list_size, &da);
@@ -493,9 +505,12 @@ int setrank_forward(const ultr_setrank_desc* desc, const float* params, const fl
   const SrAttnShape ash = {p.d, p.dh, p.H, p.att_f16, sr_knobs().attn_long_min, p.stream_bwd};
   SR_CHECK(sr_attn_supported(ash, L, 0));
   if (T > 0x7fffffff / 4) return ULTR_E_UNSUPPORTED;
+  if (score && saved_bytes < sr_saved_bytes(p)) return ULTR_E_WORKSPACE;  // (ultr_setrank_score: the buffer comes with its size)
   hipStream_t st = (hipStream_t)stream;
   float* sv = (float*)saved;
   const int F = p.F, d = p.d, dff = p.dff;
+  // a row of the plan nobody keeps (offset < 0, the scoring plan): NULL, and the kernel does not store it
+  auto opt = [&](int64_t off) -> float* { return off < 0 ? nullptr : sv + off; };
   SrCall c = {p, params, nullptr, sr_knobs(), sr_cu_count(), sv, nullptr, st, nullptr};
   _Float16* planes = reinterpret_cast<_Float16*>(sv + p.sv_planes);
   const bool planes_on = c.knobs.h3 && !p.no_h3;
@@ -522,8 +537,8 @@ int setrank_forward(const ultr_setrank_desc* desc, const float* params, const fl
   if (rt.embed && n_docs > 0 && n_docs * (int64_t)F * 4 < ((int64_t)1 << 31) && ((uintptr_t)features & 15) == 0) {
     SR_CHECK(sr_embed_fwd(c, rt, features, docids, n_docs, (int)batch, L));  // one launch (sr_embed_fwd_kernel)
   } else {
-    sr_ln_gather_fwd(features, docids, n_docs, (int)batch, L, T, F, params + p.g_in, params + p.b_in, sv + p.sv_xg, sv + p.sv_xn0,
-                  sv + p.sv_mean_in, sv + p.sv_rstd_in, st);
+    sr_ln_gather_fwd(features, docids, n_docs, (int)batch, L, T, F, params + p.g_in, params + p.b_in, opt(p.sv_xg), sv + p.sv_xn0,
+                  opt(p.sv_mean_in), opt(p.sv_rstd_in), st);
     SR_CHECK(gemm_xwT(c, sv + p.sv_xn0, p.w1, params + p.b1, sv + p.sv_h0, F, dff, 1));
     SR_CHECK(gemm_xwT(c, sv + p.sv_h0, p.w2, params + p.b2, sv + p.sv_x[0], dff, d, 0));
   }
@@ -531,7 +546,7 @@ int setrank_forward(const ultr_setrank_desc* desc, const float* params, const fl
   for (int l = 0; l < p.nl; ++l) {
     const SrLayer& y = p.lay[l];
     const float* x = sv + p.sv_x[l];
-    SR_CHECK(sr_attn_forward(ash, x, batch, L, sv + p.sv_A[l], sv + p.sv_lse[l], st));
+    SR_CHECK(sr_attn_forward(ash, x, batch, L, sv + p.sv_A[l], opt(p.sv_lse[l]), st));
     if (rt.block != SR_BLOCK_SEPARATE) {  // everything behind the attention in one launch
       SR_CHECK(sr_block_fwd(c, rt, l, scores));
       continue;
@@ -549,23 +564,27 @@ int setrank_forward(const ultr_setrank_desc* desc, const float* params, const fl
                             sv + p.sv_s2[l], sv + p.sv_x[l + 1], sv + p.sv_m2[l], sv + p.sv_r2[l], st);
       continue;
     }
+    // the scoring plan runs both LayerNorms in place (s1 and out1 share a buffer, s2 and x_{l+1} do): where the row kernel itself forms
+    // the pre-norm sum it then keeps none
+    float* const s1_keep = p.sv_s1[l] == p.sv_out1[l] ? nullptr : sv + p.sv_s1[l];
+    float* const s2_keep = p.sv_s2[l] == p.sv_x[l + 1] ? nullptr : sv + p.sv_s2[l];
     const bool ln_v4 = (d == 256 || d == 512 || d == 768 || d == 1024);
     if (ln_v4 && gemm_xwT_res(c, sv + p.sv_A[l], y.wd, params + y.bd, x, sv + p.sv_s1[l], d, d)) {
       sr_ln_residual_fwd(sv + p.sv_s1[l], nullptr, nullptr, T, d, params + y.g1, params + y.b1, nullptr, sv + p.sv_out1[l],
-                      sv + p.sv_m1[l], sv + p.sv_r1[l], (int)batch, L, st);
+                      opt(p.sv_m1[l]), opt(p.sv_r1[l]), (int)batch, L, st);
     } else {
       SR_CHECK(gemm_xwT(c, sv + p.sv_A[l], y.wd, nullptr, sv + p.sv_out1[l], d, d, 0));
-      sr_ln_residual_fwd(x, sv + p.sv_out1[l], params + y.bd, T, d, params + y.g1, params + y.b1, sv + p.sv_s1[l], sv + p.sv_out1[l],
-                      sv + p.sv_m1[l], sv + p.sv_r1[l], (int)batch, L, st);
+      sr_ln_residual_fwd(x, sv + p.sv_out1[l], params + y.bd, T, d, params + y.g1, params + y.b1, s1_keep, sv + p.sv_out1[l],
+                      opt(p.sv_m1[l]), opt(p.sv_r1[l]), (int)batch, L, st);
     }
     SR_CHECK(gemm_xwT(c, sv + p.sv_out1[l], y.wf1, params + y.bf1, sv + p.sv_f[l], d, dff, 1));
     if (ln_v4 && gemm_xwT_res(c, sv + p.sv_f[l], y.wf2, params + y.bf2, sv + p.sv_out1[l], sv + p.sv_s2[l], dff, d)) {
       sr_ln_residual_fwd(sv + p.sv_s2[l], nullptr, nullptr, T, d, params + y.g2, params + y.b2, nullptr, sv + p.sv_x[l + 1],
-                      sv + p.sv_m2[l], sv + p.sv_r2[l], (int)batch, L, st);
+                      opt(p.sv_m2[l]), opt(p.sv_r2[l]), (int)batch, L, st);
     } else {
       SR_CHECK(gemm_xwT(c, sv + p.sv_f[l], y.wf2, nullptr, sv + p.sv_x[l + 1], dff, d, 0));
-      sr_ln_residual_fwd(sv + p.sv_out1[l], sv + p.sv_x[l + 1], params + y.bf2, T, d, params + y.g2, params + y.b2, sv + p.sv_s2[l],
-                      sv + p.sv_x[l + 1], sv + p.sv_m2[l], sv + p.sv_r2[l], (int)batch, L, st);
+      sr_ln_residual_fwd(sv + p.sv_out1[l], sv + p.sv_x[l + 1], params + y.bf2, T, d, params + y.g2, params + y.b2, s2_keep,
+                      sv + p.sv_x[l + 1], opt(p.sv_m2[l]), opt(p.sv_r2[l]), (int)batch, L, st);
     }
   }
   // output FFN (SetRank.py:136, 153)
@@ -758,6 +777,14 @@ extern "C" int ultr_setrank_backward(const ultr_setrank_desc* c, const float* pa
 extern "C" int64_t ultr_setrank_dropout_workspace_bytes(const ultr_setrank_desc* c, int64_t n_rows) {
   SrPlan p;
   return (n_rows >= 0 && sr_make_plan(c, n_rows, &p)) ? sr_dropout_ws_floats(p) * (int64_t)sizeof(float) : 0;
+}
+// The evaluation forward: the bits of ultr_setrank_forward in `scores`, no record for a backward - `work` (ultr_setrank_score_bytes) holds
+// what the launches hand to each other, the planes and the range word (ultr_setrank_score_range_flag_offset).  Same driver, same route,
+// the scoring plan (sr_make_score_plan, ultr_sr_plan.h).
+extern "C" int ultr_setrank_score(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
+                                  const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* work, int64_t work_bytes,
+                                  void* stream) {
+  return setrank_forward(c, params, features, n_docs, docids, batch, list_size, scores, work, nullptr, stream, true, work_bytes);
 }
 extern "C" int ultr_setrank_forward_dropout(const ultr_setrank_desc* c, const float* params, const float* features, int64_t n_docs,
                                             const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,

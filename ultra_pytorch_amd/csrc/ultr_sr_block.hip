@@ -49,12 +49,12 @@ struct SrBlockArgs {
   int64_t T;
   int64_t bd, bf1, bf2, g1, b1, g2, b2;                  // float offsets into the parameter vector
   int64_t gd, gf1, gf2;                                  // HALF offsets of the fragment-major copies of Wd, Wf1, Wf2 from the planes
-  int64_t A, x, s1, m1, r1, out1, f, s2, m2, r2, xn;     // float offsets into `saved`
+  int64_t A, x, s1, m1, r1, out1, f, s2, m2, r2, xn;     // float offsets into `saved`; s1 .. r2 (not xn) < 0: not stored (the scoring forward)
   int p0, p1, p2, pv;                                    // float offsets into dynamic LDS
   // the last block also runs the output FFN (SetRank.py:136, 153): oh = relu(x' Wo1^T + bo1), score = oh . wo2 + bo2
   int head;
   int skip_out1;  // the backward recomputes out1 from s1 (sr_bwd_proj_kernel): the forward does not write it (105 MB per block at config 5)
-  int64_t go1, bo1, wo2, bo2, oh;                        // fragment copy of Wo1 (halves), parameter offsets, saved oh
+  int64_t go1, bo1, wo2, bo2, oh;                        // fragment copy of Wo1 (halves), parameter offsets, saved oh (< 0: not stored)
 #ifdef ULTR_TRACE
   unsigned long long* trace;
 #endif
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(NW * 64) void sr_block_fwd_kernel(SrBlockArgs a, co
       for (int tt = 0; tt < 2; ++tt) acc[t][tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     ph.run(pa, lo_off, Wh, has ? nks : 0, acc);
     if (has) {
-      const Dst dout = make_dst(sv + out_off + n0 * d, (int64_t)vr * d);
+      const Dst dout = make_dst_opt(sv, out_off, n0 * d, (int64_t)vr * d);
       const float2 bv = *reinterpret_cast<const float2*>(bias + col);
       const unsigned gv = (unsigned)(4 * q * d + 2 * i) * 4u;
 #pragma unroll
@@ -212,8 +212,8 @@ __global__ __launch_bounds__(NW * 64) void sr_block_fwd_kernel(SrBlockArgs a, co
       qv[q] = (v[q].x * v[q].x + v[q].y * v[q].y) + (v[q].z * v[q].z + v[q].w * v[q].w);
     }
     wave_sum_n<RT>(qv);
-    const Dst dmean = make_dst(sv + mean_off + n0, vr), drstd = make_dst(sv + rstd_off + n0, vr);
-    const Dst dout = make_dst(sv + out_off + n0 * d, (int64_t)vr * d);
+    const Dst dmean = make_dst_opt(sv, mean_off, n0, vr), drstd = make_dst_opt(sv, rstd_off, n0, vr);
+    const Dst dout = make_dst_opt(sv, out_off, n0 * d, (int64_t)vr * d);
     const unsigned l0 = lane == 0 ? 0u : ULTR_OOB;
     const float4 g4 = cok ? ld4(gam + c) : make_float4(0.f, 0.f, 0.f, 0.f), b4 = cok ? ld4(bet + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     float am[RT];
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(NW * 64) void sr_block_fwd_kernel(SrBlockArgs a, co
     const bool cok = c < dff;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 b4 = cok ? ld4(bias + c) : z4, w4 = (cok && wdot != nullptr) ? ld4(wdot + c) : z4;
-    const Dst df = make_dst(sv + out_off + n0 * dff, (int64_t)vr * dff);
+    const Dst df = make_dst_opt(sv, out_off, n0 * dff, (int64_t)vr * dff);
     float4 v[RT];
     float am[RT];
 #pragma unroll
@@ -374,7 +374,7 @@ struct SrEmbedArgs {
   int B, L;
   int64_t g_in, b_in, b1, b2;              // float offsets into the parameter vector
   int64_t gw1, gw2;                        // HALF offsets of the fragment copies of W1 [dff][F] and W2 [d][dff]
-  int64_t xg, mean_in, rstd_in, xn0, h0, x0;  // float offsets into `saved`
+  int64_t xg, mean_in, rstd_in, xn0, h0, x0;  // float offsets into `saved`; all but x0 < 0: not stored (the scoring forward)
   int p0, p2, pv;                          // float offsets into dynamic LDS
 };
 
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(NW * 64) void sr_embed_fwd_kernel(SrEmbedArgs a, co
     const bool cok = c < F;
     float4 v[RT];
     float s[RT], qv[RT];
-    const Dst dxg = make_dst(sv + a.xg + n0 * F, (int64_t)vr * F);
+    const Dst dxg = make_dst_opt(sv, a.xg, n0 * F, (int64_t)vr * F);
 #pragma unroll
     for (int q = 0; q < RT; ++q) {
       const int id = __builtin_amdgcn_readlane(myid, q);
@@ -433,8 +433,8 @@ __global__ __launch_bounds__(NW * 64) void sr_embed_fwd_kernel(SrEmbedArgs a, co
       qv[q] = (v[q].x * v[q].x + v[q].y * v[q].y) + (v[q].z * v[q].z + v[q].w * v[q].w);
     }
     wave_sum_n<RT>(qv);
-    const Dst dmean = make_dst(sv + a.mean_in + n0, vr), drstd = make_dst(sv + a.rstd_in + n0, vr);
-    const Dst dxn = make_dst(sv + a.xn0 + n0 * F, (int64_t)vr * F);
+    const Dst dmean = make_dst_opt(sv, a.mean_in, n0, vr), drstd = make_dst_opt(sv, a.rstd_in, n0, vr);
+    const Dst dxn = make_dst_opt(sv, a.xn0, n0 * F, (int64_t)vr * F);
     const unsigned l0 = lane == 0 ? 0u : ULTR_OOB;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 g4 = cok ? ld4(pg + c) : z4, b4 = cok ? ld4(pb + c) : z4;
@@ -513,7 +513,7 @@ __global__ __launch_bounds__(NW * 64) void sr_embed_fwd_kernel(SrEmbedArgs a, co
     const bool cok = c < dff;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 b4 = cok ? ld4(pb1 + c) : z4;
-    const Dst dh = make_dst(sv + a.h0 + n0 * dff, (int64_t)vr * dff);
+    const Dst dh = make_dst_opt(sv, a.h0, n0 * dff, (int64_t)vr * dff);
     float4 v[RT];
     float am[RT];
 #pragma unroll
@@ -607,6 +607,7 @@ void fill_block_args(Args& a, const SrCall& c, const SrRoute& rt, int l) {
     a.head = 1;
     a.go1 = c.split(p.wo1, dff, d)->g_off; a.bo1 = p.bo1; a.wo2 = p.wo2; a.bo2 = p.bo2; a.oh = p.sv_oh;
   }
+  if (p.score) a.s1 = a.out1 = a.f = a.s2 = a.oh = -1;  // no backward follows: the rows stay in LDS (the plan's buffers for them serve the separate launches)
 }
 
 }  // namespace
@@ -651,6 +652,7 @@ int sr_embed_fwd(const SrCall& c, const SrRoute& rt, const float* feats, const i
   a.g_in = p.g_in; a.b_in = p.b_in; a.b1 = p.b1; a.b2 = p.b2;
   a.gw1 = c.split(p.w1, dff, F)->g_off; a.gw2 = c.split(p.w2, d, dff)->g_off;
   a.xg = p.sv_xg; a.mean_in = p.sv_mean_in; a.rstd_in = p.sv_rstd_in; a.xn0 = p.sv_xn0; a.h0 = p.sv_h0; a.x0 = p.sv_x[0];
+  if (p.score) a.xn0 = a.h0 = -1;  // (xg and the statistics: -1 in the scoring plan itself)
   a.p0 = 0;
   a.p2 = (R + 1) * (K16 + 8);
   a.pv = a.p2 + (R + 1) * (dff + 8);

@@ -64,7 +64,7 @@ struct SrFwdBlockArgs {
   int64_t T;
   int64_t bd, bf1, bf2, g1, b1, g2, b2, bo1, wo2, bo2;   // parameters
   int64_t gd, gf1, gf2, go1;                             // HALVES: forward fragment copies of Wd, Wf1, Wf2, Wo1
-  int64_t A, x, s1, m1, r1, out1, f, s2, m2, r2, xn, oh; // saved
+  int64_t A, x, s1, m1, r1, out1, f, s2, m2, r2, xn, oh; // saved; s1 .. r2 and oh < 0: not stored (the scoring forward)
   int p0, p1, p2, os;
 };
 int sr_fwd_block_launch(SrFwdBlockArgs a, int nwg, const float* params, const _Float16* planes, float* sv, float* scores, hipStream_t st);

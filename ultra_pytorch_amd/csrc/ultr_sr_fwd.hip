@@ -240,7 +240,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     lds_barrier();
     // ---- s1 = x + (A Wd^T + bd): to `saved` and back into P1 -------------------------------------------------------------------------------
     {
-      const Dst ds1 = make_dst(sv + a.s1 + n0 * d, (int64_t)vr * d);
+      const Dst ds1 = make_dst_opt(sv, a.s1, n0 * d, (int64_t)vr * d);
       product_d4<true, true, true>(wave, lane, R, P0, ld, d >> 5, planes, a.gd, d, OS, P1, ld, ds1, pbd);
     }
     SRF_STAMP(2);
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     __builtin_amdgcn_sched_barrier(0);
     float m1v[8], r1v[8];
     {
-      const Dst dout = make_dst(sv + a.out1 + n0 * d, (int64_t)vr * d), dm = make_dst(sv + a.m1 + n0, vr), dr = make_dst(sv + a.r1 + n0, vr);
+      const Dst dout = make_dst_opt(sv, a.out1, n0 * d, (int64_t)vr * d), dm = make_dst_opt(sv, a.m1, n0, vr), dr = make_dst_opt(sv, a.r1, n0, vr);
       const float4 g4 = ld4(pg1 + 4 * lane), b4 = ld4(pb1 + 4 * lane);
       if (a.skip_out1) ln_fwd_rows<true>(wave, lane, R, ld, P1, P0, OS, g4, b4, dout, dm, dr, false, true, m1v, r1v);
       else ln_fwd_rows<false>(wave, lane, R, ld, P1, P0, OS, g4, b4, dout, dm, dr, true, true, m1v, r1v);
@@ -264,10 +264,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     lds_barrier();
     // ---- f = relu(out1 Wf1^T + bf1) ---------------------------------------------------------------------------------------------------------
     {
-      const Dst dfo = make_dst(sv + a.f + n0 * dff, (int64_t)vr * dff), none = make_dst(sv, 0);
+      const Dst dfo = make_dst_opt(sv, a.f, n0 * dff, (int64_t)vr * dff), none = make_dst(sv, 0);
       product_f_relu(wave, lane, R, P0, P2, OS, planes, a.gf1, pbf1, dfo, nullptr, 0.f, none);
       if (a.skip_out1) {  // LayerNorm_1's statistics, held back while the next tile's rows were in flight
-        const Dst dm = make_dst(sv + a.m1 + n0, vr), dr = make_dst(sv + a.r1 + n0, vr);
+        const Dst dm = make_dst_opt(sv, a.m1, n0, vr), dr = make_dst_opt(sv, a.r1, n0, vr);
         const unsigned l0 = lane == 0 ? 0u : ULTR_OOB;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     lds_barrier();
     // ---- s2 = out1 + (f Wf2^T + bf2) ---------------------------------------------------------------------------------------------------------
     {
-      const Dst ds2 = make_dst(sv + a.s2 + n0 * d, (int64_t)vr * d);
+      const Dst ds2 = make_dst_opt(sv, a.s2, n0 * d, (int64_t)vr * d);
       product_d4<true, true, true>(wave, lane, R, P2, ldf, dff >> 5, planes, a.gf2, dff, OS + 64, P1, ld, ds2, pbf2);
     }
     SRF_STAMP(5);
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     lds_barrier();
     // ---- x' = LN2(s2) ------------------------------------------------------------------------------------------------------------------------
     {
-      const Dst dout = make_dst(sv + a.xn + n0 * d, (int64_t)vr * d), dm = make_dst(sv + a.m2 + n0, vr), dr = make_dst(sv + a.r2 + n0, vr);
+      const Dst dout = make_dst(sv + a.xn + n0 * d, (int64_t)vr * d), dm = make_dst_opt(sv, a.m2, n0, vr), dr = make_dst_opt(sv, a.r2, n0, vr);
       const float4 g4 = ld4(pg2 + 4 * lane), b4 = ld4(pb2 + 4 * lane);
       float mu[8], ru[8];
       ln_fwd_rows<false>(wave, lane, R, ld, P1, P0, OS, g4, b4, dout, dm, dr, true, a.head != 0, mu, ru);
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     if (a.head) {
       lds_barrier();
       // ---- oh = relu(x' Wo1^T + bo1), score = oh . wo2 + bo2 --------------------------------------------------------------------------------
-      const Dst doh = make_dst(sv + a.oh + n0 * dff, (int64_t)vr * dff), dsc = make_dst(scores + n0, vr);
+      const Dst doh = make_dst_opt(sv, a.oh, n0 * dff, (int64_t)vr * dff), dsc = make_dst(scores + n0, vr);
       product_f_relu(wave, lane, R, P0, P2, OS, planes, a.go1, pbo1, doh, pwo2, pwo2[dff], dsc);
     }
     SRF_STAMP(8);

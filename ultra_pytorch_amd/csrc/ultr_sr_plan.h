@@ -1,5 +1,6 @@
 // ultr_sr_plan.h - what the host side of SetRank agrees on before a launch (host only: no kernel lives here): the parameter, saved-
-// activation and workspace plan of a descriptor (SrPlan, sr_make_plan), the knobs, the context of ONE ultr_setrank_forward / _backward call
+// activation and workspace plan of a descriptor (SrPlan: sr_make_plan, and sr_make_score_plan for the forward no backward follows), the
+// knobs, the context of ONE ultr_setrank_forward / _score / _backward call
 // (SrCall) and the ROUTE of a step (SrRoute, sr_route): which launches its forward and its backward take, decided once per call from the
 // same inputs on both sides.  Included by ultr_setrank.hip (the step), ultr_sr_rows.hip and ultr_sr_block.hip (the launchers).
 #pragma once
@@ -58,6 +59,8 @@ struct SrPlan {
   int64_t ws_attn_t; // [T, H] t = dA . A of the streaming attention backward (stream_bwd only: other descriptors keep their size); else -1
   int64_t ws_total;
   int bwd_fused;     // the widths ultr_sr_bwd.hip takes: transposed fragment copies exist, the arena holds its per-workgroup partials
+  int score;         // 1: the scoring plan (sr_make_score_plan) - no backward follows; sv_* offsets < 0 are rows nobody stores, the others alias
+                     // a few buffers, and the fused launches keep every row but x_{l+1} on chip
 };
 
 // row chunks of sr_wgrad_kernel for an [M, K] gradient: about two workgroups per CU, chunks of a multiple of 32 rows
@@ -73,7 +76,8 @@ inline int sr_wgrad_chunks(int64_t T, int M, int K, int* rows_per_chunk) {
   return (int)((T + rps - 1) / rps);
 }
 
-inline bool sr_make_plan(const ultr_setrank_desc* c, int64_t T, SrPlan* p) {
+// score: the activation layout of ultr_setrank_score (below) instead of the backward's complete record
+inline bool sr_make_plan_any(const ultr_setrank_desc* c, int64_t T, SrPlan* p, bool score) {
   if (!c || c->feature_size <= 0 || c->d_model <= 0 || c->num_heads <= 0 || c->num_layers <= 0 || c->num_layers > 8 ||
       c->dff <= 0 || c->d_model % c->num_heads != 0 || (c->attention_dtype != ULTR_ATTN_FP32 && c->attention_dtype != ULTR_ATTN_FP16))
     return false;
@@ -84,6 +88,7 @@ inline bool sr_make_plan(const ultr_setrank_desc* c, int64_t T, SrPlan* p) {
   p->no_h3 = (c->flags & ULTR_MODEL_FP32_PRODUCTS) ? 1 : 0;
   p->stream_bwd = (c->flags & ULTR_MODEL_SR_STREAM_BWD) ? 1 : 0;
   p->T = T;
+  p->score = score ? 1 : 0;
   const int64_t F = p->F, d = p->d, dff = p->dff;
   // THE parameter layout: every tensor starts where the one before it ends, in the reference's state_dict order
   //   g_in | b_in | W1 | b1 | W2 | b2 | Wo1 | bo1 | wo2 | bo2 | per layer: Wd | bd | Wf1 | bf1 | Wf2 | bf2 | g1 | b1 | g2 | b2
@@ -107,16 +112,36 @@ inline bool sr_make_plan(const ultr_setrank_desc* c, int64_t T, SrPlan* p) {
   p->P = o;
   int64_t s = 0;
   auto take = [&](int64_t n) { const int64_t at = s; s += (n + 3) & ~(int64_t)3; return at; };
-  p->sv_xg = take(T * F); p->sv_mean_in = take(T); p->sv_rstd_in = take(T); p->sv_xn0 = take(T * F);
-  p->sv_h0 = take(T * dff);
-  for (int l = 0; l <= p->nl; ++l) p->sv_x[l] = take(T * d);
-  for (int l = 0; l < p->nl; ++l) {
-    p->sv_A[l] = take(T * d); p->sv_s1[l] = take(T * d); p->sv_m1[l] = take(T); p->sv_r1[l] = take(T);
-    p->sv_out1[l] = take(T * d); p->sv_f[l] = take(T * dff);
-    p->sv_s2[l] = take(T * d); p->sv_m2[l] = take(T); p->sv_r2[l] = take(T);
-    p->sv_lse[l] = take(T * p->H);
+  if (!score) {
+    p->sv_xg = take(T * F); p->sv_mean_in = take(T); p->sv_rstd_in = take(T); p->sv_xn0 = take(T * F);
+    p->sv_h0 = take(T * dff);
+    for (int l = 0; l <= p->nl; ++l) p->sv_x[l] = take(T * d);
+    for (int l = 0; l < p->nl; ++l) {
+      p->sv_A[l] = take(T * d); p->sv_s1[l] = take(T * d); p->sv_m1[l] = take(T); p->sv_r1[l] = take(T);
+      p->sv_out1[l] = take(T * d); p->sv_f[l] = take(T * dff);
+      p->sv_s2[l] = take(T * d); p->sv_m2[l] = take(T); p->sv_r2[l] = take(T);
+      p->sv_lse[l] = take(T * p->H);
+    }
+    p->sv_oh = take(T * dff);
+  } else {
+    // The scoring layout: what a forward without a backward keeps alive, F + dff + 4 d floats per token whatever the depth -
+    //   X0 | X1  [T, d]    x_l and x_{l+1} ping-pong (a block reads one and writes the other)
+    //   A        [T, d]    the attention's output
+    //   S        [T, d]    separate launches: the pre-norm sum s1, then out1 = LN1(s1) IN PLACE (a row kernel: a lane reads its columns of
+    //                      its row before it writes them); s2 lands in x_{l+1}'s buffer and LN2 runs in place there
+    //   Hd       [T, dff]  separate launches: h0, every f_l, oh in turn
+    //   Xn       [T, F]    separate launches: the normalised input rows (the gathered rows are not kept)
+    // Statistics rows and lse: -1 everywhere.  On the fused launches S, Hd and Xn stay unused (the rows live in LDS): the launchers
+    // pass -1 for them (p.score).  The plan is a function of the descriptor and T alone, so it holds the separate route's buffers always.
+    const int64_t X0 = take(T * d), X1 = take(T * d), A = take(T * d), S = take(T * d), Hd = take(T * dff), Xn = take(T * F);
+    p->sv_xg = p->sv_mean_in = p->sv_rstd_in = -1;
+    p->sv_xn0 = Xn; p->sv_h0 = Hd; p->sv_oh = Hd;
+    for (int l = 0; l <= p->nl; ++l) p->sv_x[l] = (l & 1) ? X1 : X0;
+    for (int l = 0; l < p->nl; ++l) {
+      p->sv_A[l] = A; p->sv_s1[l] = S; p->sv_out1[l] = S; p->sv_f[l] = Hd; p->sv_s2[l] = p->sv_x[l + 1];
+      p->sv_m1[l] = p->sv_r1[l] = p->sv_m2[l] = p->sv_r2[l] = p->sv_lse[l] = -1;
+    }
   }
-  p->sv_oh = take(T * dff);
   p->sv_total = s;
   {
     int64_t h = 0;
@@ -192,6 +217,11 @@ inline bool sr_make_plan(const ultr_setrank_desc* c, int64_t T, SrPlan* p) {
   p->ws_total = w;
   return true;
 }
+// the plan of ultr_setrank_forward / _backward: `saved` is the backward's complete record
+inline bool sr_make_plan(const ultr_setrank_desc* c, int64_t T, SrPlan* p) { return sr_make_plan_any(c, T, p, false); }
+// the plan of ultr_setrank_score: same parameters, planes and range word, the activations of the scoring layout.  setrank_forward runs
+// against either plan; the workspace fields (the backward's) mean nothing here.
+inline bool sr_make_score_plan(const ultr_setrank_desc* c, int64_t T, SrPlan* p) { return sr_make_plan_any(c, T, p, true); }
 
 // Knobs of SetRank (README.md): read from the environment ONCE (first use), replaced whole by ultr_config_reload(); every call
 // takes one copy into its context, so one forward or backward sees one set of values.  Storage and loader: ultr_setrank.hip.

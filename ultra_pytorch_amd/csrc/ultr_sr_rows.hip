@@ -17,7 +17,9 @@ namespace {
 // y = LayerNorm(a [+ (b [+ bias])]) * gamma + beta; optionally stores the pre-norm sum and the statistics.
 // (b + bias is the preceding Linear's output: its bias add rides along instead of costing a pass of its own.)
 // a_gather: a is the feature matrix and rows are gathered through the doc ids (PAD -> zero row).
-__global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_fwd_kernel(const float* a, const float* b /* may alias y */,
+// In place (y == a or y == b, the scoring forward): a lane reads and writes columns lane + 64 k of its wave's row only, and in every
+// pass reads a column before it writes it.
+__global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_fwd_kernel(const float* a /* may alias y */, const float* b /* may alias y */,
                                                                 const float* __restrict__ bias /* added to b, may be NULL */,
                                                                 const int32_t* __restrict__ docids, int64_t n_docs, int B,
                                                                 int L, int64_t T, int W, const float* __restrict__ gamma,
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_fwd_kernel(const float* a,
 }
 
 // the input LayerNorm on gathered feature rows with 16-byte accesses (W % 4 == 0, W <= 1024): lane owns the float4
-// chunks lane, lane + 64, ... of the row; stores the gathered row (for the backward) and the normalised row
+// chunks lane, lane + 64, ... of the row; stores the gathered row (for the backward; sum_out may be NULL) and the normalised row
 __global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_gather_v4_kernel(const float* __restrict__ feats, const int32_t* __restrict__ docids,
                                                                       int64_t n_docs, int B, int L, int64_t T, int W,
                                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_gather_v4_kernel(const flo
     v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (qd < nq) {
       if (ra != nullptr) v[k] = ld4(ra + 4 * qd);
-      st4(sum_out + n * W + 4 * qd, v[k]);
+      if (sum_out != nullptr) st4(sum_out + n * W + 4 * qd, v[k]);  // (NULL, wave-uniform: a scoring forward keeps no gathered rows)
     }
     s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
   }
@@ -137,15 +139,16 @@ __global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_gather_v4_kernel(const flo
       st4(y + n * W + c, make_float4((v[k].x - mean) * rstd * gamma[c] + beta[c], (v[k].y - mean) * rstd * gamma[c + 1] + beta[c + 1],
                                      (v[k].z - mean) * rstd * gamma[c + 2] + beta[c + 2], (v[k].w - mean) * rstd * gamma[c + 3] + beta[c + 3]));
   }
-  if (lane == 0) {
+  if (lane == 0 && mean_out != nullptr) {  // (both or neither: a scoring forward keeps no statistics)
     mean_out[n] = mean;
     rstd_out[n] = rstd;
   }
 }
 
 // the residual LayerNorms (W = d_model a multiple of 256, no gather): 16-byte accesses, NV float4 per lane
+// In place (y == a or y == b): the whole row sits in registers before the first store to y.
 template <int NV>
-__global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_fwd_v4_kernel(const float* a, const float* b /* may alias y */,
+__global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_fwd_v4_kernel(const float* a /* may alias y */, const float* b /* may alias y */,
                                                                    const float* __restrict__ bias, int64_t T,
                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                    float* __restrict__ sum_out, float* y,
@@ -166,7 +169,7 @@ __global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_fwd_v4_kernel(const float*
         bv.x += bias[c]; bv.y += bias[c + 1]; bv.z += bias[c + 2]; bv.w += bias[c + 3];  // parameters: any float offset
       }
       v[k] = make_float4(av.x + bv.x, av.y + bv.y, av.z + bv.z, av.w + bv.w);
-      st4(sum_out + n * W + c, v[k]);
+      if (sum_out != nullptr) st4(sum_out + n * W + c, v[k]);
     } else {
       v[k] = av;
     }
@@ -186,7 +189,7 @@ __global__ __launch_bounds__(SR_ROWS * 64) void sr_ln_fwd_v4_kernel(const float*
     st4(y + n * W + c, make_float4((v[k].x - mean) * rstd * gamma[c] + beta[c], (v[k].y - mean) * rstd * gamma[c + 1] + beta[c + 1],
                                    (v[k].z - mean) * rstd * gamma[c + 2] + beta[c + 2], (v[k].w - mean) * rstd * gamma[c + 3] + beta[c + 3]));
   }
-  if (lane == 0) {
+  if (lane == 0 && mean_out != nullptr) {  // (both or neither: a scoring forward keeps no statistics)
     mean_out[n] = mean;
     rstd_out[n] = rstd;
   }

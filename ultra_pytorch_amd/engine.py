@@ -662,13 +662,14 @@ class SetRankStepEngine(StepEngine):
 class SetRankEvalEngine(EvalEngine):
     def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10), metrics=("ndcg",)):
         super().__init__(shape, batch, list_size, device, topn=topn, metrics=metrics)
-        self.saved = _f32(shape.saved_bytes(self.B * self.L) // 4, device)
-        self._flag = self.saved[shape.range_flag_offset(self.B * self.L):][:1].view(torch.int32)
+        # no backward follows an evaluation forward: the scoring entry's buffer (live activations only), not `saved`
+        self.work = _f32(shape.score_bytes(self.B * self.L) // 4, device)
+        self._flag = self.work[shape.score_range_flag_offset(self.B * self.L):][:1].view(torch.int32)
         self._checked = None  # (data_ptr, version) of the parameters whose split-half planes were last looked at
 
     def run(self, params, features, n_docs, docids, labels):
         _setrank_draw(self.L)
-        hip_ops.setrank_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.saved)
+        hip_ops.setrank_score(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.work)
         # the split-half planes of a loaded checkpoint may be out of range (|w| >= 64 / 128): the forward raised the word - look
         # (validation reads its metrics on the host anyway), switch this model to the fp32 products and score again
         # ONCE per parameter version (the word is a function of the weights; a blocking .item() per validation batch put a stream
@@ -679,13 +680,13 @@ class SetRankEvalEngine(EvalEngine):
         if look and hip_ops.split_half_enabled(self.shape) and int(self._flag.item()) != 0:
             hip_ops.fall_back_to_fp32_products(self.shape, "a SetRank weight of magnitude >= 64 was loaded (the split-half weight planes "
                                                            "cover |w| < 128)")
-            hip_ops.setrank_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.saved)
+            hip_ops.setrank_score(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.work)
         self._ndcg(labels, docids, n_docs)
         return self.scores, self.ndcg
 
     def forward(self, params, features, n_docs, docids):
         _setrank_draw(self.L)
-        hip_ops.setrank_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.saved)
+        hip_ops.setrank_score(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.work)
         return self.scores
 
 

@@ -160,6 +160,14 @@ class SetRankShape:
         """Float offset in `saved` of the range word of the split-half planes (ultr_update_desc::range_flag)."""
         return int(self.lib.ultr_setrank_range_flag_offset(ctypes.byref(self.desc), n_rows))
 
+    def score_bytes(self, n_rows):
+        """Bytes of setrank_score's buffer: the live activations (their size does not grow with num_layers), the planes, the range word."""
+        return int(self.lib.ultr_setrank_score_bytes(ctypes.byref(self.desc), n_rows))
+
+    def score_range_flag_offset(self, n_rows):
+        """Float offset in setrank_score's buffer of the range word of the split-half planes."""
+        return int(self.lib.ultr_setrank_score_range_flag_offset(ctypes.byref(self.desc), n_rows))
+
 
 def setrank_dropout(rate, seed, step, stream=0, scratch=None):
     """ultr_setrank_dropout for one step: the forward reads (rate, seed, step, stream), the backward of the same step the scratch too."""
@@ -181,6 +189,12 @@ def setrank_forward(shape, params, features, n_docs, docids, B, L, scores, saved
         return
     check(shape.lib.ultr_setrank_forward(ctypes.byref(shape.desc), _p(params), _p(features), int(n_docs), _p(docids), int(B),
                                          int(L), _p(scores), _p(saved), _stream()), "ultr_setrank_forward")
+
+
+def setrank_score(shape, params, features, n_docs, docids, B, L, scores, work):
+    """The evaluation forward: setrank_forward's scores bit for bit, no record for a backward.  `work`: shape.score_bytes(B * L) bytes."""
+    check(shape.lib.ultr_setrank_score(ctypes.byref(shape.desc), _p(params), _p(features), int(n_docs), _p(docids), int(B), int(L),
+                                       _p(scores), _p(work), int(work.numel() * work.element_size()), _stream()), "ultr_setrank_score")
 
 
 def setrank_backward(shape, params, B, L, saved, dscores, loss_ws, n_loss_parts, ws, grads, dropout=None):
