@@ -46,7 +46,7 @@ def list_len(cand_docids, n_docs):
 
 
 def order_key(s):
-    """The kernel's unsigned order key of float32 scores: NaN above +inf, -0 == +0 (ndcg_list_kernel's score_key)."""
+    """The kernel's unsigned order key of float32 scores: NaN above +inf, -0 == +0 (rank_order_key, ndcg_list_kernel's too)."""
     s = np.asarray(s, np.float32)
     s = np.where(s == 0, np.float32(0), s).astype(np.float32)
     u = s.view(np.uint32).astype(np.uint64)

@@ -7,6 +7,11 @@
 // which is what torch's CPU sort yields for the all-equal padding scores).  A NaN score ranks above every number, as in torch's
 // descending sort, and a NaN in a list becomes the row minimum that its invalid labels take, as torch.min does.
 // Lists beyond the 64 KiB of LDS that four such lists share (813 documents) take metrics_long_kernel: one workgroup of 16 waves per list.
+//
+// ONE ranking core serves both kernels - stage_document, validate_chunk, count_against, place_document, rank_scans, cutoff_sums and
+// metrics_means below.  A kernel keeps what is its own: how its threads stride the list, how it reads the keys in the counting loop,
+// how it joins the row minimum and the pair count, and how its workgroups arrive at the batch means; the NDCG-only form also keeps
+// its batch-mean tail (it measured slower through metrics_means: profiles/metrics_core.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -14,16 +19,10 @@
 #include "ultr_device.h"
 #include "ultr_plan.h"
 #include "ultr_prof.h"
+#include "ultr_rank.h"
 
 #define NDCG_LPW 4
 #define NDCG_MAX_TOPN 16
-
-// the descending order of scores as an unsigned key: -0 and +0 equal, every NaN equal and above +inf
-__device__ __forceinline__ unsigned score_key(float s) {
-  if (s != s) return 0xFFFFFFFFu;
-  const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct TopN {
   int n;
@@ -54,8 +53,161 @@ static size_t ndcg_lds_bytes(int L, bool all) {
              : ((size_t)NDCG_LPW * 4 * L + 4) * sizeof(float);
 }
 
-// ultr_metrics_report's batch means, by the ONE wave that arrived last at tail.counter: lanes stride the lists, fixed-order wave reduction
-// per value; then the counter is reset and, with a host report, the values and after them the sequence word go to host-mapped memory
+// ---- the ranking core: a list's arrays in LDS are ms (masked + validated predictions, then their order keys, then - ALL - the ERR
+// terms by rank), my (validated labels), md / mi (discounted gains by predicted / ideal rank), ALL: ml (validated labels by predicted
+// rank) and mv (64-bit masks of the documents whose label was valid: ordered_pair_accuracy counts pairs of those only) ------------------
+
+// document l of list b: pad mask, the masked score out and, with the label, into LDS; the running row minimum and whether a NaN was seen
+// (score, doc id and label of a position are requested together: the kernel is a chain of dependent round trips, not bytes)
+__device__ __forceinline__ void stage_document(const float* __restrict__ scores, const float* __restrict__ labels,
+                                               const int32_t* __restrict__ docids, int64_t n_docs, int B, int L, int b, int l,
+                                               float* __restrict__ masked_out, float* ms, float* my, float& mn, bool& nan_seen) {
+  float s = scores[(int64_t)b * L + l];
+  const float y = labels[(int64_t)l * B + b];
+  if (docids != nullptr && (int64_t)docids[(int64_t)l * B + b] == n_docs) s = ULTR_PAD_SCORE;
+  if (masked_out != nullptr) masked_out[(int64_t)b * L + l] = s;
+  ms[l] = s;
+  my[l] = y;
+  mn = fminf(mn, s);
+  nan_seen = nan_seen || s != s;
+}
+
+// the 64-document chunk c, a whole wave (metrics.py:251-264): invalid labels (< 0) -> label 0, prediction rowmin - 1e-6; the validated
+// predictions become order keys (rank_order_key) in place.  ALL: the chunk's validity mask into mv
+template <bool ALL>
+__device__ __forceinline__ void validate_chunk(int c, int L, int lane, float mn, float* ms, float* my, unsigned long long* mv) {
+  unsigned* mk = reinterpret_cast<unsigned*>(ms);
+  const int l = c * 64 + lane;
+  bool ok = false;
+  if (l < L) {
+    const float y = my[l];
+    ok = y >= 0.f;
+    my[l] = ok ? y : 0.f;
+    mk[l] = rank_order_key(ok ? ms[l] : -1e-6f + mn);
+  }
+  if constexpr (ALL) {
+    const unsigned long long okm = __ballot(ok);
+    if (lane == 0) mv[c] = okm;
+  }
+}
+
+// rank by counting: document d against another one, j - into d's predicted rank rs, its ideal rank ry (ties by index) and, ALL,
+// ordered_pair_accuracy's pairs (metrics.py:531-568): label_i > label_j and score_i > score_j, j valid (vj: the mask of j's chunk).
+// Between valid documents the keys order as the masked scores compare, but for NaN, which compares false (place_document: i's half)
+// (the document and the other one's key and label travel BY VALUE: the conditions stay free of loads, and so free of branches)
+struct RankDoc {
+  int i;
+  unsigned k;
+  float y;
+};
+struct RankCount {
+  int rs, ry, pairs;
+};
+template <bool ALL>
+__device__ __forceinline__ void count_against(RankCount& n, RankDoc d, int j, unsigned kj, float yj, unsigned long long vj) {
+  n.rs += (kj > d.k || (kj == d.k && j < d.i)) ? 1 : 0;
+  n.ry += (yj > d.y || (yj == d.y && j < d.i)) ? 1 : 0;
+  if constexpr (ALL) n.pairs += (d.y > yj && d.k > kj && ((vj >> (j & 63)) & 1ull)) ? 1 : 0;
+}
+
+// the counted document to its ranks: discounted gains by predicted and by ideal rank, its index into the permutation; ALL: its label by
+// predicted rank, and its pairs into this thread's count when it is valid itself and no NaN
+template <bool ALL>
+__device__ __forceinline__ void place_document(RankDoc d, RankCount n, const unsigned long long* mv, float* ml, float* md, float* mi,
+                                               int32_t* __restrict__ order_out, int b, int L, int& opa) {
+  if constexpr (ALL) {
+    if (((mv[d.i >> 6] >> (d.i & 63)) & 1ull) && d.k != 0xFFFFFFFFu) opa += n.pairs;
+    ml[n.rs] = d.y;
+  }
+  const float gain = exp2f(d.y) - 1.0f;  // weights = 1: gains = 2^label - 1 (metrics.py:213)
+  md[n.rs] = gain * (1.0f / log2f((float)n.rs + 2.0f));
+  mi[n.ry] = gain * (1.0f / log2f((float)n.ry + 2.0f));
+  if (order_out != nullptr) order_out[(int64_t)b * L + n.rs] = d.i;
+}
+
+// ONE wave over the labels by predicted rank: the metrics without a cutoff into whole[] (by ULTR_METRIC_* id; the NDCG, DCG and ERR
+// entries are filled per cutoff), and the ERR terms by rank into me (over the order keys, which nothing reads any more).  opa_lane:
+// this lane's share of the list's correctly ordered pairs (below 2^24 per addend the short kernel passes, one exact addend from the
+// long one: the wave sum takes them in lane order either way)
+__device__ __forceinline__ void rank_scans(const float* ml, float* me, int L, int lane, float pow_max, float opa_lane,
+                                           float (&whole)[ULTR_MAX_METRICS]) {
+  float carry = 1.f, ap = 0.f, pos_sum = 0.f, lab_sum = 0.f;  // prod(1 - rel) of the chunks before, sum of precision-at-hit, ARP's sums
+  int hits = 0, first = L;                                    // relevant documents so far, the first one's rank
+  for (int r0 = 0; r0 < L; r0 += 64) {
+    const int r = r0 + lane;
+    const float y = r < L ? ml[r] : 0.f;
+    const bool hit = r < L && y >= 1.f;
+    const float rel = (exp2f(y) - 1.0f) / pow_max;  // metrics.py:320 (0 behind the list's end)
+    // the exclusive product of 1 - rel along the rank, formed directly (the reference's cumprod / (1 - rel) is NaN at rel == 1):
+    // an inclusive scan over the wave, shifted by one lane, times the carry of the chunks before
+    float p = 1.0f - rel;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const float t = __shfl_up(p, d);
+      if (lane >= d) p *= t;
+    }
+    float excl = __shfl_up(p, 1);
+    if (lane == 0) excl = 1.f;
+    excl *= carry;
+    carry *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), 63));
+    if (r < L) me[r] = rel * excl * (1.0f / (float)(r + 1));
+    // mean_average_precision (metrics.py:408-453): hits up to and including this rank / (rank + 1) at every hit
+    const unsigned long long hm = __ballot(hit);
+    if (hit) ap += (float)(hits + __popcll(hm & ((2ull << lane) - 1ull))) / (float)(r + 1);
+    if (first == L && hm != 0) first = r0 + __ffsll((long long)hm) - 1;
+    hits += __popcll(hm);
+    pos_sum += (float)(r + 1) * y;
+    lab_sum += y;
+  }
+  float sums[4] = {ap, pos_sum, lab_sum, opa_lane};
+  wave_sum_n<4>(sums);
+  whole[ULTR_METRIC_MRR] = first < L ? 1.0f / (float)(first + 1) : 0.f;
+  whole[ULTR_METRIC_MAP] = hits > 0 ? sums[0] / (float)hits : 0.f;
+  whole[ULTR_METRIC_ARP] = sums[2] == 0.f ? 0.f : sums[1] / sums[2];  // _safe_div
+  whole[ULTR_METRIC_PRECISION] = (float)hits / (float)L;
+  whole[ULTR_METRIC_OPA] = sums[3] / ((float)L * (float)L);
+  wave_lds_sync();
+}
+
+// ONE wave: per cutoff the sums over the ranked arrays and list b's values into per_list.  ALL: the rows sel picks, [sel.n][topn.n],
+// written through; otherwise NDCG alone, [topn.n], written through when a batch-mean tail follows in this launch (through)
+template <bool ALL>
+__device__ __forceinline__ void cutoff_sums(const float* md, const float* mi, const float* me, int L, int lane, int b, int B,
+                                            const TopN& topn, const MetricSel& sel, float (&whole)[ULTR_MAX_METRICS],
+                                            float* __restrict__ per_list, int width, bool through) {
+  for (int k = 0; k < topn.n; ++k) {
+    const int n = topn.v[k] < L ? topn.v[k] : L;  // topn clipped to the list size (metrics.py:249)
+    float d = 0.f, id = 0.f, e = 0.f;
+    for (int r = lane; r < n; r += 64) {
+      d += md[r];
+      id += mi[r];
+      if constexpr (ALL) e += me[r];
+    }
+    d = wave_sum(d);
+    id = wave_sum(id);
+    if constexpr (ALL) e = wave_sum(e);
+    if (lane == 0) {
+      const float v = (id == 0.f) ? 0.f : d / id;  // _safe_div
+      if constexpr (ALL) {
+        whole[ULTR_METRIC_NDCG] = v;
+        whole[ULTR_METRIC_DCG] = d;
+        whole[ULTR_METRIC_ERR] = e;
+        const Src pl = make_src(per_list, (int64_t)B * width);
+        for (int m = 0; m < sel.n; ++m) {
+          float x = 0.f;
+#pragma unroll
+          for (int q = 0; q < ULTR_MAX_METRICS; ++q) x = sel.id[m] == q ? whole[q] : x;  // (registers: no indexed private array)
+          coh_st1(pl, (unsigned)(((int64_t)b * width + m * topn.n + k) * 4), x);
+        }
+      } else if (through) coh_st1(make_src(per_list, (int64_t)B * width), (unsigned)(((int64_t)b * width + k) * 4), v);
+      else per_list[(int64_t)b * width + k] = v;
+    }
+  }
+}
+
+// the metric launch's batch means, by the ONE wave that arrived last at tail.counter: lanes stride the lists, fixed-order wave reduction
+// per value (ndcg_mean_kernel's order); then the counter is reset and, with a host report, the values and after them the sequence word
+// go to host-mapped memory
 __device__ __forceinline__ void metrics_means(const float* __restrict__ per_list, int B, int width, int lane, const NdcgTail& tail) {
   const Src pl = make_src(per_list, (int64_t)B * width);
   for (int w = 0; w < width; ++w) {
@@ -86,16 +238,15 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
                                                                  int32_t* __restrict__ order_out,
                                                                  float* __restrict__ masked_out, NdcgTail tail, MetricSel sel) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sm_s = smem;                 // [LPW][L] masked + validated predictions (then their order keys; ALL: then the ERR terms by rank)
-  float* sm_y = sm_s + NDCG_LPW * L;  // [LPW][L] validated labels
-  float* sm_d = sm_y + NDCG_LPW * L;  // [LPW][L] discounted gains by predicted rank
-  float* sm_i = sm_d + NDCG_LPW * L;  // [LPW][L] discounted gains by ideal rank
-  float* sm_l = sm_i + NDCG_LPW * L;  // ALL: [LPW][L] validated labels by predicted rank
+  float* sm_s = smem;                 // [LPW][L] ms
+  float* sm_y = sm_s + NDCG_LPW * L;  // [LPW][L] my
+  float* sm_d = sm_y + NDCG_LPW * L;  // [LPW][L] md
+  float* sm_i = sm_d + NDCG_LPW * L;  // [LPW][L] mi
+  float* sm_l = sm_i + NDCG_LPW * L;  // ALL: [LPW][L] ml
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x * NDCG_LPW + wave;
   const int nch = (L + 63) >> 6;  // 64-document chunks of a list
-  // ALL: [LPW][nch] 64-bit masks of the documents whose label was valid (ordered_pair_accuracy counts pairs of those only)
-  unsigned long long* sm_v = reinterpret_cast<unsigned long long*>(sm_l + (ALL ? NDCG_LPW * L : 0));
+  unsigned long long* sm_v = reinterpret_cast<unsigned long long*>(sm_l + (ALL ? NDCG_LPW * L : 0));  // ALL: [LPW][nch] mv
   unsigned* arrived = reinterpret_cast<unsigned*>(sm_v + (ALL ? NDCG_LPW * nch : 0));  // waves of this workgroup that finished their list (ultr_ndcg_report)
   if (tail.counter != nullptr) {
     if (threadIdx.x == 0) *arrived = 0u;
@@ -108,142 +259,32 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
   float* mi = sm_i + wave * L;
   float* ml = sm_l + wave * L;
   unsigned long long* mv = sm_v + wave * nch;
-  // pad mask, then metrics.py:251-264: invalid labels (< 0) -> label 0, prediction rowmin - 1e-6
-  // (score, doc id and label of a position are requested together: the kernel is a chain of dependent round trips, not bytes)
   float mn = INFINITY;
   bool nan_seen = false;
-  for (int l = lane; l < L; l += 64) {
-    float s = scores[(int64_t)b * L + l];
-    const float y = labels[(int64_t)l * B + b];
-    if (docids != nullptr && (int64_t)docids[(int64_t)l * B + b] == n_docs) s = ULTR_PAD_SCORE;
-    if (masked_out != nullptr) masked_out[(int64_t)b * L + l] = s;
-    ms[l] = s;
-    my[l] = y;
-    mn = fminf(mn, s);
-    nan_seen = nan_seen || s != s;
-  }
+  for (int l = lane; l < L; l += 64) stage_document(scores, labels, docids, n_docs, B, L, b, l, masked_out, ms, my, mn, nan_seen);
   mn = -wave_max(-mn);
   if (__ballot(nan_seen) != 0) mn = __builtin_nanf("");  // torch.min propagates a NaN (fminf drops it)
-  unsigned* mk = reinterpret_cast<unsigned*>(ms);  // the validated predictions, from here on as order keys (score_key)
-  for (int l0 = 0; l0 < L; l0 += 64) {
-    const int l = l0 + lane;
-    bool ok = false;
-    if (l < L) {
-      const float y = my[l];
-      ok = y >= 0.f;
-      my[l] = ok ? y : 0.f;
-      mk[l] = score_key(ok ? ms[l] : -1e-6f + mn);
-    }
-    if constexpr (ALL) {
-      const unsigned long long okm = __ballot(ok);
-      if (lane == 0) mv[l0 >> 6] = okm;
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  for (int l0 = 0; l0 < L; l0 += 64) validate_chunk<ALL>(l0 >> 6, L, lane, mn, ms, my, mv);
+  wave_lds_sync();
+  const unsigned* mk = reinterpret_cast<const unsigned*>(ms);
   int opa = 0;  // ALL: this lane's correctly ordered pairs
   for (int i = lane; i < L; i += 64) {
-    const unsigned ki = mk[i];
-    const float yi = my[i];
-    int rs = 0, ry = 0, pairs = 0;
+    const RankDoc d{i, mk[i], my[i]};
+    RankCount n{0, 0, 0};
     unsigned long long vj = 0;
     for (int j = 0; j < L; ++j) {
-      const unsigned kj = mk[j];
-      const float yj = my[j];
-      rs += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
-      ry += (yj > yi || (yj == yi && j < i)) ? 1 : 0;
       if constexpr (ALL) {
-        // ordered_pair_accuracy (metrics.py:531-568): label_i > label_j and score_i > score_j, j valid (i: below).  Between valid
-        // documents the keys order as the masked scores compare, but for NaN, which compares false
         if ((j & 63) == 0) vj = mv[j >> 6];
-        pairs += (yi > yj && ki > kj && ((vj >> (j & 63)) & 1ull)) ? 1 : 0;
       }
+      count_against<ALL>(n, d, j, mk[j], my[j], vj);
     }
-    if constexpr (ALL) {
-      if (((mv[i >> 6] >> (i & 63)) & 1ull) && ki != 0xFFFFFFFFu) opa += pairs;
-      ml[rs] = yi;
-    }
-    const float gain = exp2f(yi) - 1.0f;  // weights = 1: gains = 2^label - 1 (metrics.py:213)
-    md[rs] = gain * (1.0f / log2f((float)rs + 2.0f));
-    mi[ry] = gain * (1.0f / log2f((float)ry + 2.0f));
-    if (order_out != nullptr) order_out[(int64_t)b * L + rs] = i;
+    place_document<ALL>(d, n, mv, ml, md, mi, order_out, b, L, opa);
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  // ALL: the metrics without a cutoff, and the ERR terms by rank (over the order keys, which nothing reads any more)
-  float whole[ULTR_MAX_METRICS] = {};  // by ULTR_METRIC_* id (the NDCG, DCG and ERR entries are filled per cutoff)
-  float* me = ms;
-  if constexpr (ALL) {
-    float carry = 1.f, ap = 0.f, pos_sum = 0.f, lab_sum = 0.f;  // prod(1 - rel) of the chunks before, sum of precision-at-hit, ARP's sums
-    int hits = 0, first = L;                                    // relevant documents so far, the first one's rank
-    for (int r0 = 0; r0 < L; r0 += 64) {
-      const int r = r0 + lane;
-      const float y = r < L ? ml[r] : 0.f;
-      const bool hit = r < L && y >= 1.f;
-      const float rel = (exp2f(y) - 1.0f) / sel.pow_max;  // metrics.py:320 (0 behind the list's end)
-      // the exclusive product of 1 - rel along the rank, formed directly (the reference's cumprod / (1 - rel) is NaN at rel == 1):
-      // an inclusive scan over the wave, shifted by one lane, times the carry of the chunks before
-      float p = 1.0f - rel;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const float t = __shfl_up(p, d);
-        if (lane >= d) p *= t;
-      }
-      float excl = __shfl_up(p, 1);
-      if (lane == 0) excl = 1.f;
-      excl *= carry;
-      carry *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), 63));
-      if (r < L) me[r] = rel * excl * (1.0f / (float)(r + 1));
-      // mean_average_precision (metrics.py:408-453): hits up to and including this rank / (rank + 1) at every hit
-      const unsigned long long hm = __ballot(hit);
-      if (hit) ap += (float)(hits + __popcll(hm & ((2ull << lane) - 1ull))) / (float)(r + 1);
-      if (first == L && hm != 0) first = r0 + __ffsll((long long)hm) - 1;
-      hits += __popcll(hm);
-      pos_sum += (float)(r + 1) * y;
-      lab_sum += y;
-    }
-    float sums[4] = {ap, pos_sum, lab_sum, (float)opa};  // (the pair count is below 2^24: exact)
-    wave_sum_n<4>(sums);
-    whole[ULTR_METRIC_MRR] = first < L ? 1.0f / (float)(first + 1) : 0.f;
-    whole[ULTR_METRIC_MAP] = hits > 0 ? sums[0] / (float)hits : 0.f;
-    whole[ULTR_METRIC_ARP] = sums[2] == 0.f ? 0.f : sums[1] / sums[2];  // _safe_div
-    whole[ULTR_METRIC_PRECISION] = (float)hits / (float)L;
-    whole[ULTR_METRIC_OPA] = sums[3] / ((float)L * (float)L);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
+  wave_lds_sync();
+  float whole[ULTR_MAX_METRICS] = {};
+  if constexpr (ALL) rank_scans(ml, ms, L, lane, sel.pow_max, (float)opa, whole);  // (the pair count is below 2^24: exact)
   const int width = ALL ? sel.n * topn.n : topn.n;  // floats of a list in per_list, and of the batch means
-  for (int k = 0; k < topn.n; ++k) {
-    const int n = topn.v[k] < L ? topn.v[k] : L;  // topn clipped to the list size (metrics.py:249)
-    float d = 0.f, id = 0.f, e = 0.f;
-    for (int r = lane; r < n; r += 64) {
-      d += md[r];
-      id += mi[r];
-      if constexpr (ALL) e += me[r];
-    }
-    d = wave_sum(d);
-    id = wave_sum(id);
-    if constexpr (ALL) e = wave_sum(e);
-    if (lane == 0) {
-      const float v = (id == 0.f) ? 0.f : d / id;  // _safe_div
-      if constexpr (ALL) {
-        whole[ULTR_METRIC_NDCG] = v;
-        whole[ULTR_METRIC_DCG] = d;
-        whole[ULTR_METRIC_ERR] = e;
-        const Src pl = make_src(per_list, (int64_t)B * width);
-        for (int m = 0; m < sel.n; ++m) {
-          float x = 0.f;
-#pragma unroll
-          for (int q = 0; q < ULTR_MAX_METRICS; ++q) x = sel.id[m] == q ? whole[q] : x;  // (registers: no indexed private array)
-          coh_st1(pl, (unsigned)(((int64_t)b * width + m * topn.n + k) * 4), x);
-        }
-      } else if (tail.counter != nullptr) coh_st1(make_src(per_list, (int64_t)B * topn.n), (unsigned)(((int64_t)b * topn.n + k) * 4), v);  // written through
-      else per_list[(int64_t)b * topn.n + k] = v;
-    }
-  }
+  cutoff_sums<ALL>(md, mi, ms, L, lane, b, B, topn, sel, whole, per_list, width, tail.counter != nullptr);
   if (tail.counter == nullptr) return;
   // ---- the last workgroup to arrive forms the batch means: every wave waits for its write-through stores to be acknowledged, the
   // workgroup's waves meet (waves without a list left the kernel at its top: the counter counts LISTS, a workgroup adds its own
@@ -263,6 +304,9 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
     metrics_means(per_list, B, width, lane, tail);
     return;
   }
+  // NDCG alone keeps a tail of its own: its at most 16 means wait in registers and leave together, where metrics_means stores each
+  // value before it loads for the next.  Through metrics_means this launch measured about 0.8 us slower on an 8.5 us kernel
+  // (profiles/metrics_core.md).  The same sums in the same order; the sequence word is word 16 of this report
   const Src pl = make_src(per_list, (int64_t)B * topn.n);
   float vals[NDCG_MAX_TOPN];
   for (int k = 0; k < topn.n; ++k) {
@@ -284,7 +328,8 @@ __global__ __launch_bounds__(NDCG_LPW * 64) void ndcg_list_kernel(const float* _
 
 // ---- lists beyond the 64 KiB that four single-wave lists share: ONE workgroup of METRICS_LONG_WAVES waves per list, that list's arrays
 // in up to the whole 160 KiB of LDS.  ndcg_list_kernel<true>'s contract and, wherever both take a list, its bits: the row minimum is a
-// min (no order), the ranks and the pair count are integers, and every float sum is formed by wave 0 alone in that kernel's loop order.
+// min (no order), the ranks and the pair count are integers, and every float sum is formed by wave 0 alone, by the functions that
+// kernel calls.
 #define METRICS_LONG_WAVES 16
 #define METRICS_LONG_THREADS (METRICS_LONG_WAVES * 64)
 #define METRICS_LDS_MAX (160 * 1024)
@@ -309,31 +354,22 @@ __global__ __launch_bounds__(METRICS_LONG_THREADS) void metrics_long_kernel(cons
                                                                             NdcgTail tail, MetricSel sel) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int Lp = (L + 3) & ~3;
-  float* ms = smem;     // [Lp] masked + validated predictions (then their order keys, then the ERR terms by rank)
-  float* my = ms + Lp;  // [Lp] validated labels
-  float* md = my + Lp;  // [Lp] discounted gains by predicted rank
-  float* mi = md + Lp;  // [Lp] discounted gains by ideal rank
-  float* ml = mi + Lp;  // [Lp] validated labels by predicted rank
+  float* ms = smem;     // [Lp] each
+  float* my = ms + Lp;
+  float* md = my + Lp;
+  float* mi = md + Lp;
+  float* ml = mi + Lp;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
   const int nch = (L + 63) >> 6;
-  unsigned long long* mv = reinterpret_cast<unsigned long long*>(ml + Lp);  // [nch] 64-bit masks of the documents whose label was valid
+  unsigned long long* mv = reinterpret_cast<unsigned long long*>(ml + Lp);  // [nch]
   float* w_min = reinterpret_cast<float*>(mv + nch);                        // [waves] each wave's minimum
   int* w_nan = reinterpret_cast<int*>(w_min + METRICS_LONG_WAVES);          // [waves] whether it saw a NaN
   int* w_opa = w_nan + METRICS_LONG_WAVES;                                  // [waves] its correctly ordered pairs
-  // pad mask, row minimum (ndcg_list_kernel's first loop, all waves striding the list)
+  // all waves stride the list; the row minimum and the NaN flag meet in LDS
   float mn = INFINITY;
   bool nan_seen = false;
-  for (int l = tid; l < L; l += METRICS_LONG_THREADS) {
-    float s = scores[(int64_t)b * L + l];
-    const float y = labels[(int64_t)l * B + b];
-    if (docids != nullptr && (int64_t)docids[(int64_t)l * B + b] == n_docs) s = ULTR_PAD_SCORE;
-    if (masked_out != nullptr) masked_out[(int64_t)b * L + l] = s;
-    ms[l] = s;
-    my[l] = y;
-    mn = fminf(mn, s);
-    nan_seen = nan_seen || s != s;
-  }
+  for (int l = tid; l < L; l += METRICS_LONG_THREADS) stage_document(scores, labels, docids, n_docs, B, L, b, l, masked_out, ms, my, mn, nan_seen);
   mn = -wave_max(-mn);
   const unsigned long long nan_lanes = __ballot(nan_seen);
   if (lane == 0) {
@@ -348,127 +384,44 @@ __global__ __launch_bounds__(METRICS_LONG_THREADS) void metrics_long_kernel(cons
     any_nan |= w_nan[w];
   }
   if (any_nan != 0) mn = __builtin_nanf("");  // torch.min propagates a NaN (fminf drops it)
-  // label validation, a 64-document chunk per wave at a time
-  unsigned* mk = reinterpret_cast<unsigned*>(ms);  // the validated predictions, from here on as order keys (score_key)
-  for (int c = wave; c < nch; c += METRICS_LONG_WAVES) {
-    const int l = c * 64 + lane;
-    bool ok = false;
-    if (l < L) {
-      const float y = my[l];
-      ok = y >= 0.f;
-      my[l] = ok ? y : 0.f;
-      mk[l] = score_key(ok ? ms[l] : -1e-6f + mn);
-    }
-    const unsigned long long okm = __ballot(ok);
-    if (lane == 0) mv[c] = okm;
-  }
+  for (int c = wave; c < nch; c += METRICS_LONG_WAVES) validate_chunk<true>(c, L, lane, mn, ms, my, mv);
   __syncthreads();
   // rank by counting: document i of a thread against every j, four j per 16-byte LDS read (one address per wave: a broadcast)
+  const unsigned* mk = reinterpret_cast<const unsigned*>(ms);
   int opa = 0;
   const int L4 = L & ~3;
   for (int i = tid; i < L; i += METRICS_LONG_THREADS) {
-    const unsigned ki = mk[i];
-    const float yi = my[i];
-    int rs = 0, ry = 0, pairs = 0;
+    const RankDoc d{i, mk[i], my[i]};
+    RankCount n{0, 0, 0};
     unsigned long long vj = 0;
-    auto count = [&](int j, unsigned kj, float yj) {
-      rs += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
-      ry += (yj > yi || (yj == yi && j < i)) ? 1 : 0;
-      pairs += (yi > yj && ki > kj && ((vj >> (j & 63)) & 1ull)) ? 1 : 0;  // ordered_pair_accuracy, as ndcg_list_kernel counts it
-    };
     for (int j = 0; j < L4; j += 4) {
       const uint4 k4 = *reinterpret_cast<const uint4*>(mk + j);
       const float4 y4 = *reinterpret_cast<const float4*>(my + j);
       if ((j & 63) == 0) vj = mv[j >> 6];
-      count(j, k4.x, y4.x);
-      count(j + 1, k4.y, y4.y);
-      count(j + 2, k4.z, y4.z);
-      count(j + 3, k4.w, y4.w);
+      count_against<true>(n, d, j, k4.x, y4.x, vj);
+      count_against<true>(n, d, j + 1, k4.y, y4.y, vj);
+      count_against<true>(n, d, j + 2, k4.z, y4.z, vj);
+      count_against<true>(n, d, j + 3, k4.w, y4.w, vj);
     }
     for (int j = L4; j < L; ++j) {
       if ((j & 63) == 0) vj = mv[j >> 6];
-      count(j, mk[j], my[j]);
+      count_against<true>(n, d, j, mk[j], my[j], vj);
     }
-    if (((mv[i >> 6] >> (i & 63)) & 1ull) && ki != 0xFFFFFFFFu) opa += pairs;
-    ml[rs] = yi;
-    const float gain = exp2f(yi) - 1.0f;  // weights = 1: gains = 2^label - 1 (metrics.py:213)
-    md[rs] = gain * (1.0f / log2f((float)rs + 2.0f));
-    mi[ry] = gain * (1.0f / log2f((float)ry + 2.0f));
-    if (order_out != nullptr) order_out[(int64_t)b * L + rs] = i;
+    place_document<true>(d, n, mv, ml, md, mi, order_out, b, L, opa);
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) opa += __shfl_xor(opa, d);
   if (lane == 0) w_opa[wave] = opa;
   __syncthreads();  // the last barrier: every wave is still here
   if (wave != 0) return;
-  // ---- wave 0 alone: ndcg_list_kernel<true>'s scans and sums over the ranked arrays, statement for statement -------------------------
+  // ---- wave 0 alone: the scans and sums over the ranked arrays ---------------------------------------------------------------------------
   int opa_all = 0;  // an integer up to L * L / 2 < 2^31, converted once
 #pragma unroll
   for (int w = 0; w < METRICS_LONG_WAVES; ++w) opa_all += w_opa[w];
   float whole[ULTR_MAX_METRICS] = {};
-  float* me = ms;  // the ERR terms by rank (over the order keys, which nothing reads any more)
-  {
-    float carry = 1.f, ap = 0.f, pos_sum = 0.f, lab_sum = 0.f;
-    int hits = 0, first = L;
-    for (int r0 = 0; r0 < L; r0 += 64) {
-      const int r = r0 + lane;
-      const float y = r < L ? ml[r] : 0.f;
-      const bool hit = r < L && y >= 1.f;
-      const float rel = (exp2f(y) - 1.0f) / sel.pow_max;
-      float p = 1.0f - rel;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const float t = __shfl_up(p, d);
-        if (lane >= d) p *= t;
-      }
-      float excl = __shfl_up(p, 1);
-      if (lane == 0) excl = 1.f;
-      excl *= carry;
-      carry *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), 63));
-      if (r < L) me[r] = rel * excl * (1.0f / (float)(r + 1));
-      const unsigned long long hm = __ballot(hit);
-      if (hit) ap += (float)(hits + __popcll(hm & ((2ull << lane) - 1ull))) / (float)(r + 1);
-      if (first == L && hm != 0) first = r0 + __ffsll((long long)hm) - 1;
-      hits += __popcll(hm);
-      pos_sum += (float)(r + 1) * y;
-      lab_sum += y;
-    }
-    float sums[4] = {ap, pos_sum, lab_sum, lane == 0 ? (float)opa_all : 0.f};
-    wave_sum_n<4>(sums);
-    whole[ULTR_METRIC_MRR] = first < L ? 1.0f / (float)(first + 1) : 0.f;
-    whole[ULTR_METRIC_MAP] = hits > 0 ? sums[0] / (float)hits : 0.f;
-    whole[ULTR_METRIC_ARP] = sums[2] == 0.f ? 0.f : sums[1] / sums[2];  // _safe_div
-    whole[ULTR_METRIC_PRECISION] = (float)hits / (float)L;
-    whole[ULTR_METRIC_OPA] = sums[3] / ((float)L * (float)L);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
+  rank_scans(ml, ms, L, lane, sel.pow_max, lane == 0 ? (float)opa_all : 0.f, whole);
   const int width = sel.n * topn.n;
-  for (int k = 0; k < topn.n; ++k) {
-    const int n = topn.v[k] < L ? topn.v[k] : L;  // topn clipped to the list size (metrics.py:249)
-    float d = 0.f, id = 0.f, e = 0.f;
-    for (int r = lane; r < n; r += 64) {
-      d += md[r];
-      id += mi[r];
-      e += me[r];
-    }
-    d = wave_sum(d);
-    id = wave_sum(id);
-    e = wave_sum(e);
-    if (lane == 0) {
-      whole[ULTR_METRIC_NDCG] = (id == 0.f) ? 0.f : d / id;  // _safe_div
-      whole[ULTR_METRIC_DCG] = d;
-      whole[ULTR_METRIC_ERR] = e;
-      const Src pl = make_src(per_list, (int64_t)B * width);
-      for (int m = 0; m < sel.n; ++m) {
-        float x = 0.f;
-#pragma unroll
-        for (int q = 0; q < ULTR_MAX_METRICS; ++q) x = sel.id[m] == q ? whole[q] : x;  // (registers: no indexed private array)
-        coh_st1(pl, (unsigned)(((int64_t)b * width + m * topn.n + k) * 4), x);
-      }
-    }
-  }
+  cutoff_sums<true>(md, mi, ms, L, lane, b, B, topn, sel, whole, per_list, width, true);
   // the list that arrives last forms the batch means (no workgroup waits for another)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   unsigned old = 0;
@@ -487,28 +440,39 @@ __global__ void ndcg_mean_kernel(const float* __restrict__ per_list, int B, int 
   if (lane == 0) out[k] = s / (float)B;
 }
 
+// the cutoffs of a call as the kernels' argument; false: no list, a count outside 1 .. NDCG_MAX_TOPN, or a cutoff below 1
+static bool parse_topn(const int32_t* topn, int32_t n_topn, TopN* t) {
+  if (!topn || n_topn <= 0 || n_topn > NDCG_MAX_TOPN) return false;
+  t->n = n_topn;
+  for (int k = 0; k < n_topn; ++k) {
+    if (topn[k] <= 0) return false;
+    t->v[k] = topn[k];
+  }
+  return true;
+}
+
+// THE launch of ndcg_list_kernel<false>: per-list values alone (tail.counter == NULL), or with the batch means and the report
+static int ndcg_launch(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch, int32_t list_size,
+                       const int32_t* topn, int32_t n_topn, int32_t* order_out, float* masked_out, float* ndcg_ws, NdcgTail tail,
+                       hipStream_t st) {
+  TopN t;
+  if (!scores || !labels || !ndcg_ws || batch <= 0 || list_size <= 0 || !parse_topn(topn, n_topn, &t)) return ULTR_E_BADARG;
+  const size_t lds = ndcg_lds_bytes(list_size, false);
+  if (lds > 64 * 1024) return ULTR_E_UNSUPPORTED;
+  UltrProfScope prof(ULTR_K_NDCG, st);
+  ULTR_LAUNCH(prof, ndcg_list_kernel<false>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
+              n_docs, (int)batch, (int)list_size, t, ndcg_ws, order_out, masked_out, tail, MetricSel{});
+  return (int)hipGetLastError();
+}
+
 extern "C" int ultr_ndcg(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,
                          int32_t list_size, const int32_t* topn, int32_t n_topn, float* ndcg_out, int32_t* order_out,
                          float* masked_out, float* ndcg_ws, void* stream) {
-  if (!scores || !labels || !topn || !ndcg_out || !ndcg_ws || batch <= 0 || list_size <= 0 || n_topn <= 0 ||
-      n_topn > NDCG_MAX_TOPN)
-    return ULTR_E_BADARG;
-  TopN t;
-  t.n = n_topn;
-  for (int k = 0; k < n_topn; ++k) {
-    if (topn[k] <= 0) return ULTR_E_BADARG;
-    t.v[k] = topn[k];
-  }
-  const size_t lds = ndcg_lds_bytes(list_size, false);
-  if (lds > 64 * 1024) return ULTR_E_UNSUPPORTED;
+  if (!ndcg_out) return ULTR_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
-  {
-    UltrProfScope prof(ULTR_K_NDCG, st);
-    ULTR_LAUNCH(prof, ndcg_list_kernel<false>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
-                n_docs, (int)batch, (int)list_size, t, ndcg_ws, order_out, masked_out, NdcgTail{nullptr, nullptr, nullptr, 0u}, MetricSel{});
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  const int rc = ndcg_launch(scores, labels, docids, n_docs, batch, list_size, topn, n_topn, order_out, masked_out, ndcg_ws,
+                             NdcgTail{nullptr, nullptr, nullptr, 0u}, st);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(ndcg_mean_kernel, dim3(n_topn), dim3(64), 0, st, (const float*)ndcg_ws, (int)batch, (int)n_topn,
                      ndcg_out);
   return (int)hipGetLastError();
@@ -518,22 +482,9 @@ extern "C" int ultr_ndcg(const float* scores, const float* labels, const int32_t
 extern "C" int ultr_ndcg_report(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, int32_t batch,
                                 int32_t list_size, const int32_t* topn, int32_t n_topn, float* ndcg_out, int32_t* order_out,
                                 float* masked_out, float* ndcg_ws, uint32_t* counter, float* host_report, uint32_t seq, void* stream) {
-  if (!scores || !labels || !topn || !ndcg_out || !ndcg_ws || !counter || batch <= 0 || list_size <= 0 || n_topn <= 0 ||
-      n_topn > NDCG_MAX_TOPN)
-    return ULTR_E_BADARG;
-  TopN t;
-  t.n = n_topn;
-  for (int k = 0; k < n_topn; ++k) {
-    if (topn[k] <= 0) return ULTR_E_BADARG;
-    t.v[k] = topn[k];
-  }
-  const size_t lds = ndcg_lds_bytes(list_size, false);
-  if (lds > 64 * 1024) return ULTR_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  UltrProfScope prof(ULTR_K_NDCG, st);
-  ULTR_LAUNCH(prof, ndcg_list_kernel<false>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
-              n_docs, (int)batch, (int)list_size, t, ndcg_ws, order_out, masked_out, NdcgTail{counter, ndcg_out, host_report, seq}, MetricSel{});
-  return (int)hipGetLastError();
+  if (!ndcg_out || !counter) return ULTR_E_BADARG;
+  return ndcg_launch(scores, labels, docids, n_docs, batch, list_size, topn, n_topn, order_out, masked_out, ndcg_ws,
+                     NdcgTail{counter, ndcg_out, host_report, seq}, (hipStream_t)stream);
 }
 
 // ONE launch for any of the eight metrics of utils/metrics.py: out [n_metrics][n_topn] in the order of metric_ids (include/ultr_hip.h).
@@ -543,15 +494,10 @@ static int metrics_launch(const float* scores, const float* labels, const int32_
                           const int32_t* topn, int32_t n_topn, const int32_t* metric_ids, int32_t n_metrics, float max_label, float* out,
                           int32_t* order_out, float* masked_out, float* ws, uint32_t* counter, float* host_report, uint32_t seq, void* stream,
                           bool long_only) {
-  if (!scores || !labels || !topn || !metric_ids || !out || !ws || !counter || batch <= 0 || list_size <= 0 || n_topn <= 0 ||
-      n_topn > NDCG_MAX_TOPN || n_metrics <= 0 || n_metrics > ULTR_MAX_METRICS || !(fabsf(max_label) < INFINITY))
-    return ULTR_E_BADARG;
   TopN t;
-  t.n = n_topn;
-  for (int k = 0; k < n_topn; ++k) {
-    if (topn[k] <= 0) return ULTR_E_BADARG;
-    t.v[k] = topn[k];
-  }
+  if (!scores || !labels || !metric_ids || !out || !ws || !counter || batch <= 0 || list_size <= 0 || n_metrics <= 0 ||
+      n_metrics > ULTR_MAX_METRICS || !(fabsf(max_label) < INFINITY) || !parse_topn(topn, n_topn, &t))
+    return ULTR_E_BADARG;
   MetricSel sel{};
   sel.n = n_metrics;
   sel.pow_max = exp2f(max_label);
@@ -565,11 +511,12 @@ static int metrics_launch(const float* scores, const float* labels, const int32_
   // (the per-list block is addressed with 32-bit byte offsets through a buffer descriptor)
   if (list_size > metrics_long_max_list() || (int64_t)batch * n_metrics * n_topn * 4 > INT32_MAX) return ULTR_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
+  const NdcgTail tail{counter, out, host_report, seq};
   const size_t lds = ndcg_lds_bytes(list_size, true);
   if (!long_only && lds <= 64 * 1024) {
     UltrProfScope prof(ULTR_K_NDCG, st);
     ULTR_LAUNCH(prof, ndcg_list_kernel<true>, dim3((batch + NDCG_LPW - 1) / NDCG_LPW), dim3(NDCG_LPW * 64), lds, st, scores, labels, docids,
-                n_docs, (int)batch, (int)list_size, t, ws, order_out, masked_out, NdcgTail{counter, out, host_report, seq}, sel);
+                n_docs, (int)batch, (int)list_size, t, ws, order_out, masked_out, tail, sel);
     return (int)hipGetLastError();
   }
   const size_t lds_long = metrics_long_lds_bytes(list_size);
@@ -578,7 +525,7 @@ static int metrics_launch(const float* scores, const float* labels, const int32_
     return ULTR_E_UNSUPPORTED;
   UltrProfScope prof(ULTR_K_NDCG, st);
   ULTR_LAUNCH(prof, metrics_long_kernel, dim3((unsigned)batch), dim3(METRICS_LONG_THREADS), lds_long, st, scores, labels, docids, n_docs,
-              (int)batch, (int)list_size, t, ws, order_out, masked_out, NdcgTail{counter, out, host_report, seq}, sel);
+              (int)batch, (int)list_size, t, ws, order_out, masked_out, tail, sel);
   return (int)hipGetLastError();
 }
 

@@ -8,7 +8,7 @@
 //
 // One wavefront per batch slot, as click_draw.  Per slot of the re-rank:
 //   list_len = 1 + the last non-PAD position (interior PADs take part with their score, the model's score of the zero row);
-//   keys: deterministic - the score as an unsigned order key (score_key: NaN above +inf, -0 == +0);
+//   keys: deterministic - the score as an unsigned order key (rank_order_key: NaN above +inf, -0 == +0);
 //         stochastic    - the exponential race tau (s - max) - log E, E = -log(1 - u) ~ Exp(1): sorting these keys descending
 //                         draws a ranking with exactly the Plackett-Luce distribution of sequential sampling without replacement
 //                         (np.random.choice(replace=False, p)); a document whose fp32 probability exp(tau (s - max)) / sum is 0

@@ -334,6 +334,26 @@ METRIC_IDS = {"ndcg": 0, "dcg": 1, "mrr": 2, "err": 3, "map": 4, "arp": 5, "prec
 _METRICS_SEQ_WORD = 8 * 16  # ultr_metrics_report's sequence word in the host report (ultr_ndcg_report's is 16)
 
 
+def _metric_ids(metrics):
+    """The ULTR_METRIC_* ids of a tuple of distinct RankingMetricKey names, as the metric launch takes them."""
+    unknown = [m for m in metrics if m not in METRIC_IDS]
+    if unknown or len(set(metrics)) != len(metrics) or not metrics:
+        raise ValueError("metrics must be distinct keys of %s, got %r" % (sorted(METRIC_IDS), metrics))
+    return (ctypes.c_int32 * len(metrics))(*[METRIC_IDS[m] for m in metrics])
+
+
+def _wait_report(u, word, seq, timeout_s, noun):
+    """Spin until word `word` of a report in host-mapped memory (u: its uint32 view) carries the launch's sequence number."""
+    spins, t0 = 0, None
+    while int(u[word]) != seq:
+        spins += 1
+        if spins & 0x3FF == 0:
+            now = time.perf_counter()
+            t0 = now if t0 is None else t0
+            if now - t0 > timeout_s:
+                raise _lib.UltrHipError("no %s report from the GPU within %.0f s" % (noun, timeout_s))
+
+
 def metrics_fit_short(list_size):
     """Whether the metric launch's kernel of one wave per list takes this list size (csrc/ultr_metrics.hip ndcg_lds_bytes: 64 KiB of LDS
     for four lists) - the routing threshold of ultr_metrics_report, 813 documents."""
@@ -378,11 +398,8 @@ class EvalEngine:
         # ("ndcg",) beyond the NDCG launch's 1023 documents: the metric launch with the one id (the same arithmetic in the same order)
         self._all = self.metrics != ("ndcg",) or not ndcg_fit(self.L)
         if self._all:
-            unknown = [m for m in self.metrics if m not in METRIC_IDS]
-            if unknown or len(set(self.metrics)) != len(self.metrics) or not self.metrics:
-                raise ValueError("metrics must be distinct keys of %s, got %r" % (sorted(METRIC_IDS), self.metrics))
+            self._ids_arr = _metric_ids(self.metrics)
             nm, nt = len(self.metrics), len(self.topn)
-            self._ids_arr = (ctypes.c_int32 * nm)(*[METRIC_IDS[m] for m in self.metrics])
             self.metric_out = _f32(nm * nt, device).view(nm, nt)  # batch means, a row per metric in the order asked
             self.metric_ws = _f32(self.B * nm * nt, device).view(self.B, nm, nt)  # per-list values
             # (self.ndcg / self.ndcg_ws stay allocated; the NDCG row of this path is metric_out's)
@@ -397,39 +414,31 @@ class EvalEngine:
         ml = metrics_mod.RankingMetricKey.MAX_LABEL
         return 4.0 if ml is None else float(ml)
 
-    def _ndcg(self, labels, docids, n_docs):
+    def _launch_tail(self):
+        """The next launch's sequence number taken, the arguments every entry of this engine's path ends with - from the cutoffs to the
+        stream: the metric launch's (ultr_metrics_report, ultr_dnn_forward_metrics) or the NDCG launch's (ultr_ndcg_report,
+        ultr_dnn_forward_ndcg)."""
         self._seq = (self._seq % 0xFFFFFFFF) + 1
         if self._all:
-            _lib.check(self._lib.ultr_metrics_report(self.scores.data_ptr(), labels.data_ptr(), docids.data_ptr(), int(n_docs), self.B, self.L,
-                                                     self._topn_arr, len(self.topn), self._ids_arr, len(self.metrics), self._max_label(),
-                                                     self.metric_out.data_ptr(), self.order.data_ptr(), self.masked.data_ptr(),
-                                                     self.metric_ws.data_ptr(), self._counter.data_ptr(), self._hs.data_ptr(), self._seq,
-                                                     hip_ops.raw_stream()), "ultr_metrics_report")
-            return
-        _lib.check(self._lib.ultr_ndcg_report(self.scores.data_ptr(), labels.data_ptr(), docids.data_ptr(), int(n_docs), self.B, self.L,
-                                              self._topn_arr, len(self.topn), self.ndcg.data_ptr(), self.order.data_ptr(),
-                                              self.masked.data_ptr(), self.ndcg_ws.data_ptr(), self._counter.data_ptr(),
-                                              self._hs.data_ptr(), self._seq, hip_ops.raw_stream()), "ultr_ndcg_report")
+            outs = (self._ids_arr, len(self.metrics), self._max_label(), self.metric_out.data_ptr(), self.order.data_ptr(),
+                    self.masked.data_ptr(), self.metric_ws.data_ptr())
+        else:
+            outs = (self.ndcg.data_ptr(), self.order.data_ptr(), self.masked.data_ptr(), self.ndcg_ws.data_ptr())
+        return (self._topn_arr, len(self.topn)) + outs + (self._counter.data_ptr(), self._hs.data_ptr(), self._seq, hip_ops.raw_stream())
+
+    def _ndcg(self, labels, docids, n_docs):
+        """The metric launch alone, on self.scores."""
+        name = "ultr_metrics_report" if self._all else "ultr_ndcg_report"
+        _lib.check(getattr(self._lib, name)(self.scores.data_ptr(), labels.data_ptr(), docids.data_ptr(), int(n_docs), self.B, self.L,
+                                            *self._launch_tail()), name)
 
     def run(self, params, features, n_docs, docids, labels):
         """ONE host call (ultr_dnn_forward_ndcg): the forward, then the metric launch with its report in host-mapped memory."""
-        self._seq = (self._seq % 0xFFFFFFFF) + 1
+        name = "ultr_dnn_forward_metrics" if self._all else "ultr_dnn_forward_ndcg"
         wt = hip_ops.weight_copy(self.shape).get(params)
-        if self._all:
-            _lib.check(self._lib.ultr_dnn_forward_metrics(ctypes.byref(self.shape.desc), params.data_ptr(), wt.data_ptr() if wt is not None else None,
-                                                          features.data_ptr() if n_docs > 0 else None, int(n_docs), docids.data_ptr(),
-                                                          labels.data_ptr(), self.B, self.L, self.scores.data_ptr(), self._topn_arr,
-                                                          len(self.topn), self._ids_arr, len(self.metrics), self._max_label(),
-                                                          self.metric_out.data_ptr(), self.order.data_ptr(), self.masked.data_ptr(),
-                                                          self.metric_ws.data_ptr(), self._counter.data_ptr(), self._hs.data_ptr(), self._seq,
-                                                          hip_ops.raw_stream()), "ultr_dnn_forward_metrics")
-            return self.scores, self.ndcg
-        _lib.check(self._lib.ultr_dnn_forward_ndcg(ctypes.byref(self.shape.desc), params.data_ptr(), wt.data_ptr() if wt is not None else None,
-                                                   features.data_ptr() if n_docs > 0 else None, int(n_docs), docids.data_ptr(),
-                                                   labels.data_ptr(), self.B, self.L, self.scores.data_ptr(), self._topn_arr, len(self.topn),
-                                                   self.ndcg.data_ptr(), self.order.data_ptr(), self.masked.data_ptr(), self.ndcg_ws.data_ptr(),
-                                                   self._counter.data_ptr(), self._hs.data_ptr(), self._seq, hip_ops.raw_stream()),
-                   "ultr_dnn_forward_ndcg")
+        _lib.check(getattr(self._lib, name)(ctypes.byref(self.shape.desc), params.data_ptr(), wt.data_ptr() if wt is not None else None,
+                                            features.data_ptr() if n_docs > 0 else None, int(n_docs), docids.data_ptr(), labels.data_ptr(),
+                                            self.B, self.L, self.scores.data_ptr(), *self._launch_tail()), name)
         return self.scores, self.ndcg
 
     def forward(self, params, features, n_docs, docids):
@@ -448,16 +457,9 @@ class EvalEngine:
         return self._hs_f[:len(self.topn)].copy()
 
     def _wait_report(self, word, timeout_s):
-        seq, u, spins, t0 = self._seq, self._hs_u, 0, None
-        if seq == 0:
+        if self._seq == 0:
             raise RuntimeError("read_ndcg() before the first run()")
-        while int(u[word]) != seq:
-            spins += 1
-            if spins & 0x3FF == 0:
-                now = time.perf_counter()
-                t0 = now if t0 is None else t0
-                if now - t0 > timeout_s:
-                    raise _lib.UltrHipError("no NDCG report from the GPU within %.0f s" % timeout_s)
+        _wait_report(self._hs_u, word, self._seq, timeout_s, "NDCG")
 
     def read_metrics(self, timeout_s=60.0):
         """{metric: values per cutoff} of the LAST run(), from the launch's report in host-mapped memory (no stream synchronisation)."""
@@ -482,9 +484,7 @@ class EvalSetEngine:
             raise RuntimeError("ultra_pytorch_amd needs an MI355X/ROCm GPU: there is no CPU fallback")
         self.shape, self.B, self.L, self.device = shape, int(batch), int(list_size), device
         self.topn, self.metrics = [int(t) for t in topn], tuple(metrics)
-        unknown = [m for m in self.metrics if m not in METRIC_IDS]
-        if unknown or len(set(self.metrics)) != len(self.metrics) or not self.metrics:
-            raise ValueError("metrics must be distinct keys of %s, got %r" % (sorted(METRIC_IDS), self.metrics))
+        self._ids_arr = _metric_ids(self.metrics)
         if not metrics_fit(self.L):
             raise ValueError("list size %d is beyond the metric launch's bound (engine.metrics_fit)" % self.L)
         self._lib = shape.lib
@@ -503,7 +503,6 @@ class EvalSetEngine:
         self.n_queries = 0
         if self._cls is None:
             self._topn_arr = (ctypes.c_int32 * nt)(*self.topn)
-            self._ids_arr = (ctypes.c_int32 * nm)(*[METRIC_IDS[m] for m in self.metrics])
             self.scores = _f32(B * L, device).view(B, L)
             self.masked = _f32(B * L, device).view(B, L)
             self.order = torch.empty(B, L, dtype=torch.int32, device=device)
@@ -564,17 +563,9 @@ class EvalSetEngine:
 
     def read(self, timeout_s=60.0):
         """{metric: float64 [n_topn]} of the LAST run(), merged over the set - from the report in host-mapped memory."""
-        seq, u, spins, t0 = self._seq, self._hs_u, 0, None
-        if seq == 0:
+        if self._seq == 0:
             raise RuntimeError("read() before the first run()")
-        word = _lib.EVAL_SEQ_BYTE // 4
-        while int(u[word]) != seq:
-            spins += 1
-            if spins & 0x3FF == 0:
-                now = time.perf_counter()
-                t0 = now if t0 is None else t0
-                if now - t0 > timeout_s:
-                    raise _lib.UltrHipError("no evaluation report from the GPU within %.0f s" % timeout_s)
+        _wait_report(self._hs_u, _lib.EVAL_SEQ_BYTE // 4, self._seq, timeout_s, "evaluation")
         nt = len(self.topn)
         vals = self._hs_d[:self.n_values].copy()
         return {m: vals[k * nt:(k + 1) * nt] for k, m in enumerate(self.metrics)}
