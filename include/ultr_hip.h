@@ -257,7 +257,10 @@ int ultr_pdgd_loss(const float* scores, const float* labels, const int32_t* doci
  * list_size <= 128 on the matrix-core attention path (head depth 16 / 32 / 64), <= 120 otherwise - a forward at a longer list is an
  * evaluation (ULTR_E_UNSUPPORTED from the backward) - unless the descriptor carries ULTR_MODEL_SR_STREAM_BWD: then any list_size,
  * through the streaming attention backward (fp32 matrix cores at head depth 16 / 32 / 64, a scalar kernel at every other up to 228;
- * deterministic, no atomics). */
+ * deterministic, no atomics).
+ * `saved`, `workspace` (and `work` of ultr_setrank_score) are to be 16-byte aligned - what a torch allocation gives; the features
+ * pointer needs its natural 4-byte alignment only (a caller may pass a slice of a larger matrix: the fused embedding launch steps
+ * aside for the separate launches where it is not 16-byte aligned). */
 enum ultr_attention_dtype { ULTR_ATTN_FP32 = 0, ULTR_ATTN_FP16 = 1 };
 typedef struct ultr_setrank_desc {
   int32_t feature_size, d_model, num_heads, num_layers, dff;
@@ -293,6 +296,23 @@ enum ultr_setrank_attn_path_id {
   ULTR_SR_ATTN_LONG_SCALAR = 5   /* keys / partner tokens streamed in tiles, scalar */
 };
 int32_t ultr_setrank_attn_path(const ultr_setrank_desc* c, int32_t list_size, int32_t backward);
+/* Which launches a step takes (additive within ABI 8; host-only, launches nothing): the route ultr_setrank_forward and
+ * ultr_setrank_backward decide once per call at batch x list_size - dropout != 0: of a dropout step - under the knobs as last read
+ * (ultr_config_reload) and the descriptor's flags, for 16-byte aligned `saved` / `workspace` and a feature matrix the fused embedding
+ * launch takes (16-byte aligned, below 2 GiB: the forward tests that at the launch), with the CU count the forward itself reads (256
+ * where no device answers).  ULTR_E_BADARG: a bad desc, a NULL out, batch <= 0 or list_size <= 0. */
+typedef struct ultr_setrank_route_info {
+  int32_t embed;          /* 1: gather + input LayerNorm + embedding FFN as one launch */
+  int32_t block;          /* behind the attention of every encoder block: 0 separate launches, 1 the round-5 kernel, 2 the persistent kernel */
+  int32_t head_rides;     /* the output FFN runs inside the last block's launch */
+  int32_t skip_out1;      /* out1 is neither written by the forward nor read by the backward */
+  int32_t bwd_head, bwd_blocks, bwd_embed; /* the fused backward launches (ULTR_SR_BWD_FUSED bits 2, 1, 4) */
+  int32_t rows_per_tile, tiles, workgroups; /* the persistent launches, both directions (0: none run) */
+  int32_t block_rows, embed_rows; /* rows per workgroup of the round-5 block / embedding kernel (0: it does not apply) */
+  int32_t wgrad_split;    /* chunks of whole lists of the plain weight-gradient kernel */
+  int32_t reserved[3];    /* 0 */
+} ultr_setrank_route_info;
+int ultr_setrank_route(const ultr_setrank_desc* c, int32_t batch, int32_t list_size, int32_t dropout, ultr_setrank_route_info* out);
 /* The evaluation forward (additive within ABI 8): the scores of ultr_setrank_forward, bit for bit on every route and attention family,
  * and no record for a backward.  `work` (ultr_setrank_score_bytes; about F + dff + 4 d_model floats per row whatever num_layers, plus
  * the split-half planes) holds only what one launch hands to the next: x_l / x_{l+1} alternate between two buffers, the attention's

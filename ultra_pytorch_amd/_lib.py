@@ -98,6 +98,15 @@ class SetRankDesc(ctypes.Structure):
 SR_ATTN_PATHS = ("scalar", "mfma", "f16", "split_half", "long_mfma", "long_scalar")
 
 
+class SetRankRouteInfo(ctypes.Structure):  # ultr_setrank_route_info (ultr_setrank_route)
+    _fields_ = [("embed", c_i32), ("block", c_i32), ("head_rides", c_i32), ("skip_out1", c_i32), ("bwd_head", c_i32),
+                ("bwd_blocks", c_i32), ("bwd_embed", c_i32), ("rows_per_tile", c_i32), ("tiles", c_i32), ("workgroups", c_i32),
+                ("block_rows", c_i32), ("embed_rows", c_i32), ("wgrad_split", c_i32), ("reserved", c_i32 * 3)]
+
+
+SR_BLOCK_SEPARATE, SR_BLOCK_ROUND5, SR_BLOCK_PERSISTENT = 0, 1, 2  # ultr_setrank_route_info::block
+
+
 class SetRankDropout(ctypes.Structure):  # ultr_setrank_dropout
     _fields_ = [("rate", c_f32), ("seed", ctypes.c_uint64), ("step", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("scratch", c_vp),
                 ("scratch_bytes", c_i64)]
@@ -154,6 +163,7 @@ SIGNATURES = {
     "ultr_setrank_score_range_flag_offset": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
     "ultr_setrank_score": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "ultr_setrank_attn_path": (c_i32, [ctypes.POINTER(SetRankDesc), c_i32, c_i32]),
+    "ultr_setrank_route": (c_i32, [ctypes.POINTER(SetRankDesc), c_i32, c_i32, c_i32, ctypes.POINTER(SetRankRouteInfo)]),
     "ultr_setrank_dropout_workspace_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
     "ultr_setrank_forward_dropout": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp,
                                              ctypes.POINTER(SetRankDropout), c_vp]),

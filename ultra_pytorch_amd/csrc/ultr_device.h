@@ -33,6 +33,18 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_or<0x143>(0.f, v);
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+// the same sum in double, every lane gets it (a butterfly of lane exchanges: for the few sums that must not round in fp32)
+__device__ __forceinline__ double wave_sum_d(double v) {
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+// d score of the listwise softmax cross entropy, x D:  p S - w  with p = e / sum(e), S = sum(w) over the list.  In real arithmetic a
+// list's d scores sum to zero (the scorer's bias gradient IS that sum): S is summed in double and rounded once, p is a quotient and the
+// product is fused, so what a list keeps is a rounding of its d scores, not of its fp32 weight sum (6e-8 S per list before).  The
+// stand-alone launch (ultr_loss.hip) and the backward's fused prologues (ultr_dnn_bwd.hip) give the same bits.  (The fused step kernel of
+// ultr_dnn_fb.hip still forms exp(s - lse) S - w with S summed in fp32: same values to the 1e-5 bars, the residue above in its bias
+// gradients.)
+__device__ __forceinline__ float softmax_ce_dscore(float e, float sum_e, float S_once, float w) { return fmaf(e / sum_e, S_once, -w); }
 // N independent sums at once: the six dependent DPP steps of the N chains interleave (a single chain leaves the
 // VALU idle for most of each step's latency)
 template <int N>

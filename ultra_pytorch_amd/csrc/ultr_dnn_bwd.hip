@@ -58,6 +58,7 @@ __global__ __launch_bounds__(NW * 64) void dnn_bwd_kernel(DnnPlan p, BwdPlan bp,
     const int b_lo = (int)(n0 / L), b_hi = (int)(nlast / L);
     for (int b = b_lo + wave; b <= b_hi; b += NW) {
       float mx = -INFINITY, S = 0.f;
+      double Sd = 0.0;
       for (int l = lane; l < L; l += 64) {
         const float sc = fl.scores[(int64_t)b * L + l];
         const float y = fl.labels[(int64_t)l * B + b];
@@ -66,12 +67,15 @@ __global__ __launch_bounds__(NW * 64) void dnn_bwd_kernel(DnnPlan p, BwdPlan bp,
         else if (fl.ipw != nullptr) pwt = (y > 0.f) ? fl.ipw[l < fl.n_ipw ? l : fl.n_ipw - 1] : 0.f;
         mx = fmaxf(mx, sc);
         S += (y + 0.0000001f) * pwt;
+        Sd += (double)((y + 0.0000001f) * pwt);
       }
       mx = wave_max(mx);
       S = wave_sum(S);
+      const float Sa = (float)wave_sum_d(Sd);  // the weight sum rounded ONCE (ultr_device.h: softmax_ce_dscore)
       float se = 0.f;
       for (int l = lane; l < L; l += 64) se += expf(fl.scores[(int64_t)b * L + l] - mx);
-      const float lse = mx + logf(wave_sum(se));
+      se = wave_sum(se);
+      const float lse = mx + logf(se);
       float lb = 0.f;
       for (int l = lane; l < L; l += 64) {
         const float sc = fl.scores[(int64_t)b * L + l];
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(NW * 64) void dnn_bwd_kernel(DnnPlan p, BwdPlan bp,
         if (fl.pw != nullptr) pwt = fl.pw[(int64_t)b * L + l];
         else if (fl.ipw != nullptr) pwt = (y > 0.f) ? fl.ipw[l < fl.n_ipw ? l : fl.n_ipw - 1] : 0.f;
         const float w = (y + 0.0000001f) * pwt;
-        const float ds = expf(sc - lse) * S - w;
+        const float ds = softmax_ce_dscore(expf(sc - mx), se, Sa, w);
         lb += w * (lse - sc);
         const int64_t n = (int64_t)b * L + l;
         if (n >= n0 && n <= nlast) {
@@ -429,8 +433,11 @@ __global__ __launch_bounds__(NW * 64) void dnn_bwd2_kernel(DnnPlan p, BwdPlan bp
         const float w = act ? (y + 0.0000001f) * pwt : 0.f;
         const float mx = wave_max(act ? sc : -INFINITY);
         const float S = wave_sum(w);
-        const float lse = mx + logf(wave_sum(act ? expf(sc - mx) : 0.f));
-        const float dsv = expf(sc - lse) * S - w;
+        const float Sa = (float)wave_sum_d((double)w);  // the weight sum rounded ONCE (ultr_device.h: softmax_ce_dscore)
+        const float e = act ? expf(sc - mx) : 0.f;
+        const float se = wave_sum(e);
+        const float lse = mx + logf(se);
+        const float dsv = softmax_ce_dscore(e, se, Sa, w);
         const float lb = wave_sum(act ? w * (lse - sc) : 0.f);
         const int64_t n = (int64_t)b * L + lane;
         if (act && n >= n0 && n <= nlast) {
@@ -445,6 +452,7 @@ __global__ __launch_bounds__(NW * 64) void dnn_bwd2_kernel(DnnPlan p, BwdPlan bp
     } else {
       for (int b = b_lo + wave; b <= b_hi; b += NW) {
         float mx = -INFINITY, S = 0.f;
+        double Sd = 0.0;
         for (int l = lane; l < L; l += 64) {
           const float sc = fl.scores[(int64_t)b * L + l];
           const float y = fl.labels[(int64_t)l * B + b];
@@ -453,12 +461,15 @@ __global__ __launch_bounds__(NW * 64) void dnn_bwd2_kernel(DnnPlan p, BwdPlan bp
           else if (fl.ipw != nullptr) pwt = (y > 0.f) ? fl.ipw[l < fl.n_ipw ? l : fl.n_ipw - 1] : 0.f;
           mx = fmaxf(mx, sc);
           S += (y + 0.0000001f) * pwt;
+          Sd += (double)((y + 0.0000001f) * pwt);
         }
         mx = wave_max(mx);
         S = wave_sum(S);
+        const float Sa = (float)wave_sum_d(Sd);  // the weight sum rounded ONCE (ultr_device.h: softmax_ce_dscore)
         float se = 0.f;
         for (int l = lane; l < L; l += 64) se += expf(fl.scores[(int64_t)b * L + l] - mx);
-        const float lse = mx + logf(wave_sum(se));
+        se = wave_sum(se);
+        const float lse = mx + logf(se);
         float lb = 0.f;
         for (int l = lane; l < L; l += 64) {
           const float sc = fl.scores[(int64_t)b * L + l];
@@ -467,7 +478,7 @@ __global__ __launch_bounds__(NW * 64) void dnn_bwd2_kernel(DnnPlan p, BwdPlan bp
           if (fl.pw != nullptr) pwt = fl.pw[(int64_t)b * L + l];
           else if (fl.ipw != nullptr) pwt = (y > 0.f) ? fl.ipw[l < fl.n_ipw ? l : fl.n_ipw - 1] : 0.f;
           const float w = (y + 0.0000001f) * pwt;
-          const float dsv = expf(sc - lse) * S - w;
+          const float dsv = softmax_ce_dscore(expf(sc - mx), se, Sa, w);
           lb += w * (lse - sc);
           const int64_t n = (int64_t)b * L + l;
           if (n >= n0 && n <= nlast) {

@@ -63,6 +63,7 @@ __global__ __launch_bounds__(LPW * 64) void softmax_ce_kernel(const float* __res
   for (int t = lane; t < tail; t += 64) mt[t] = 0.f;
   if (b < B) {
     float mx = -INFINITY, S = 0.f;
+    double Sd = 0.0;
     for (int l = lane; l < L; l += 64) {
       const float s = scores[(int64_t)b * L + l];
       const float y = labels[(int64_t)l * B + b];
@@ -74,17 +75,20 @@ __global__ __launch_bounds__(LPW * 64) void softmax_ce_kernel(const float* __res
       mw[l] = w;
       mx = fmaxf(mx, s);
       S += w;
+      Sd += (double)w;
     }
     mx = wave_max(mx);
     S = wave_sum(S);
+    const float Sa = (float)wave_sum_d(Sd);  // the weight sum rounded ONCE (ultr_device.h: softmax_ce_dscore)
     float se = 0.f;
     for (int l = lane; l < L; l += 64) se += expf(ms[l] - mx);
-    const float lse = mx + logf(wave_sum(se));
+    se = wave_sum(se);
+    const float lse = mx + logf(se);
     float lb = 0.f;
     for (int l = lane; l < L; l += 64) {
       const float s = ms[l], w = mw[l];
       lb += w * (lse - s);                                   // -w * log_softmax(s)
-      dscores[(int64_t)b * L + l] = expf(s - lse) * S - w;   // x D
+      dscores[(int64_t)b * L + l] = softmax_ce_dscore(expf(s - mx), se, Sa, w);   // x D
     }
     lb = wave_sum(lb);
     if (lane == 0) {

@@ -449,6 +449,23 @@ extern "C" int32_t ultr_setrank_attn_path(const ultr_setrank_desc* c, int32_t li
   return sr_attn_path(ash, list_size, backward != 0, k.attn_h3 >= 1 && ((k.attn_mask >> 1) & 1) != 0);
 }
 
+// The route a plain step (dropout = 0) or a dropout step takes at batch x list_size: the plan and the route of the forward and the backward
+// themselves (sr_make_plan, sr_route - no condition is restated here), under the knobs as last read, the descriptor's flags, the CU
+// count the forward reads, and 16-byte aligned `saved`.  Launches nothing.
+extern "C" int ultr_setrank_route(const ultr_setrank_desc* c, int32_t batch, int32_t list_size, int32_t dropout, ultr_setrank_route_info* out) {
+  SrPlan p;
+  if (out == nullptr || batch <= 0 || list_size <= 0 || !sr_make_plan(c, (int64_t)batch * list_size, &p)) return ULTR_E_BADARG;
+  const SrKnobs& k = sr_knobs();
+  const SrRoute rt = sr_route(p, k, sr_cu_count(), k.h3 && !p.no_h3, dropout != 0, true);
+  memset(out, 0, sizeof(*out));
+  out->embed = rt.embed; out->block = rt.block; out->head_rides = rt.head_rides; out->skip_out1 = rt.skip_out1;
+  out->bwd_head = rt.bwd_head; out->bwd_blocks = rt.bwd_blocks; out->bwd_embed = rt.bwd_embed;
+  out->rows_per_tile = rt.R; out->tiles = rt.tiles; out->workgroups = rt.nwg;
+  out->block_rows = rt.block_R; out->embed_rows = rt.embed_R;
+  out->wgrad_split = p.wg_split;
+  return 0;
+}
+
 extern "C" int64_t ultr_setrank_param_count(const ultr_setrank_desc* c) {
   SrPlan p;
   return sr_make_plan(c, 0, &p) ? p.P : 0;

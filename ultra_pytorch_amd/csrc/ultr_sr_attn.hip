@@ -854,7 +854,9 @@ __global__ __launch_bounds__(SR_MAXT * 64) void sr_attn_bwd_h3_kernel(const floa
   } while (0)
 
 // matrix-core attention: list_size <= 128 (one wave per 16-token block), head depth 16 / 32 / 64, 16-byte aligned head
-// slices; ULTR_SR_SCALAR_ATTN=1 forces the scalar kernels
+// slices; ULTR_SR_SCALAR_ATTN=1 forces the scalar kernels.  The gate tests d % 4 (with the head depths above: every head slice starts a
+// multiple of 16 bytes into its row, every row a multiple of 16 bytes into x); that IS the promise where x itself is 16-byte
+// aligned - x lives in `saved`, which callers are to pass 16-byte aligned (include/ultr_hip.h), as every caller in the tree does.
 bool attn_mfma_shape_ok(const SrAttnShape& p) {  // (the streaming kernels of ultr_sr_attn_long.hip take the same shapes at any list size)
   const char* v = getenv("ULTR_SR_SCALAR_ATTN");
   if (v != nullptr && v[0] == '1') return false;

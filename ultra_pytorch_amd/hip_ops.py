@@ -164,6 +164,14 @@ class SetRankShape:
         """Bytes of setrank_score's buffer: the live activations (their size does not grow with num_layers), the planes, the range word."""
         return int(self.lib.ultr_setrank_score_bytes(ctypes.byref(self.desc), n_rows))
 
+    def route(self, B, L, dropout=False):
+        """The launches one step takes at B lists of L documents (ultr_setrank_route: the library's own plan and route under the knobs
+        as it last read them; host-only, launches nothing) as a dict of the fields of ultr_setrank_route_info."""
+        info = _lib.SetRankRouteInfo()
+        check(self.lib.ultr_setrank_route(ctypes.byref(self.desc), int(B), int(L), 1 if dropout else 0, ctypes.byref(info)),
+              "ultr_setrank_route")
+        return {name: int(getattr(info, name)) for name, _ in _lib.SetRankRouteInfo._fields_ if name != "reserved"}
+
     def score_range_flag_offset(self, n_rows):
         """Float offset in setrank_score's buffer of the range word of the split-half planes."""
         return int(self.lib.ultr_setrank_score_range_flag_offset(ctypes.byref(self.desc), n_rows))
