@@ -125,16 +125,53 @@ int ultr_dnn_build_wt(const ultr_dnn_desc* d, const float* params, float* wt, vo
  * in fp32), so the caller switches to the fp32 products (ULTR_FB_H3=0 ULTR_FWD_H3=0 ULTR_BWD_H3=0 + ultr_config_reload) when
  * this is not 0.  During training the same information arrives with the step report (host_scalars[8]). */
 int ultr_dnn_wt_range(const ultr_dnn_desc* d, const float* wt, void* stream);
-/* Which forward kernel ultr_dnn_forward launches for n_rows = batch x list_size rows when it is given aligned operands and the
- * weight copies (host-only, for tests and the bench line): 16 / 32 = dnn_fwd_kernel with that many rows per workgroup,
- * 1000 + R = the wide-tile kernel dnn_fwdw_kernel with R = 17 .. 48 rows per workgroup (round 5), 0 = the per-layer path
- * (training forward only), < 0 = bad descriptor. */
+/* Which kernels a call takes (additive within ABI 8; host-only, launches nothing): the route ultr_dnn_forward, ultr_dnn_backward,
+ * ultr_dnn_backward_softmax and the fused step decide once per call - the queries below read the same function - at batch x list_size
+ * rows gathered from n_docs documents, under the knobs as last read (ultr_config_reload), for what ultr_train_step and the evaluation
+ * always pass: 16-byte aligned pointers and the weight copies present; with the CU count the planners read (256 where no device
+ * answers).  ULTR_E_UNSUPPORTED where the call itself would refuse (`out` is filled, the family that refuses is ULTR_DNN_UNSUPPORTED);
+ * ULTR_E_BADARG: a bad desc, a NULL out, batch <= 0, list_size <= 0, n_docs < 0 or an unknown `call`. */
+enum ultr_dnn_route_call {
+  ULTR_DNN_CALL_EVAL = 0,          /* ultr_dnn_forward with saved == NULL */
+  ULTR_DNN_CALL_STEP_SOFTMAX = 1,  /* ultr_train_step, algo ULTR_ALGO_SOFTMAX */
+  ULTR_DNN_CALL_STEP_DSCORES = 2   /* ultr_train_step of an algorithm whose dscores come from its loss kernel */
+};
+enum ultr_dnn_family {
+  ULTR_DNN_NONE = 0,         /* not part of this call */
+  ULTR_DNN_TILE = 1,         /* dnn_fwd_kernel / dnn_bwd_kernel: 16- or 32-row tiles */
+  ULTR_DNN_TILE2 = 2,        /* dnn_bwd2_kernel (backward only) */
+  ULTR_DNN_WIDE = 3,         /* dnn_fwdw_kernel / dnn_bwdw_kernel: 17 .. 64 rows per workgroup */
+  ULTR_DNN_PER_LAYER = 4,    /* the per-layer launches (training forward, backward) */
+  ULTR_DNN_FUSED = 5,        /* ran inside dnn_fb_kernel */
+  ULTR_DNN_UNSUPPORTED = 6   /* the call returns ULTR_E_UNSUPPORTED */
+};
+enum ultr_dnn_loss_place {
+  ULTR_DNN_LOSS_NONE = 0,      /* evaluation */
+  ULTR_DNN_LOSS_LAUNCH = 1,    /* a launch of its own (ultr_softmax_ce, or the algorithm's loss kernel) */
+  ULTR_DNN_LOSS_PROLOGUE = 2,  /* the prologue of dnn_bwd_kernel / dnn_bwd2_kernel */
+  ULTR_DNN_LOSS_FUSED = 3      /* inside dnn_fb_kernel */
+};
+typedef struct ultr_dnn_route_info {
+  int32_t fused_waves;        /* 0: the separate kernels; 8 / 16: dnn_fb_kernel on that many waves per workgroup */
+  int32_t fwd, fwd_rows;      /* ultr_dnn_family of the forward and its rows per workgroup (0: per-layer; dnn_fb_kernel: the live
+                               * rows of its 16-row tile, whole lists) */
+  int32_t bwd, bwd_rows;      /* ... of the row-local backward */
+  int32_t loss;               /* ultr_dnn_loss_place */
+  int32_t wg_split_half;      /* 1: the weight gradients take dnn_wgrad_h3_kernel */
+  int32_t reserved[5];        /* 0 */
+} ultr_dnn_route_info;
+int ultr_dnn_route(const ultr_dnn_desc* d, int32_t batch, int32_t list_size, int64_t n_docs, int32_t call, ultr_dnn_route_info* out);
+/* The older queries, views of the same route (for tests, tools and the bench line).  Which forward kernel ultr_dnn_forward launches
+ * for n_rows = batch x list_size rows: 16 / 32 = dnn_fwd_kernel with that many rows per workgroup, 1000 + R = the wide-tile kernel
+ * dnn_fwdw_kernel with R = 17 .. 64 rows per workgroup, 0 = the per-layer path (training forward only), < 0 = bad descriptor.
+ * They name the kernel that is launched: where nothing can take the float4 paths - a feature or hidden width that is no multiple
+ * of 4, ULTR_NO_VEC=1 - that is a 16- / 32-row tile kernel (before the route existed they answered "wide" or "per-layer" there). */
 int32_t ultr_dnn_forward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows, int32_t training);
-/* ... and the row-local backward kernel of ultr_train_step (aligned operands, dscores from a loss kernel): 16 / 32 = dnn_bwd2_kernel /
- * dnn_bwd_kernel, 1000 + R = the wide-tile kernel dnn_bwdw_kernel, 0 = the per-layer path. */
+/* ... and the row-local backward kernel of ultr_train_step (dscores from a loss kernel): 16 / 32 = dnn_bwd2_kernel / dnn_bwd_kernel
+ * (ultr_dnn_route tells them apart), 1000 + R = the wide-tile kernel dnn_bwdw_kernel, 0 = the per-layer path. */
 int32_t ultr_dnn_backward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows);
 /* ... and whether a softmax / IPW training step of `batch` lists of `list_size` takes the fused forward + loss + backward kernel
- * dnn_fb_kernel (aligned operands): 0 = no (the separate kernels), 8 / 16 = yes, with that many waves per workgroup (ULTR_FB_NW). */
+ * dnn_fb_kernel: 0 = no (the separate kernels), 8 / 16 = yes, with that many waves per workgroup (ULTR_FB_NW). */
 int32_t ultr_fused_fb_waves(const ultr_dnn_desc* d, int32_t batch, int32_t list_size);
 
 /* ---- a5 (backward half): what loss.backward() does for the DNN ----------------------

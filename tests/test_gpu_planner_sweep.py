@@ -6,8 +6,9 @@ RandomState(0) around every boundary - rows per workgroup 16 / 17, 48 / 49, 64 /
 255 / 256 / 257 and 511 / 512 / 513, feature sizes that are not multiples of 4, zero to four hidden layers, list sizes 1, 9, 10, 17,
 100, 101, PAD documents (rank_list_size < max_candidate_num), training and evaluation - each runs ONE product step
 (engine.StepEngine.train_step = ultr_train_step) against oracle.ultr_oracle at the golden tolerances (loss 1e-5, scores 1e-5,
-gradients 1e-5 (|g| + sum |terms|) per entry), or one evaluation forward (scores 1e-5).  The sweep asserts that it reached every kernel
-family (the planners ultr_dnn_forward_tile_rows / ultr_dnn_backward_tile_rows say what a shape takes).
+gradients 1e-5 (|g| + sum |terms|) per entry), or one evaluation forward (scores 1e-5).  Three tiny shapes behind the drawn ones reach
+the fused launch on 8 and on 16 waves and its neighbour one document past the 16-row tile.  The sweep asserts that it reached every
+kernel family (ultr_dnn_route, the route the entry points themselves decide, says what a case launches).
 Reference: DNN.py:18-56 (any widths, any depth), base_algorithm.py:118-154, ipw_rank.py:102-182."""
 import numpy as np
 import pytest
@@ -47,6 +48,9 @@ def draw_cases():
         algo = "dla" if k % 5 == 4 else "softmax"
         train = k % 7 != 6
         cases.append(dict(k=k, F=F, hidden=hidden, B=B, L=L, act=ACTS[rng.randint(4)], n_pad=n_pad, algo=algo, train=train))
+    # behind the draw: dnn_fb_kernel on 16 waves (one 256-wide layer, a full 16-row tile), one document more (not fused), and on 8 waves
+    for F, hidden, B, L, n_pad in ((24, [256], 5, 16, 0), (24, [256], 5, 17, 0), (24, [64, 32], 6, 9, 2)):
+        cases.append(dict(k=len(cases), F=F, hidden=hidden, B=B, L=L, act="elu", n_pad=n_pad, algo="softmax", train=True))
     return cases
 
 
@@ -55,16 +59,18 @@ SEEN = {}
 
 
 def families(c):
+    """What the case launches, by ultr_dnn_route: fwd_ / eval_fwd_ + tile16 | wide | per_layer; bwd_ (dnn_bwd_kernel) / bwd2_
+    (dnn_bwd2_kernel) + tile16 | tile32, bwd_wide, bwd_per_layer; fused8 / fused16 (dnn_fb_kernel on that many waves)."""
     from ultra_pytorch_amd import _lib, hip_ops
-    lib = _lib.load()
-    shape = hip_ops.DnnShape(c["F"], c["hidden"], c["act"])
-    n = c["B"] * c["L"]
-    fwd = lib.ultr_dnn_forward_tile_rows(shape.desc, n, 1 if c["train"] else 0)
-    name = lambda code: "wide" if code >= 1000 else ("per_layer" if code == 0 else "tile%d" % code)
+    call = "eval" if not c["train"] else ("step_softmax" if c["algo"] == "softmax" else "step_dscores")
+    r = hip_ops.DnnShape(c["F"], c["hidden"], c["act"]).route(c["B"], c["L"], call=call)
+    if r["fused_waves"]:
+        return ["fused%d" % r["fused_waves"]]
+    name = lambda fam, rows: "tile%d" % rows if fam in ("tile", "tile2") else fam
+    fwd, bwd = _lib.DNN_FAMILIES[r["fwd"]], _lib.DNN_FAMILIES[r["bwd"]]
     if not c["train"]:
-        return ["eval_fwd_" + name(fwd)]
-    bwd = lib.ultr_dnn_backward_tile_rows(shape.desc, n)
-    return ["fwd_" + name(fwd), "bwd_" + name(bwd)]
+        return ["eval_fwd_" + name(fwd, r["fwd_rows"])]
+    return ["fwd_" + name(fwd, r["fwd_rows"]), ("bwd2_" if bwd == "tile2" else "bwd_") + name(bwd, r["bwd_rows"])]
 
 
 @pytest.mark.parametrize("c", CASES, ids=lambda c: "%02d_F%d_%s_B%dxL%d_%s_%s" % (c["k"], c["F"], "x".join(map(str, c["hidden"])) or "linear", c["B"], c["L"],
@@ -138,7 +144,9 @@ def test_one_step_against_the_oracle(c):
 
 def test_the_sweep_reached_every_kernel_family():
     """(runs after the cases above: pytest keeps file order)"""
-    need = ["fwd_tile16", "fwd_wide", "bwd_wide", "eval_fwd_tile16", "eval_fwd_wide"]
+    need = ["fwd_tile16", "fwd_wide", "bwd_wide", "eval_fwd_tile16", "eval_fwd_wide",
+            # what the route, unlike the older queries, tells apart or reaches at all
+            "bwd_tile16", "bwd_tile32", "bwd2_tile16", "bwd2_tile32", "fwd_per_layer", "bwd_per_layer", "fused8", "fused16"]
     missing = [f for f in need if SEEN.get(f, 0) == 0]
     assert not missing, (missing, SEEN)
     assert any(k.startswith("bwd_tile") for k in SEEN), SEEN

@@ -24,6 +24,15 @@ class DnnDesc(ctypes.Structure):
                 ("flags", c_i32)]
 
 
+class DnnRouteInfo(ctypes.Structure):  # ultr_dnn_route_info (ultr_dnn_route)
+    _fields_ = [("fused_waves", c_i32), ("fwd", c_i32), ("fwd_rows", c_i32), ("bwd", c_i32), ("bwd_rows", c_i32), ("loss", c_i32),
+                ("wg_split_half", c_i32), ("reserved", c_i32 * 5)]
+
+
+DNN_CALLS = ("eval", "step_softmax", "step_dscores")  # include/ultr_hip.h: ultr_dnn_route_call
+DNN_FAMILIES = ("none", "tile", "tile2", "wide", "per_layer", "fused", "unsupported")  # ultr_dnn_family
+DNN_LOSS_PLACES = ("none", "launch", "prologue", "fused")  # ultr_dnn_loss_place
+
 MODEL_FP32_PRODUCTS = 1  # ultr_dnn_desc / ultr_setrank_desc ::flags (include/ultr_hip.h, ABI 6)
 MODEL_SR_STREAM_BWD = 2  # ultr_setrank_desc::flags: the streaming attention backward beyond the one-pass kernels' list bounds
 ABI_VERSION = 8          # include/ultr_hip.h: ULTR_ABI_VERSION - load() refuses a library that reports another one
@@ -139,6 +148,7 @@ SIGNATURES = {
     "ultr_dnn_forward_tile_rows": (c_i32, [ctypes.POINTER(DnnDesc), c_i64, c_i32]),
     "ultr_dnn_backward_tile_rows": (c_i32, [ctypes.POINTER(DnnDesc), c_i64]),
     "ultr_fused_fb_waves": (c_i32, [ctypes.POINTER(DnnDesc), c_i32, c_i32]),
+    "ultr_dnn_route": (c_i32, [ctypes.POINTER(DnnDesc), c_i32, c_i32, c_i64, c_i32, ctypes.POINTER(DnnRouteInfo)]),
     "ultr_dnn_backward": (c_i32, [ctypes.POINTER(DnnDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp]),
     "ultr_dnn_backward_softmax": (c_i32, [ctypes.POINTER(DnnDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,

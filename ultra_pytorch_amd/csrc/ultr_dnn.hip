@@ -6,9 +6,9 @@
 //   ultr_dnn_wgrad.hip  dnn_wgrad_kernel, dnn_wgrad_h3_kernel, grad_reduce_kernel, grad_reduce_xchg_kernel, grad_sumsq_kernel
 //   ultr_dnn_kernels.h  LDS strides, the matrix-core GEMM building blocks, plan structs, the launchers' declarations
 //   ultr_dnn_big.hip    the per-layer launches for shapes whose row tile does not fit LDS
-// Here: ultr_make_dnn_plan / ultr_make_bwd_plan (what every kernel is handed), the planners that pick a kernel family by shape
-// (fwd_wide_plan, bwd_wide_plan, big_*_wanted), the weight-copy builder, ultr_dnn_forward / _backward / _backward_softmax and the fused
-// step's host side.
+// Here: ultr_make_dnn_plan / ultr_make_bwd_plan (what every kernel is handed), dnn_route - the one place that picks a call's kernels,
+// over the planners of each family (fwd_wide_plan, bwd_wide_plan, big_*_wanted, fused_fb_waves) - the weight-copy builder,
+// ultr_dnn_forward / _backward / _backward_softmax and the fused step's host side, which read the route and launch.
 //
 // Matrix math: v_mfma_f32_16x16x4_f32 (exact fp32) - and, for layers with >= 256 outputs / inputs where the plan carries split-half
 // weight copies (DnnPlan::h3f / h3b; knobs ULTR_FB_H3 / ULTR_FWD_H3 / ULTR_BWD_H3, default on), three v_mfma_f32_16x16x32_f16 on
@@ -256,18 +256,12 @@ bool ultr_make_dnn_plan(const ultr_dnn_desc* d, int64_t N, DnnPlan* p) {
   return true;
 }
 
-static size_t fwd_pv_floats(const DnnPlan& p) { return (size_t)p.pv_total; }
 static size_t fwd_lds_bytes(const DnnPlan& p, int R) {
-  return ((size_t)2 * R * fwd_ld_of(p.maxdim, p.fwd_h3) + fwd_pv_floats(p)) * sizeof(float);
+  return ((size_t)2 * R * fwd_ld_of(p.maxdim, p.fwd_h3) + (size_t)p.pv_total) * sizeof(float);
 }
-static int fwd_rows_per_wg(const DnnPlan& p, int64_t N) {
-  int r = knobs().fwd_r;
-  if (r == 16 || r == 32) return r;
-  // 16-row tiles everywhere: 32-row tiles halve the W stream per row, but their LDS footprint leaves one workgroup per CU and
-  // the grid quantises badly (measured at cfg3 / B=1024: 114 -> 100 us and 57 -> 43 us with 16 rows); ULTR_FWD_R=32 forces them
-  (void)N;
-  return 16;
-}
+// 16-row tiles everywhere: 32-row tiles halve the W stream per row, but their LDS footprint leaves one workgroup per CU and
+// the grid quantises badly (measured at cfg3 / B=1024: 114 -> 100 us and 57 -> 43 us with 16 rows); ULTR_FWD_R=32 forces them
+static int fwd_rows_per_wg() { return knobs().fwd_r == 32 ? 32 : 16; }
 static size_t bwd_lds_bytes(const DnnPlan& p, int R) {
   return ((size_t)R * (2 * bwd_ldu(p.maxdim) + bwd_ldz(p.maxdim)) + 2 * (size_t)bwd_ldu(p.maxdim) + 5 * (size_t)R) * sizeof(float) + (size_t)R * sizeof(int64_t);
 }
@@ -277,11 +271,20 @@ static int bwd_rows_per_wg(const DnnPlan& p, int64_t N) {
   return ((N + 15) / 16 > 512 && bwd_lds_bytes(p, 32) <= 160 * 1024) ? 32 : 16;
 }
 
-bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, int wg_mode) {
+// the geometry of a call whose route picks nothing else: the row-tile kernels, the layer-0 shortcut whenever there is a hidden layer (every
+// backward kernel skips du_0), the split-half weight gradients by the knob and the batch size where the shapes and the operands (av) allow
+static BwdGeom bwd_geom(const DnnPlan& p, int64_t N, bool av) {
+  const int rblk = bwd_rows_per_wg(p, N);
+  bool h3w = av && knobs().wg_h3 != 0 && p.nl >= 2 && (knobs().wg_h3 >= 2 || N >= knobs().wg_h3_min_rows);
+  for (int j = 0; j < p.nl - 1; ++j)
+    if (p.M[j] % 4 != 0 || p.K[j] % 4 != 0 || p.off_w[j] % 4 != 0) h3w = false;
+  return BwdGeom{rblk, (int)((N + rblk - 1) / rblk), p.nl >= 2 ? 1 : 0, 0, h3w ? 1 : 0};
+}
+
+bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, const BwdGeom& g) {
   memset(bp, 0, sizeof(*bp));
   bp->N = N;
-  bp->rblk = bwd_rows_per_wg(p, N);
-  bp->nrb = (int)((N + bp->rblk - 1) / bp->rblk);
+  bp->rblk = g.rblk; bp->nrb = g.nrb; bp->l0g = g.l0g; bp->wg_prenorm = g.wg_prenorm;
   int v = 0;
   for (int j = 0; j < p.nl; ++j) {
     bp->voff_g[j] = v; v += p.K[j];
@@ -298,7 +301,7 @@ bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, int wg_mode) {
   off += ultr_sumsq2_len(p.P);  // level-2 partials at ultr_sumsq2_off(P) (= here: sumsq_off is 0)
   off = (off + 3) & ~(int64_t)3;
   // sized for the finest row blocking any kernel uses (the fused forward+backward kernel owns >= 9 live rows per block)
-  const int64_t nrb_alloc = (N + 8) / 9 + 1 > bp->nrb ? (N + 8) / 9 + 1 : bp->nrb;
+  const int64_t nrb_alloc = (N + 8) / 9 + 1;
   bp->vslab_off = off; off += nrb_alloc * bp->vlen; off = (off + 3) & ~(int64_t)3;
   bp->vred_off = off; off += bp->vlen; off = (off + 3) & ~(int64_t)3;
   bp->vred_blocks = (bp->vlen + 63) / 64;
@@ -312,11 +315,10 @@ bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, int wg_mode) {
   }
   // wgrad geometry
   int tiles = 0, tiles2 = 0;
-  bool h3w = wg_mode != 0 && knobs().wg_h3 != 0 && p.nl >= 2 && (knobs().wg_h3 >= 2 || N >= knobs().wg_h3_min_rows);
+  const bool h3w = g.wg_h3 != 0;
   for (int j = 0; j < p.nl - 1; ++j) {
     tiles += ((p.M[j] + 63) / 64) * ((p.K[j] + 63) / 64);
     tiles2 += ((p.M[j] + 127) / 128) * ((p.K[j] + 127) / 128);
-    if (p.M[j] % 4 != 0 || p.K[j] % 4 != 0 || p.off_w[j] % 4 != 0) h3w = false;
   }
   bp->wg_h3 = h3w ? 1 : 0;
   // workgroups over all hidden Linears: about one per CU for a small batch (every workgroup is a chain of latencies and a
@@ -357,7 +359,6 @@ bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, int wg_mode) {
     w.slab_off = off; off += (int64_t)w.nsplit * ((int64_t)w.M * w.K + w.M); off = (off + 3) & ~(int64_t)3;
   }
   bp->wgrad_blocks = blk;
-  bp->wg_tiles2 = bp->wg_live = bp->wg_chunk = 0;
   if (h3w) {
     bp->wg_tiles2 = tiles2;
     bp->wg_live = tiles2 * bp->wl[0].nsplit;  // (every layer got the same split count: one formula, one N)
@@ -365,7 +366,6 @@ bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, int wg_mode) {
     bp->wgrad_blocks = 8 * bp->wg_chunk;
   }
   bp->lfold_off = off; off += 64 * tail_max;  // second level of the loss-partial fold (more than 1024 partials)
-  bp->l0g = 0;
   bp->l0part_off = off;
   if (p.nl >= 2) off += ((int64_t)bp->wl[0].nmb * bp->wl[0].nsplit * 2 * p.K[0] + 3) & ~(int64_t)3;
   {
@@ -376,7 +376,6 @@ bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, int wg_mode) {
   bp->total = off;
   return true;
 }
-
 
 void ultr_make_red_plan(const DnnPlan& p, const BwdPlan& bp, RedPlan* rp) {
   int s = 0;
@@ -415,13 +414,17 @@ static bool all_vec(const DnnPlan& p, int vm, int64_t N, int64_t n_docs) {
   return (vm >> 31) & 1;
 }
 
-static int vecmask_for(const DnnPlan& p, const float* params, const float* features) {
+static int vecmask_for(const DnnPlan& p, const DnnOperands& o) {
   int mask = 0;
-  const bool pa = ((uintptr_t)params & 15) == 0;
   for (int j = 0; j < p.nl; ++j)
-    if (pa && p.K[j] % 4 == 0 && p.off_w[j] % 4 == 0) mask |= (1 << j);
-  if (features != nullptr && ((uintptr_t)features & 15) == 0 && p.K[0] % 4 == 0) mask |= (1u << 31);
+    if (o.params16 && p.K[j] % 4 == 0 && p.off_w[j] % 4 == 0) mask |= (1 << j);
+  if (o.features16 && p.K[0] % 4 == 0) mask |= (1u << 31);
   return mask;
+}
+static bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+// what a call knows of its operands (dscores: the buffer a separate loss launch writes, or the caller's own)
+static DnnOperands operands_of(const float* params, const float* features, const float* wt, const float* dscores) {
+  return DnnOperands{aligned16(params), features != nullptr && aligned16(features), wt != nullptr, aligned16(wt), dscores != nullptr};
 }
 
 extern "C" int64_t ultr_dnn_param_count(const ultr_dnn_desc* d) {
@@ -449,13 +452,11 @@ extern "C" int64_t ultr_dnn_bwd_workspace_bytes(const ultr_dnn_desc* d, int64_t 
   BwdPlan bp;
   if (n_rows < 0 || !ultr_make_dnn_plan(d, n_rows, &p)) return 0;
   // worst case over the env-tunable geometry: size for both row-block choices
-  ultr_make_bwd_plan(p, n_rows, &bp);
-  int64_t t = bp.total;
-  if (bp.wg_h3) {  // the launcher may fall back to the register kernel's geometry (unaligned pointers)
-    BwdPlan b0;
-    ultr_make_bwd_plan(p, n_rows, &b0, 0);
-    t = b0.total > t ? b0.total : t;
-  }
+  BwdPlan b0;
+  const BwdGeom g = bwd_geom(p, n_rows, true), g0 = bwd_geom(p, n_rows, false);  // (unaligned pointers: the register wgrad kernel's geometry)
+  ultr_make_bwd_plan(p, n_rows, &bp, g);
+  ultr_make_bwd_plan(p, n_rows, &b0, g0);
+  const int64_t t = b0.total > bp.total ? b0.total : bp.total;
   const int64_t extra = ((n_rows + 15) / 16) * (int64_t)bp.vlen;  // if rblk were 16
   return (t + extra + 1024) * (int64_t)sizeof(float);
 }
@@ -569,11 +570,9 @@ static bool big_fwd_wanted(const DnnPlan& p, int64_t N, size_t row_tile_lds) {
   const int64_t chunks0 = ((N + 63) / 64) * ((p.M[0] + 127) / 128), gslots = 3 * (int64_t)cus;
   return full >= 3 && rem != 0 && rem * 4 <= slots && chunks0 <= gslots + gslots / 8;
 }
-static bool big_bwd_wanted(const DnnPlan& p, int64_t N) {
+static bool big_bwd_wanted(int64_t N, bool v2 /* the shape fits dnn_bwd2_kernel */) {
   const int mode = knobs().big_bwd;
   if (mode != 1) return mode >= 2;
-  const bool v2 = knobs().bwd_nw == 8 && p.maxdim <= 512 &&
-                  bwd2_lds_floats(p, bwd_rows_per_wg(p, N), 8) * sizeof(float) <= 160 * 1024;
   return N >= (v2 ? 16384 : 4096);
 }
 
@@ -670,42 +669,111 @@ static bool bwd_wide_plan(const DnnPlan& p, int64_t N, WideBwd* wb, size_t* lds_
   return true;
 }
 
+// Does a step of `batch` lists of L take dnn_fb_kernel, and on how many waves per workgroup?  0 = no (the separate kernels), 8 / 16.
+// av: every operand, the weight copies included, takes the 16-byte paths.  The 16-wave build (ULTR_FB_NW) covers split-half products
+// with every tile at most 256 wide (the split-half copies need widths >= 256, so every hidden layer is exactly 256 wide: each of the
+// 16 waves owns exactly one 16-column tile of every product), where its 16 column-partial rows still fit the LDS.
+#ifndef FB_NW_DEFAULT
+#define FB_NW_DEFAULT 16
+#endif
+static int fused_fb_waves(const DnnPlan& p, bool av, int64_t batch, int L, size_t* lds_out) {
+  if (knobs().no_fused_fb != 0 || L > 16) return 0;
+  const int lpb = 16 / L;
+  const int64_t N = batch * L, nblk = (batch + lpb - 1) / lpb;
+  const size_t lds = fb_lds_floats(p, 8) * sizeof(float);
+  const bool ok = av && p.nl >= 2 && p.maxdim <= 512 && p.pv_total <= 3 * 512 * 4 && lds <= 160 * 1024 &&
+                  nblk <= (int64_t)knobs().fb_max_wg_per_cu * dnn_device_cus() &&  // one round of workgroups (tools/fused_threshold.py:
+                                                                                   // B=256 62 vs 68 us, B=288 94 vs 70 us)
+                  nblk <= (N + 8) / 9 + 1 &&                                       // vector-slab allocation (>= 9 live rows / block)
+                  p.sv_total * 4 < ((int64_t)1 << 31) && p.P * 4 < ((int64_t)1 << 31);
+  if (!ok) return 0;
+  const int want = knobs().fb_nw == 8 || knobs().fb_nw == 16 ? knobs().fb_nw : FB_NW_DEFAULT;
+  // static LDS of the kernel: the layer records and the 16 per-row output scales
+  const size_t lds16 = fb_lds_floats(p, 16) * sizeof(float), stat = (size_t)ULTR_MAXL * FbPlan::NFIELD * sizeof(int) + 16 * sizeof(float);
+  const bool nw16 = want == 16 && p.fb_h3 != 0 && p.maxdim <= 256 && lds16 + stat <= 160 * 1024;
+  *lds_out = nw16 ? lds16 : lds;
+  return nw16 ? 16 : 8;
+}
+
+// The route of one call (DnnRoute, ultr_dnn_kernels.h): the ONE place that picks among the kernels.  The entry points below read it
+// and launch; ultr_dnn_route and the older queries read it and answer.
+static DnnRoute dnn_route(const DnnPlan& p, int64_t batch, int L, int64_t n_docs, const DnnOperands& o, DnnCall call) {
+  DnnRoute r = {};
+  const Knobs& k = knobs();
+  const int64_t N = batch * L, lim = (int64_t)1 << 31;
+  size_t wlds = 0;
+  const size_t cap = 160 * 1024;  // LDS of a workgroup
+  r.vm = vecmask_for(p, o);
+  r.av = all_vec(p, r.vm, N, n_docs) && k.no_vec == 0;
+  if (call == DNN_EVAL_FWD || call == DNN_TRAIN_FWD) {
+    // the fast paths need the k-major weight copy (ultr_dnn_build_wt / kept current by ultr_apply_update)
+    r.av = r.av && (o.wt || p.nl == 1) && o.wt16;
+    r.fwd_rows = fwd_rows_per_wg(); r.fwd_nw = k.fwd_nw; r.fwd_lds = fwd_lds_bytes(p, r.fwd_rows);
+    if (call == DNN_TRAIN_FWD && o.wt && r.av && ultr_dnn_big_ok(p, N, n_docs) && k.big_fwd != 0 &&
+        (big_fwd_wanted(p, N, r.fwd_lds) || r.fwd_lds > cap)) {
+      // training forward of a big batch: one pass per layer (needs `saved` for the activations between the passes)
+      r.fwd = ULTR_DNN_PER_LAYER; r.fwd_rows = 0; r.fwd_split_half = k.fwd_h3 != 0 && !p.no_h3;
+    } else if (r.av && o.wt && fwd_wide_plan(p, N, &r.wp, &wlds)) {
+      r.fwd = ULTR_DNN_WIDE; r.fwd_rows = r.wp.R; r.fwd_lds = wlds;
+    } else if (r.fwd_lds > cap) {
+      r.fwd = ULTR_DNN_UNSUPPORTED;
+    } else {
+      r.fwd = ULTR_DNN_TILE;
+      // one workgroup per CU anyway and a layer that takes 64-column chunks: the 16-byte-load build
+      if (r.av && r.fwd_rows == 16 && r.fwd_nw == 8 && k.fwd_q4 && r.fwd_lds > 80 * 1024)
+        for (int j = 0; j < p.nl - 1; ++j) r.fwd_q4 = r.fwd_q4 || (p.M[j] % 64 == 0 && p.M[j] >= 512);
+    }
+    return r;
+  }
+  r.g = bwd_geom(p, N, r.av); r.bwd_nw = k.bwd_nw;
+  if (call == DNN_STEP_SOFTMAX) {
+    r.fb_waves = fused_fb_waves(p, r.av && o.wt && o.wt16, batch, L, &r.fb_lds);
+    if (r.fb_waves == 0) return r;  // the separate calls
+    r.fb_lpb = 16 / L; r.fb_blocks = (batch + r.fb_lpb - 1) / r.fb_lpb;
+    r.fwd = r.bwd = ULTR_DNN_FUSED; r.fwd_rows = r.fb_lpb * L; r.loss = ULTR_DNN_LOSS_FUSED;
+    r.g.nrb = (int)r.fb_blocks;  // vector slabs / loss partials: one per fused block
+    r.g.wg_prenorm = 1;          // the fused kernel leaves the ready-made wgrad operands in `saved`
+    return r;
+  }
+  // the row-local backward.  dnn_bwdw_kernel and the per-layer launches take dscores: a softmax loss then runs as its own launch
+  const size_t lds = bwd_lds_bytes(p, r.g.rblk), lds2 = bwd2_lds_floats(p, r.g.rblk, 8) * sizeof(float);
+  const bool v2 = k.bwd_nw == 8 && p.maxdim <= 512 && lds2 <= cap;  // dnn_bwd2_kernel: K_j <= 512, 8 waves, LDS budget (and aligned operands)
+  const bool by_dscores = o.dscores && r.av && p.nl >= 2;
+  const bool big = by_dscores && ultr_dnn_big_ok(p, N, n_docs) && k.big_bwd != 0 && (big_bwd_wanted(N, v2) || lds > cap);
+  if (ultr_tail_len(L) > 4096 || (lds > cap && !big)) {
+    r.bwd = ULTR_DNN_UNSUPPORTED;
+  } else if (by_dscores && o.wt && o.wt16 && bwd_wide_plan(p, N, &r.wb, &wlds)) {
+    r.bwd = ULTR_DNN_WIDE; r.g.rblk = r.wb.R;
+    r.g.nrb = (int)((N + r.wb.R - 1) / r.wb.R);  // one vector slab per workgroup
+  } else if (big) {
+    r.bwd = ULTR_DNN_PER_LAYER; r.bwd_split_half = k.bwd_h3 != 0 && !p.no_h3 && o.wt;
+    r.g.nrb = (int)((N + ULTR_BIG_ROWS - 1) / ULTR_BIG_ROWS);  // one vector slab per row block of the row kernels
+  } else {
+    r.bwd = r.av && v2 && p.sv_total * 4 < lim && p.P * 4 < lim ? ULTR_DNN_TILE2 : ULTR_DNN_TILE;
+  }
+  r.bwd_lds = r.bwd == ULTR_DNN_WIDE ? wlds : r.bwd == ULTR_DNN_TILE2 ? lds2 : lds;
+  r.loss = call == DNN_BWD_SOFTMAX && (r.bwd == ULTR_DNN_TILE || r.bwd == ULTR_DNN_TILE2) ? ULTR_DNN_LOSS_PROLOGUE : ULTR_DNN_LOSS_LAUNCH;
+  return r;
+}
 
 extern "C" int ultr_dnn_forward(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features,
                                 int64_t n_docs, const int32_t* docids, int32_t batch, int32_t list_size, float* scores,
                                 void* saved, void* stream) {
   if (!params || !docids || !scores || batch <= 0 || list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features))
     return ULTR_E_BADARG;
-  const int64_t N = (int64_t)batch * list_size;
   DnnPlan p;
-  if (!ultr_make_dnn_plan(d, N, &p)) return ULTR_E_BADARG;
-  const int R = fwd_rows_per_wg(p, N);
-  const size_t lds = fwd_lds_bytes(p, R);
-  const int nw = knobs().fwd_nw;
-  const int vm = vecmask_for(p, params, features);
+  if (!ultr_make_dnn_plan(d, (int64_t)batch * list_size, &p)) return ULTR_E_BADARG;
+  const DnnRoute r = dnn_route(p, batch, list_size, n_docs, operands_of(params, features, wt, nullptr), saved ? DNN_TRAIN_FWD : DNN_EVAL_FWD);
   hipStream_t st = (hipStream_t)stream;
   UltrProfScope prof(ULTR_K_FWD, st);
-  // the fast path needs the k-major weight copy (ultr_dnn_build_wt / kept current by ultr_apply_update)
-  const bool av = all_vec(p, vm, N, n_docs) && knobs().no_vec == 0 && (wt != nullptr || p.nl == 1) &&
-                  ((uintptr_t)wt & 15) == 0;
-  // training forward of a big batch: one pass per layer (needs `saved` for the activations between the passes)
-  if (saved != nullptr && wt != nullptr && av && ultr_dnn_big_ok(p, N, n_docs) &&
-      knobs().big_fwd != 0 && (big_fwd_wanted(p, N, lds) || lds > 160 * 1024))
+  if (r.fwd == ULTR_DNN_PER_LAYER)
     return ultr_dnn_big_forward(p, params, wt, features, n_docs, docids, (int)batch, (int)list_size, scores, (float*)saved, st,
-                                prof.on ? prof.a : nullptr, prof.on ? prof.b : nullptr, knobs().fwd_h3 != 0 && !p.no_h3 && wt != nullptr);
-  {
-    WidePlan wp;
-    size_t wlds = 0;
-    if (av && wt != nullptr && fwd_wide_plan(p, N, &wp, &wlds)) {
-      return ultr_launch_dnn_fwdw(prof, p, wp, wlds, st, features, n_docs, docids, (int)batch, (int)list_size, scores, (float*)saved, wt);
-    }
-  }
-  if (lds > 160 * 1024) return ULTR_E_UNSUPPORTED;
-  bool q4 = false;  // one workgroup per CU anyway and a layer that takes 64-column chunks: the 16-byte-load build
-  if (av && R == 16 && nw == 8 && knobs().fwd_q4 && lds > 80 * 1024)
-    for (int j = 0; j < p.nl - 1; ++j) q4 = q4 || (p.M[j] % 64 == 0 && p.M[j] >= 512);
-  return ultr_launch_dnn_fwd(prof, p, R, nw, av, q4, lds, st, params, features, n_docs, docids, (int)batch, (int)list_size, scores, (float*)saved, wt,
-                             vm);
+                                prof.on ? prof.a : nullptr, prof.on ? prof.b : nullptr, r.fwd_split_half);
+  if (r.fwd == ULTR_DNN_WIDE)
+    return ultr_launch_dnn_fwdw(prof, p, r.wp, r.fwd_lds, st, features, n_docs, docids, (int)batch, (int)list_size, scores, (float*)saved, wt);
+  if (r.fwd != ULTR_DNN_TILE) return ULTR_E_UNSUPPORTED;
+  return ultr_launch_dnn_fwd(prof, p, r.fwd_rows, r.fwd_nw, r.av, r.fwd_q4, r.fwd_lds, st, params, features, n_docs, docids, (int)batch,
+                             (int)list_size, scores, (float*)saved, wt, r.vm);
 }
 
 // validation(): ultr_dnn_forward (saved = NULL) + ultr_ndcg_report of its scores behind ONE host call.  (Round 6 also built the ONE-LAUNCH
@@ -737,27 +805,39 @@ extern "C" int ultr_dnn_forward_metrics(const ultr_dnn_desc* d, const float* par
                              masked_out, ws, counter, host_report, seq, stream);
 }
 
-extern "C" int32_t ultr_dnn_forward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows, int32_t training) {
+// ---- the queries: the route of a call with 16-byte aligned operands and the weight copies present (include/ultr_hip.h) ----
+static bool route_query(const ultr_dnn_desc* d, int64_t batch, int L, int64_t n_docs, DnnCall call, DnnRoute* r) {
   DnnPlan p;
-  if (n_rows <= 0 || !ultr_make_dnn_plan(d, n_rows, &p)) return -1;
-  const int R = fwd_rows_per_wg(p, n_rows);
-  const size_t lds = fwd_lds_bytes(p, R);
-  if (training && ultr_dnn_big_ok(p, n_rows, n_rows) && knobs().big_fwd != 0 && (big_fwd_wanted(p, n_rows, lds) || lds > 160 * 1024)) return 0;
-  WidePlan wp;
-  size_t wlds = 0;
-  if (knobs().no_vec == 0 && fwd_wide_plan(p, n_rows, &wp, &wlds)) return 1000 + wp.R;
-  return R;
+  if (batch <= 0 || L <= 0 || n_docs < 0 || !ultr_make_dnn_plan(d, batch * L, &p)) return false;
+  *r = dnn_route(p, batch, L, n_docs, DnnOperands{true, true, true, true, true}, call);
+  return true;
 }
-
+extern "C" int ultr_dnn_route(const ultr_dnn_desc* d, int32_t batch, int32_t list_size, int64_t n_docs, int32_t call, ultr_dnn_route_info* out) {
+  DnnRoute f, b;
+  if (!out || call < ULTR_DNN_CALL_EVAL || call > ULTR_DNN_CALL_STEP_DSCORES) return ULTR_E_BADARG;
+  if (!route_query(d, batch, list_size, n_docs, call == ULTR_DNN_CALL_EVAL ? DNN_EVAL_FWD : DNN_TRAIN_FWD, &f)) return ULTR_E_BADARG;
+  b = f;  // (evaluation: no backward part; a step, as ultr_train_step: the fused launch where the shape qualifies, else the separate calls)
+  if (call == ULTR_DNN_CALL_STEP_SOFTMAX) route_query(d, batch, list_size, n_docs, DNN_STEP_SOFTMAX, &b);
+  if (b.fb_waves != 0) f = b;
+  else if (call != ULTR_DNN_CALL_EVAL)
+    route_query(d, batch, list_size, n_docs, call == ULTR_DNN_CALL_STEP_SOFTMAX ? DNN_BWD_SOFTMAX : DNN_BWD_DSCORES, &b);
+  const int bwd_rows = b.bwd == ULTR_DNN_FUSED ? b.fwd_rows : (b.bwd == ULTR_DNN_NONE || b.bwd == ULTR_DNN_PER_LAYER) ? 0 : b.g.rblk;
+  *out = ultr_dnn_route_info{b.fb_waves, f.fwd, f.fwd_rows, b.bwd, bwd_rows, b.loss, b.g.wg_h3, {0}};
+  return (f.fwd == ULTR_DNN_UNSUPPORTED || b.bwd == ULTR_DNN_UNSUPPORTED) ? ULTR_E_UNSUPPORTED : 0;
+}
+// the older encodings (n_rows: as many lists of one document, gathered from as many)
+static int32_t tile_rows_code(int family, int rows) { return family == ULTR_DNN_PER_LAYER ? 0 : family == ULTR_DNN_WIDE ? 1000 + rows : rows; }
+extern "C" int32_t ultr_dnn_forward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows, int32_t training) {
+  DnnRoute r;
+  return route_query(d, n_rows, 1, n_rows, training ? DNN_TRAIN_FWD : DNN_EVAL_FWD, &r) ? tile_rows_code(r.fwd, r.fwd_rows) : -1;
+}
 extern "C" int32_t ultr_dnn_backward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows) {
-  DnnPlan p;
-  BwdPlan bp;
-  if (n_rows <= 0 || !ultr_make_dnn_plan(d, n_rows, &p) || !ultr_make_bwd_plan(p, n_rows, &bp)) return -1;
-  WideBwd wb;
-  size_t wl = 0;
-  if (knobs().no_vec == 0 && bwd_wide_plan(p, n_rows, &wb, &wl)) return 1000 + wb.R;
-  if (knobs().big_bwd != 0 && ultr_dnn_big_ok(p, n_rows, n_rows) && (big_bwd_wanted(p, n_rows) || bwd_lds_bytes(p, bp.rblk) > 160 * 1024)) return 0;
-  return bp.rblk;
+  DnnRoute r;
+  return route_query(d, n_rows, 1, n_rows, DNN_BWD_DSCORES, &r) ? tile_rows_code(r.bwd, r.g.rblk) : -1;
+}
+extern "C" int32_t ultr_fused_fb_waves(const ultr_dnn_desc* d, int32_t batch, int32_t list_size) {
+  DnnRoute r;
+  return route_query(d, batch, list_size, 0, DNN_STEP_SOFTMAX, &r) ? r.fb_waves : -1;
 }
 
 bool ultr_wgrad_h3_geometry(int64_t T, int M, int K, int* nsplit, int* rows_per_split) {
@@ -774,72 +854,36 @@ bool ultr_wgrad_h3_geometry(int64_t T, int M, int K, int* nsplit, int* rows_per_
   return true;
 }
 
-static int backward_impl(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs,
-                         const int32_t* docids, int32_t batch, int32_t list_size, const void* saved, const float* dscores,
-                         const void* loss_ws, void* bwd_ws, float* grads, void* stream, FusedSoftmax fl,
-                         StepCtx* ctx /* the step in flight (ultr_plan.h); nullptr: a stand-alone call */, int fused_rb = 0 /* > 0: the fused forward+backward kernel ran with this many rows per block;
-                                             only the weight gradients and the reduction remain */) {
-  if (!params || !docids || !saved || (!dscores && !fl.scores) || !bwd_ws || !grads || batch <= 0 || list_size <= 0 ||
-      n_docs < 0 || (n_docs > 0 && !features))
-    return ULTR_E_BADARG;
-  const int64_t N = (int64_t)batch * list_size;
-  const float* wt = ctx ? ctx->wt : nullptr;  // the weight copies of the step: the public ultr_dnn_backward has no such argument
-  DnnPlan p;
-  BwdPlan bp;
-  if (!ultr_make_dnn_plan(d, N, &p) || !ultr_make_bwd_plan(p, N, &bp)) return ULTR_E_BADARG;
-  const bool l0g_ok = p.nl >= 2;  // the layer-0 shortcut whenever there is a hidden layer (its A/B knob of round 1 is gone: the explicit du_0 path had rotted)
-  const int tail = (int)ultr_tail_len(list_size);
-  if (tail > 4096) return ULTR_E_UNSUPPORTED;
-  const size_t lds = bwd_lds_bytes(p, bp.rblk);
-  const int nw = knobs().bwd_nw;
-  const int vm = vecmask_for(p, params, features);
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  float* ws = (float*)bwd_ws;
-  const bool av = all_vec(p, vm, N, n_docs) && knobs().no_vec == 0;
-  if (bp.wg_h3 && !av) ultr_make_bwd_plan(p, N, &bp, 0);  // the split-half weight gradients take 16-byte paths only
-  if (fused_rb > 0) bp.nrb = (int)((N + fused_rb - 1) / fused_rb);  // vector slabs / loss partials: one per fused block
-  const bool big = fused_rb == 0 && dscores != nullptr && av && l0g_ok && ultr_dnn_big_ok(p, N, n_docs) &&
-                   knobs().big_bwd != 0 && (big_bwd_wanted(p, N) || lds > 160 * 1024);
-  if (lds > 160 * 1024 && !big) return ULTR_E_UNSUPPORTED;
-  // fast variant: aligned shapes, K_j <= 512, 8 waves, LDS budget (see dnn_bwd2_kernel)
-  const size_t lds2 = bwd2_lds_floats(p, bp.rblk, 8) * sizeof(float);
-  const bool v2 = av && nw == 8 && p.maxdim <= 512 && lds2 <= 160 * 1024 && p.sv_total * 4 < ((int64_t)1 << 31) &&
-                  p.P * 4 < ((int64_t)1 << 31);
-  bp.l0g = l0g_ok ? 1 : 0;  // every backward kernel skips du_0; the wgrad launch makes up for it
-  bp.wg_prenorm = (fused_rb > 0) ? 1 : 0;  // the fused kernel left the ready-made wgrad operands in `saved`
-  WideBwd wb;
-  size_t wblds = 0;
-  const bool wide = fused_rb == 0 && dscores != nullptr && av && l0g_ok && wt != nullptr && ((uintptr_t)wt & 15) == 0 &&
-                    bwd_wide_plan(p, N, &wb, &wblds);
-  if (fused_rb > 0) {
-    // the row-local half already ran inside dnn_fb_kernel
-  } else if (wide) {
+// what every backward entry point hands on (ctx: the step in flight, ultr_plan.h; nullptr: a stand-alone call)
+struct BwdArgs {
+  const float* params; const float* features; int64_t n_docs; const int32_t* docids; int32_t batch, list_size;
+  const void* saved; const void* loss_ws; void* bwd_ws; float* grads; void* stream; StepCtx* ctx;
+};
+// the row-local backward the route names (none: it ran inside dnn_fb_kernel), the weight gradients, the slab reduction.  bp is final
+// but for the chunking of the loss-partial fold, which depends on the partial count of this launch
+static int backward_impl(const DnnPlan& p, const DnnRoute& r, BwdPlan bp, const BwdArgs& a, const float* dscores, const FusedSoftmax& fl) {
+  StepCtx* ctx = a.ctx;
+  const float *params = a.params, *features = a.features, *saved = (const float*)a.saved, *wt = ctx ? ctx->wt : nullptr;  // (the step's weight copies)
+  const int batch = a.batch, list_size = a.list_size, tail = (int)ultr_tail_len(list_size);
+  float *ws = (float*)a.bwd_ws, *grads = a.grads;
+  hipStream_t st = (hipStream_t)a.stream;
+  if (r.bwd != ULTR_DNN_FUSED) {
     UltrProfScope prof(ULTR_K_BWD, st);
-    bp.rblk = wb.R;
-    bp.nrb = (int)((N + wb.R - 1) / wb.R);  // one vector slab per workgroup
-    const int rcw = ultr_launch_dnn_bwdw(prof, p, bp, wb, wblds, st, (const float*)saved, dscores, ws, wt);
-    if (rcw) return rcw;
-  } else if (big) {
-    UltrProfScope prof(ULTR_K_BWD, st);
-    bp.nrb = (int)((N + ULTR_BIG_ROWS - 1) / ULTR_BIG_ROWS);  // one vector slab per row block of the row kernels
-    const int rc = ultr_dnn_big_backward(p, bp, params, (const float*)saved, dscores, ws, st, prof.on ? prof.a : nullptr,
-                                         prof.on ? prof.b : nullptr, knobs().bwd_h3 != 0 && !p.no_h3 && wt != nullptr);
+    int rc;
+    if (r.bwd == ULTR_DNN_WIDE)
+      rc = ultr_launch_dnn_bwdw(prof, p, bp, r.wb, r.bwd_lds, st, saved, dscores, ws, wt);
+    else if (r.bwd == ULTR_DNN_PER_LAYER)
+      rc = ultr_dnn_big_backward(p, bp, params, saved, dscores, ws, st, prof.on ? prof.a : nullptr, prof.on ? prof.b : nullptr, r.bwd_split_half);
+    else if (r.bwd == ULTR_DNN_TILE2)
+      rc = ultr_launch_dnn_bwd2(prof, p, bp, r.bwd_lds, st, params, features, a.n_docs, a.docids, batch, list_size, saved, dscores, ws, fl, wt);
+    else
+      rc = ultr_launch_dnn_bwd(prof, p, bp, r.bwd_nw, r.av, r.bwd_lds, st, params, features, a.n_docs, a.docids, batch, list_size, saved, dscores, ws,
+                               r.vm, fl);
     if (rc) return rc;
-  } else if (v2) {
-    UltrProfScope prof(ULTR_K_BWD, st);
-    const int rc2 = ultr_launch_dnn_bwd2(prof, p, bp, lds2, st, params, features, n_docs, docids, (int)batch, (int)list_size, (const float*)saved,
-                                         dscores, ws, fl, wt);
-    if (rc2) return rc2;
-  } else {
-    UltrProfScope prof(ULTR_K_BWD, st);
-    const int rc1 = ultr_launch_dnn_bwd(prof, p, bp, nw, av, lds, st, params, features, n_docs, docids, (int)batch, (int)list_size, (const float*)saved,
-                                        dscores, ws, vm, fl);
-    if (rc1) return rc1;
   }
-  e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  const float* lp = (const float*)loss_ws;
+  const float* lp = (const float*)a.loss_ws;
   const int nlp = fl.scores ? bp.nrb : (int)ultr_loss_parts(batch);
   if (nlp > 1024) {
     int len = (nlp + 63) / 64;
@@ -869,8 +913,8 @@ static int backward_impl(const ultr_dnn_desc* d, const float* params, const floa
       cd.world = 0;
     }
     if (bp.lf_chunks > 0) er.host = nullptr;  // two-level fold of > 1024 partials: the loss is only final in the reduction launch
-    const int rcg = ultr_launch_dnn_wgrad(prof, p, bp, av, bp.wg_h3 != 0, wlds, wgrid, st, params, features, n_docs, docids, (int)batch,
-                                          (int)list_size, (const float*)saved, ws, bp.wg_h3 ? 0 : (vm >> 31) & 1, grads, lp, nlp, tail, er, cd);
+    const int rcg = ultr_launch_dnn_wgrad(prof, p, bp, r.av, bp.wg_h3 != 0, wlds, wgrid, st, params, features, a.n_docs, a.docids, batch,
+                                          list_size, saved, ws, bp.wg_h3 ? 0 : (r.vm >> 31) & 1, grads, lp, nlp, tail, er, cd);
     if (rcg) return rcg;
   }
   RedPlan rp;
@@ -902,6 +946,25 @@ static int backward_impl(const ultr_dnn_desc* d, const float* params, const floa
   return (int)hipGetLastError();
 }
 
+// behind both public backward calls: the plans, the route, the launches.  sm.scores != nullptr: the NA / IPW loss of these scores, in
+// the backward kernel's prologue or - the wide-tile and the per-layer backward take dscores - as its own launch into sm.dscores_out
+static int backward_call(const ultr_dnn_desc* d, const BwdArgs& a, const float* dscores, const FusedSoftmax& sm) {
+  if (!a.params || !a.docids || !a.saved || !a.bwd_ws || !a.grads || a.batch <= 0 || a.list_size <= 0 || a.n_docs < 0 ||
+      (a.n_docs > 0 && !a.features) || (!dscores && !sm.scores))
+    return ULTR_E_BADARG;
+  const int64_t N = (int64_t)a.batch * a.list_size;
+  DnnPlan p;
+  BwdPlan bp;
+  if (!ultr_make_dnn_plan(d, N, &p)) return ULTR_E_BADARG;
+  const DnnRoute r = dnn_route(p, a.batch, a.list_size, a.n_docs, operands_of(a.params, a.features, a.ctx ? a.ctx->wt : nullptr, sm.scores ? sm.dscores_out : dscores),
+                               sm.scores ? DNN_BWD_SOFTMAX : DNN_BWD_DSCORES);
+  if (r.bwd == ULTR_DNN_UNSUPPORTED) return ULTR_E_UNSUPPORTED;
+  if (!ultr_make_bwd_plan(p, N, &bp, r.g)) return ULTR_E_BADARG;
+  if (r.loss == ULTR_DNN_LOSS_PROLOGUE || !sm.scores) return backward_impl(p, r, bp, a, dscores, sm);
+  const int rc = ultr_softmax_ce(sm.scores, sm.labels, sm.pw, sm.ipw, sm.n_ipw, a.batch, a.list_size, sm.dscores_out, sm.loss_part, a.stream);
+  return rc ? rc : backward_impl(p, r, bp, a, sm.dscores_out, FusedSoftmax{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr});
+}
+
 extern "C" int ultr_dnn_backward(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs,
                                  const int32_t* docids, int32_t batch, int32_t list_size, const void* saved,
                                  const float* dscores, const void* loss_ws, void* bwd_ws, float* grads, void* stream) {
@@ -910,8 +973,8 @@ extern "C" int ultr_dnn_backward(const ultr_dnn_desc* d, const float* params, co
 int ultr_dnn_backward_ctx(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs, const int32_t* docids,
                           int32_t batch, int32_t list_size, const void* saved, const float* dscores, const void* loss_ws, void* bwd_ws,
                           float* grads, void* stream, StepCtx* ctx) {
-  FusedSoftmax fl = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, dscores, loss_ws, bwd_ws, grads, stream, fl, ctx);
+  const BwdArgs a = {params, features, n_docs, docids, batch, list_size, saved, loss_ws, bwd_ws, grads, stream, ctx};
+  return backward_call(d, a, dscores, FusedSoftmax{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr});
 }
 
 extern "C" int ultr_dnn_backward_softmax(const ultr_dnn_desc* d, const float* params, const float* features, int64_t n_docs,
@@ -927,62 +990,8 @@ int ultr_dnn_backward_softmax_ctx(const ultr_dnn_desc* d, const float* params, c
                                   const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw, float* dscores_out,
                                   void* loss_ws, void* bwd_ws, float* grads, void* stream, StepCtx* ctx) {
   if (!scores || !labels || !loss_ws || (ipw_table && n_ipw <= 0)) return ULTR_E_BADARG;
-  {
-    // big batches take the per-layer backward, which wants the loss as its own stage
-    DnnPlan p;
-    const int64_t N = (int64_t)batch * list_size;
-    // ... and so do shapes whose row tile does not fit the LDS (a layer wider than 512 at a small batch): the same condition
-    // backward_impl applies to the other algorithms - without it this entry point returned ULTR_E_UNSUPPORTED there
-    BwdPlan bp0;
-    const bool planned = dscores_out && batch > 0 && list_size > 0 && ultr_make_dnn_plan(d, N, &p) && ultr_make_bwd_plan(p, N, &bp0);
-    // ... and the wide-tile backward of ultr_train_step (dnn_bwdw_kernel), which takes dscores too
-    WideBwd wb0;
-    size_t wl0 = 0;
-    const bool wide = planned && ctx && ctx->wt != nullptr && knobs().no_vec == 0 && bwd_wide_plan(p, N, &wb0, &wl0);
-    if (planned && (wide || ((big_bwd_wanted(p, N) || bwd_lds_bytes(p, bp0.rblk) > 160 * 1024) && knobs().big_bwd != 0 &&
-        knobs().no_vec == 0 && ultr_dnn_big_ok(p, N, n_docs)))) {
-      const int rc = ultr_softmax_ce(scores, labels, pw, ipw_table, n_ipw, batch, list_size, dscores_out, loss_ws, stream);
-      if (rc) return rc;
-      FusedSoftmax none = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-      return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, dscores_out, loss_ws, bwd_ws, grads, stream, none, ctx);
-    }
-  }
-  FusedSoftmax fl = {scores, labels, pw, ipw_table, (int)n_ipw, dscores_out, (float*)loss_ws};
-  return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, nullptr, loss_ws, bwd_ws, grads, stream, fl, ctx);
-}
-
-// Does a step of `batch` lists of L take dnn_fb_kernel, and on how many waves per workgroup?  0 = no (the separate kernels), 8 / 16.
-// `vm` as vecmask_for gives it, wt_aligned = the weight copies sit on a 16-byte boundary.  The 16-wave build (ULTR_FB_NW) covers
-// split-half products with every tile at most 256 wide (the split-half copies need widths >= 256, so every hidden layer is exactly
-// 256 wide: each of the 16 waves owns exactly one 16-column tile of every product), where its 16 column-partial rows still fit the LDS.
-#ifndef FB_NW_DEFAULT
-#define FB_NW_DEFAULT 16
-#endif
-static int fused_fb_waves(const DnnPlan& p, int vm, bool wt_aligned, int64_t batch, int L, int64_t n_docs, size_t* lds_out) {
-  if (knobs().no_fused_fb != 0 || batch <= 0 || L <= 0 || L > 16) return 0;
-  const int64_t N = batch * L;
-  const int lpb = 16 / L;
-  const int64_t nblk = (batch + lpb - 1) / lpb;
-  const size_t lds = fb_lds_floats(p, 8) * sizeof(float);
-  const bool ok = all_vec(p, vm, N, n_docs) && knobs().no_vec == 0 && wt_aligned &&
-                  p.nl >= 2 && p.maxdim <= 512 && p.pv_total <= 3 * 512 * 4 && lds <= 160 * 1024 &&
-                  nblk <= (int64_t)knobs().fb_max_wg_per_cu * dnn_device_cus() &&  // one round of workgroups (tools/fused_threshold.py:
-                                                                                   // B=256 62 vs 68 us, B=288 94 vs 70 us)
-                  nblk <= (N + 8) / 9 + 1 &&                                       // vector-slab allocation (>= 9 live rows / block)
-                  p.sv_total * 4 < ((int64_t)1 << 31) && p.P * 4 < ((int64_t)1 << 31);
-  if (!ok) return 0;
-  const int want = knobs().fb_nw == 8 || knobs().fb_nw == 16 ? knobs().fb_nw : FB_NW_DEFAULT;
-  // static LDS of the kernel: the layer records and the 16 per-row output scales
-  const size_t lds16 = fb_lds_floats(p, 16) * sizeof(float), stat = (size_t)ULTR_MAXL * FbPlan::NFIELD * sizeof(int) + 16 * sizeof(float);
-  const bool nw16 = want == 16 && p.fb_h3 != 0 && p.maxdim <= 256 && lds16 + stat <= 160 * 1024;
-  if (lds_out) *lds_out = nw16 ? lds16 : lds;
-  return nw16 ? 16 : 8;
-}
-extern "C" int32_t ultr_fused_fb_waves(const ultr_dnn_desc* d, int32_t batch, int32_t list_size) {
-  DnnPlan p;
-  if (batch <= 0 || list_size <= 0 || !ultr_make_dnn_plan(d, (int64_t)batch * list_size, &p)) return -1;
-  const float* aligned = reinterpret_cast<const float*>((uintptr_t)16);  // (vecmask_for only looks at the address)
-  return fused_fb_waves(p, vecmask_for(p, aligned, aligned), true, batch, list_size, 0, nullptr);
+  const BwdArgs a = {params, features, n_docs, docids, batch, list_size, saved, loss_ws, bwd_ws, grads, stream, ctx};
+  return backward_call(d, a, nullptr, FusedSoftmax{scores, labels, pw, ipw_table, (int)n_ipw, dscores_out, (float*)loss_ws});
 }
 
 // internal (ultr_train_step): forward + NA/IPW loss + backward for a small batch through dnn_fb_kernel, then the weight
@@ -995,23 +1004,14 @@ int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const f
   if (!params || !wt || !docids || !scores || !saved || !labels || !loss_ws || !bwd_ws || !grads || batch <= 0 ||
       list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features) || (ipw_table && n_ipw <= 0))
     return ULTR_E_BADARG;
-  const int L = list_size;
-  if (knobs().no_fused_fb != 0 || L > 16) return ULTR_E_UNSUPPORTED;
-  const int64_t N = (int64_t)batch * L;
+  const int64_t N = (int64_t)batch * list_size;
   DnnPlan p;
   BwdPlan bp;
-  if (!ultr_make_dnn_plan(d, N, &p) || !ultr_make_bwd_plan(p, N, &bp)) return ULTR_E_BADARG;
-  const int lpb = 16 / L, rb = lpb * L;
-  const int64_t nblk = (batch + lpb - 1) / lpb;
-  size_t lds = 0;
-  const int fb_nw = fused_fb_waves(p, vecmask_for(p, params, features), ((uintptr_t)wt & 15) == 0, batch, L, n_docs, &lds);
-  if (fb_nw == 0) return ULTR_E_UNSUPPORTED;
-  bp.nrb = (int)nblk;
-  bp.l0g = p.nl >= 2 ? 1 : 0;  // must match backward_impl's choice
-  bp.wg_prenorm = 1;
-  hipStream_t st = (hipStream_t)stream;
+  if (!ultr_make_dnn_plan(d, N, &p)) return ULTR_E_BADARG;
+  const DnnRoute route = dnn_route(p, batch, list_size, n_docs, operands_of(params, features, wt, dscores_out), DNN_STEP_SOFTMAX);
+  if (route.fb_waves == 0) return ULTR_E_UNSUPPORTED;
+  if (!ultr_make_bwd_plan(p, N, &bp, route.g)) return ULTR_E_BADARG;
   FusedSoftmax fl = {nullptr, labels, pw, ipw_table, (int)n_ipw, dscores_out, (float*)loss_ws};
-  float* ws = (float*)bwd_ws;
   FbPlan fp;
   memset(&fp, 0, sizeof(fp));
   for (int j = 0; j < p.nl; ++j) {
@@ -1026,17 +1026,16 @@ int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const f
     put64(FbPlan::DZ_OFF, j < p.nl - 1 ? bp.dz_off[j] : 0); put64(FbPlan::WT_OFF, p.wt_off[j]);
     put64(FbPlan::WHF_OFF, p.whf_off[j]); put64(FbPlan::WHB_OFF, p.whb_off[j]);
   }
-  hipError_t e;
   {
-    UltrProfScope prof(ULTR_K_FUSED, st);
-    const int rcf = ultr_launch_dnn_fb(prof, p, bp, fb_nw, lds, nblk, st, params, wt, features, n_docs, docids, (int)batch, L, lpb, scores, (float*)saved, ws,
-                                       fl, fp);
+    UltrProfScope prof(ULTR_K_FUSED, (hipStream_t)stream);
+    const int rcf = ultr_launch_dnn_fb(prof, p, bp, route.fb_waves, route.fb_lds, route.fb_blocks, (hipStream_t)stream, params, wt, features, n_docs, docids,
+                                       (int)batch, (int)list_size, route.fb_lpb, scores, (float*)saved, (float*)bwd_ws, fl, fp);
     if (rcf) return rcf;
   }
-  e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   fl.scores = scores;  // marks "loss partials come one per row block" for the reduction
-  return backward_impl(d, params, features, n_docs, docids, batch, list_size, saved, nullptr, loss_ws, bwd_ws, grads, stream, fl,
-                       ctx, rb);
+  const BwdArgs a = {params, features, n_docs, docids, batch, list_size, saved, loss_ws, bwd_ws, grads, stream, ctx};
+  return backward_impl(p, route, bp, a, nullptr, fl);
 }
 

@@ -802,6 +802,38 @@ struct WideBwd {
   int kslen[ULTR_MAXL];   // 32-deep steps per slice
 };
 
+// ---- the route of one call (ultr_dnn.hip: dnn_route) ----------------------------------------------------------------------------------
+// Every choice among the kernels, decided ONCE per call from the plan, (batch, list_size, n_docs), the knobs and what only the caller
+// knows of its operands; the entry points read it and launch, the queries (ultr_dnn_route, ultr_dnn_forward_tile_rows, ...) read it and
+// answer.  Only the part that belongs to the kind of call is filled; the rest is zero.
+enum DnnCall { DNN_EVAL_FWD, DNN_TRAIN_FWD, DNN_BWD_DSCORES, DNN_BWD_SOFTMAX, DNN_STEP_SOFTMAX };
+struct DnnOperands {
+  bool params16, features16;  // on a 16-byte boundary (features: and present)
+  bool wt, wt16;              // the weight copies are present / on a 16-byte boundary (absent counts as aligned)
+  bool dscores;               // there is a [B, L] buffer a separate loss launch can leave d(loss)/d(scores) in
+};
+struct DnnRoute {
+  int vm;                  // vector mask: bit j = layer j's parameters, bit 31 = the feature rows take aligned float4 loads
+  bool av;                 // every hot-loop load takes them (all_vec, ULTR_NO_VEC; a forward: and the weight copies are usable)
+  // DNN_STEP_SOFTMAX: dnn_fb_kernel
+  int fb_waves;            // 0: the shape does not qualify (the separate calls); 8 / 16
+  int fb_lpb;              // lists per workgroup
+  int64_t fb_blocks;
+  size_t fb_lds;
+  // the forward: ultr_dnn_family, rows per workgroup (0: per-layer), the tile kernel's waves and 16-byte-load build
+  int fwd, fwd_rows, fwd_nw;
+  bool fwd_q4, fwd_split_half;  // (split_half: the per-layer GEMMs on hi / lo planes)
+  size_t fwd_lds;
+  WidePlan wp;
+  // the row-local backward: ultr_dnn_family (g.rblk rows per workgroup), dnn_bwd_kernel's waves
+  int bwd, bwd_nw;
+  bool bwd_split_half;
+  size_t bwd_lds;
+  WideBwd wb;
+  int loss;                // ultr_dnn_loss_place
+  BwdGeom g;               // what ultr_make_bwd_plan is told
+};
+
 // dnn_fb_kernel (ultr_dnn_fb.hip)
 __host__ __device__ static inline size_t fb_lds_floats(const DnnPlan& p, int nw) {
   const size_t ld = fwd_ld(p.maxdim), ldu = bwd_ldu(p.maxdim);

@@ -12,7 +12,7 @@
 // weight-gradient kernels (wg_stage / wg_head, ultr_dnn_wgrad.hip); RedPlan in the slab reductions (red_stage / red_lookup); the
 // update's work map (upd_at, ultr_update.hip).  The plans stay by-value arguments built per call from the model's shape and
 // (B, L): nothing is cached on the device, so nothing can go stale when the shape, the batch or the launch mode changes, and
-// every caller (ultr_train_step, the stage API, SetRank's ultr_wgrad_h3_plain, plans re-made with wg_mode 0) takes the same path.
+// every caller (ultr_train_step, the stage API, SetRank's ultr_wgrad_h3_plain) takes the same path.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -183,14 +183,14 @@ struct BwdPlan {
   // gradients.  Instead the wgrad launch contracts dz_0 with the NORMALISED input xhat_0 (G = dz_0^T xhat_0, S = sum_r dz_0) and
   // its epilogue emits  dW_0 = gamma o G + S (x) beta  (exact algebra, no division) plus partial column sums of
   // d gamma_0 = sum_m W_0[m,:] o G[m,:]  and  d beta_0 = sum_m W_0[m,:] S[m]  per (row block of W_0, row split).
-  int l0g;                  // 1: shortcut active (set by the launcher together with the kernel that skips du_0)
+  int l0g;                  // 1: shortcut active (BwdGeom: every backward kernel skips du_0)
   // 1: `saved` holds what the wgrad launch contracts with, ready-made (the fused forward+backward kernel keeps x_j on chip, so
   // its copies in `saved` serve the weight gradients only): u_j = LayerNorm_j output for j >= 1, xhat_0 (l0g) or u_0 for j = 0.
   // The wgrad loop then issues two loads per 16 MFMAs instead of four and applies no transform.
   int wg_prenorm;
   // 1: the geometry of wl[] (blocks, row splits, slabs) is the one of dnn_wgrad_h3_kernel - weight gradients on the fp16 matrix
-  // cores with split (hi / lo) operands, 128 x 128 blocks staged through LDS (ultr_dnn.hip).  Chosen by ultr_make_bwd_plan from
-  // the shapes and ULTR_WG_H3; the launcher re-plans with wg_mode 0 when the pointers do not allow the 16-byte paths.
+  // cores with split (hi / lo) operands, 128 x 128 blocks staged through LDS (ultr_dnn.hip).  Chosen by the call's route from the
+  // shapes, ULTR_WG_H3 and the operands (BwdGeom::wg_h3: never when the pointers do not allow the 16-byte paths).
   int wg_h3;
   // wg_h3 block numbering: block b works on item  lin = (b % 8) * wg_chunk + b / 8  (consecutive block ids go round-robin to the 8
   // XCDs, so every XCD owns ONE contiguous range of items), items ordered row split first: split = lin / wg_tiles2, tile of all
@@ -237,7 +237,12 @@ struct RedPlan {
 
 struct ultr_dnn_desc;
 bool ultr_make_dnn_plan(const ultr_dnn_desc* d, int64_t N, DnnPlan* p);  // ultr_dnn.hip
-bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, int wg_mode = -1);  // ultr_dnn.hip; wg_mode 0: never the split-half weight gradients
+// what a call's route (DnnRoute, ultr_dnn_kernels.h) fixes of its BwdPlan: the plan is built from it once and is final
+struct BwdGeom {
+  int rblk, nrb;   // rows per workgroup of the row-local backward kernel; vector slabs / loss partials of the prologue = its workgroups
+  int l0g, wg_prenorm, wg_h3;  // BwdPlan's fields of the same names
+};
+bool ultr_make_bwd_plan(const DnnPlan& p, int64_t N, BwdPlan* bp, const BwdGeom& g);  // ultr_dnn.hip
 void ultr_make_red_plan(const DnnPlan& p, const BwdPlan& bp, RedPlan* rp); // ultr_dnn.hip
 
 // library-internal, ultr_dnn_big.hip: the per-layer (un-fused) training forward / row-local backward for big batches
