@@ -101,6 +101,13 @@ int64_t ultr_loss_workspace_bytes(int64_t batch, int32_t list_size);
 /* step-tail partials the stand-alone ultr_*_loss kernels leave in `loss_ws` (one per workgroup) = the n_loss_parts of
  * ultr_setrank_backward */
 int64_t ultr_loss_part_count(int64_t batch);
+/* Dynamic LDS in bytes that the stand-alone loss kernel of `algo` (ULTR_ALGO_SOFTMAX .. ULTR_ALGO_PDGD) requests at list_size
+ * (additive within ABI 8; host-only, launches nothing) - read from the layout the kernel itself carves its LDS with
+ * (csrc/ultr_listloss.h).  ULTR_E_UNSUPPORTED where the entry would refuse the list size: beyond 64 KiB for ultr_softmax_ce,
+ * ultr_dla_loss and ultr_regem_loss, beyond 160 KiB for ultr_pairdebias_loss, ultr_lambdarank_loss and ultr_prs_loss, beyond 256
+ * documents for ultr_pdgd_loss - the longest accepted lists are stated with each entry below.  ULTR_E_BADARG: an algorithm without a
+ * stand-alone loss kernel, list_size <= 0. */
+int64_t ultr_loss_lds_bytes(int32_t algo, int32_t list_size);
 
 /* ---- a2 + a3: gather + DNN forward --------------------------------------------------
  * Replaces BaseAlgorithm.get_ranking_scores + ranking_model (base_algorithm.py:118-154)
@@ -206,7 +213,8 @@ int ultr_grad_sumsq(float* grads, int64_t n_params, int32_t list_size, void* bwd
  * propensity_estimator.py:22-42):  pw[b,l] = labels[l,b] > 0 ? ipw_table[min(l,n_ipw-1)] : 0.
  * pw (explicit [B, L] weights) and ipw_table may both be NULL (NA: weights = 1).
  * Writes dscores[b,l] = softmax(s_b)_l * S_b - w_bl   (the gradient times the global
- * normaliser D = sum w) and per-workgroup partial sums of (loss_sum, D) into loss_ws. */
+ * normaliser D = sum w) and per-workgroup partial sums of (loss_sum, D) into loss_ws.
+ * list_size up to 4095 (64 KiB of LDS, ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
 int ultr_softmax_ce(const float* scores, const float* labels, const float* pw, const float* ipw_table,
                     int32_t n_ipw, int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
 
@@ -216,7 +224,8 @@ int ultr_softmax_ce(const float* scores, const float* labels, const float* pw, c
  * DenoisingNet's Linear(L,1).  logits_to_prob: 0 softmax, 1 sigmoid (dla.py:21-22).
  * dscores = rank-loss gradient x D_rank (the ranker_loss_weight is applied by the update);
  * loss_ws gets (rank_loss_sum, D_rank, exam_loss_sum, D_exam) and the per-position sums of
- * d(exam_loss)/d(propensity) x D_exam. */
+ * d(exam_loss)/d(propensity) x D_exam.
+ * list_size up to 3276 (64 KiB of LDS, ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
 int ultr_dla_loss(const float* scores, const float* labels, const float* prop_params, int32_t logits_to_prob,
                   int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
 
@@ -224,7 +233,8 @@ int ultr_dla_loss(const float* scores, const float* labels, const float* prop_pa
  * Replaces the 2-level Python pair loop of PairDebias.train (pairwise_debias.py:142-157)
  * + pairwise_cross_entropy_loss (base_algorithm.py:228-248), including the reference's xB
  * broadcast inflation; `batch_total` is the GLOBAL batch size (== batch on one GPU).
- * loss_ws gets loss_sum and the per-position t_plus_loss / t_minus_loss sums. */
+ * loss_ws gets loss_sum and the per-position t_plus_loss / t_minus_loss sums.
+ * list_size up to 585 (160 KiB of LDS, ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
 int ultr_pairdebias_loss(const float* scores, const float* labels, const float* t_plus, const float* t_minus,
                          int32_t batch, int32_t list_size, int32_t batch_total, float* dscores, void* loss_ws,
                          void* stream);
@@ -232,7 +242,8 @@ int ultr_pairdebias_loss(const float* scores, const float* labels, const float* 
 /* ---- a11: LambdaRank -----------------------------------------------------------------
  * Replaces LambdaRank.train's loss section (lambda_rank.py:116-135) + dcg/compute_delta_ndcg
  * (lambda_rank.py:247-291): per-list descending sort, pairwise delta-NDCG-weighted
- * BCE-with-logits on sigma(s_i - s_j), batch-global natural-log IDCG (kept separate as D). */
+ * BCE-with-logits on sigma(s_i - s_j), batch-global natural-log IDCG (kept separate as D).
+ * list_size up to 531 (160 KiB of LDS, ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
 int ultr_lambdarank_loss(const float* scores, const float* labels, const float* t_plus, const float* t_minus,
                          float sigma, int32_t batch, int32_t list_size, float* dscores, void* loss_ws,
                          void* stream);
@@ -242,7 +253,8 @@ int ultr_lambdarank_loss(const float* scores, const float* labels, const float* 
  * :20-34): gamma = sigmoid(s); posteriors with the propensity [L]; pseudo-labels ceil(p_r1 - u) with u from
  * `uniforms` [B, L] (teacher-forced) or, when NULL, Philox keyed by (seed, step); BCE-with-logits, mean over
  * B*L (the count is left in the tail as D).  loss_ws also gets the per-position sums of the M-step
- * (regression_EM.py:180-183), applied by ultr_apply_update (aux = propensity).  pseudo_labels_out may be NULL. */
+ * (regression_EM.py:180-183), applied by ultr_apply_update (aux = propensity).  pseudo_labels_out may be NULL.
+ * list_size up to 8190 (64 KiB of LDS, ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
 int ultr_regem_loss(const float* scores, const float* labels, const float* propensity, const float* uniforms,
                     uint64_t seed, uint64_t step, int32_t batch, int32_t list_size, float* dscores,
                     float* pseudo_labels_out, void* loss_ws, void* stream);
@@ -253,7 +265,9 @@ int ultr_regem_loss(const float* scores, const float* labels, const float* prope
  * (0 where ipw == 0), per-list descending sort, prs_ij = ipw_i * pw_j on the pairs i < j of the sorted order,
  * delta-NDCG-weighted F.binary_cross_entropy (logs clamped at -100) of 1 / (exp(-sigma (s_i - s_j)) + 1),
  * batch-global natural-log IDCG (kept separate as D).  The gradient is autograd's through that composition,
- * including its explosion where x rounds to 1 and its NaN where exp overflows in the lower triangle. */
+ * including its explosion where x rounds to 1 and its NaN where exp overflows in the lower triangle.
+ * list_size up to 952 (160 KiB of LDS, ultr_loss_lds_bytes), for ultr_prs_loss_pw too; beyond, ULTR_E_UNSUPPORTED and nothing is
+ * launched. */
 int ultr_prs_loss(const float* scores, const float* labels, const float* ipw_table, int32_t n_ipw, float sigma,
                   int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
 /* The same with a weight per list entry (additive within ABI 8): ipw_bl [B, L], indexed by PRESENTATION position, replaces
@@ -270,7 +284,8 @@ int ultr_prs_loss_pw(const float* scores, const float* labels, const float* ipw_
  * label_k < label_l (pdgd.py:138-172); weight 1 / (1 + exp(min(delta, 20))) with delta the flipped list's sum of log
  * suffix sums minus the original's (pdgd.py:128-134, 160-176), a constant; loss = sum of -w e^{s_l} / (e^{s_l} + e^{s_k}) on
  * the raw scores (pdgd.py:193-205), its gradient autograd's through that expression (NaN where exp overflows).
- * Plain sum (D = 1).  Deterministic (no atomics).  list_size > 256: ULTR_E_UNSUPPORTED. */
+ * Plain sum (D = 1).  Deterministic (no atomics).  list_size up to 256 (one thread per position; 136 KiB of LDS there,
+ * ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
 int ultr_pdgd_loss(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, float tau,
                    int32_t cutoff, int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
 

@@ -308,7 +308,7 @@ def param_update(p, g_raw, state, ss, hyper, tail):
 # the shared case tables
 # ------------------------------------------------------------------------------------------------------------------------
 ALGOS = ("softmax", "dla", "pairdebias", "lambdarank", "regem")
-LENGTHS = (1, 2, 15, 16, 17, 63, 64, 65, 129, 255, 256)   # lane (64) and slice (PD_JW = 16) boundaries, the 256 cap
+LENGTHS = (1, 2, 15, 16, 17, 63, 64, 65, 129, 255, 256)   # lane (64) and slice (LOSS_JW = 16) boundaries, the 256 cap
 SCALE_LENGTHS = (17, 65, 256)
 # Scores x 8: pair gaps reach about +-50, sigmoids and softplus saturate, nothing overflows in float32.  (Per algorithm: the largest
 # of 8, 4, 2 at which the float32 oracle itself holds the bars, test_loss_ref_cpu.py::test_oracle_losses_hold_the_gpu_bars.)
@@ -410,6 +410,9 @@ def loss_cases():
         for L in (20, 70):
             for k in (1, 5, L - 1):
                 out.append(make_case("tie-%s-L%d-k%d" % (algo, L, k), algo, 3, L, tie=k))
+    # the longest lists the pair-walk kernels accept (160 KiB of LDS, tests/test_loss_layout_cpu.py): the last word of the layout
+    out.append(make_case("edge-pairdebias-L585", "pairdebias", 2, 585))
+    out.append(make_case("edge-lambdarank-L531", "lambdarank", 2, 531))
     return {c["name"]: c for c in out}
 
 

@@ -68,7 +68,8 @@ def test_loss_kernels(name):
     wavefront, the cap), B = 3; DLA also with logits_to_prob = sigmoid beyond 64 positions; RegressionEM's `l += 64` loops take up
     to four trips.  scale-*: scores x 8 (LambdaRank x 4, loss_ref.SCORE_SCALE).  labels-*: graded and fractional clicks through
     PairDebias' mask min(1, |c_i - c_j|), a list without a click and one with a single click, a LambdaRank list of all-equal
-    labels (gradients exactly 0).  tie-*: the last 1, 5, L - 1 documents share one score and differ in label - the stable order."""
+    labels (gradients exactly 0).  tie-*: the last 1, 5, L - 1 documents share one score and differ in label - the stable order.
+    edge-*: PairDebias at L = 585 and LambdaRank at L = 531, the longest lists their 160 KiB of LDS hold (B = 2)."""
     case = R.loss_cases()[name]
     run = make_run(case)
     ds, tail = run_loss(run, case)
@@ -77,6 +78,28 @@ def test_loss_kernels(name):
     if name == "labels-lambdarank-flat":
         assert (ds[0] == 0.0).all()
         assert np.abs(ds[1:]).max() > 0 and tail[1] > 0
+
+
+def test_pair_walk_kernels_refuse_lists_beyond_the_lds_budget():
+    """One document past the longest accepted list (edge-pairdebias-L585, edge-lambdarank-L531 above): a host refusal, nothing is
+    launched."""
+    import torch
+    from ultra_pytorch_amd import _lib, hip_ops
+    lib = _lib.load()
+    for fn, L in (("ultr_pairdebias_loss", 586), ("ultr_lambdarank_loss", 532)):
+        s = torch.zeros(1, L, device="cuda")
+        ds = torch.full((1, L), 7.0, device="cuda")
+        ws = torch.zeros(hip_ops.loss_workspace_bytes(1, L) // 4, device="cuda")
+        t = torch.ones(L, device="cuda")
+        if fn == "ultr_pairdebias_loss":
+            rc = lib.ultr_pairdebias_loss(s.data_ptr(), s.data_ptr(), t.data_ptr(), t.data_ptr(), 1, L, 1, ds.data_ptr(), ws.data_ptr(),
+                                          hip_ops.raw_stream())
+        else:
+            rc = lib.ultr_lambdarank_loss(s.data_ptr(), s.data_ptr(), t.data_ptr(), t.data_ptr(), 1.0, 1, L, ds.data_ptr(), ws.data_ptr(),
+                                          hip_ops.raw_stream())
+        assert rc == -2, (fn, rc)  # ULTR_E_UNSUPPORTED
+        torch.cuda.synchronize()
+        assert (ds == 7.0).all() and not ws.any()
 
 
 def hold_step(case, run, g, tail2, out):

@@ -94,10 +94,10 @@ def test_golden_setrank_step():
 
 
 # ---- the loss kernel against the restatement ------------------------------------------------------------------------------
-PRS_JW, LDS_LIMIT = 16, 160 * 1024
+PRS_JW, LDS_LIMIT = 16, 160 * 1024  # csrc/ultr_listloss.h: LOSS_JW
 
 
-def _lds_bytes(L):  # ultr_prs.hip: prs_lds_bytes (one list per workgroup)
+def _lds_bytes(L):  # csrc/ultr_listloss.h: PrsLds (one list per workgroup)
     return ((4 + 2 * L) + 8 * L + L + PRS_JW * L * 2) * 4
 
 

@@ -1,0 +1,236 @@
+// ultr_listloss.h — what the seven list-loss kernels share (ultr_loss.hip, ultr_prs.hip, ultr_pdgd.hip):
+//   * one LDS layout per kernel, a __host__ __device__ struct built from L: the kernel takes its pointers from the offsets, the
+//     launcher and ultr_loss_lds_bytes take `bytes` - the two sides cannot drift apart;
+//   * launch_list_loss, the one launcher behind the extern "C" entries;
+//   * the flat pieces of the pair-walk kernels (pairdebias_kernel, lambdarank_kernel, prs_loss_kernel): indices and slice
+//     bounds, staging, rank by counting, the fixed-order fold of the slice partials, the scatter, the workgroup tail store.
+// The kernels call the pieces in sequence and keep their own per-pair bodies.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/ultr_hip.h"
+#include "ultr_device.h"
+#include "ultr_plan.h"
+#include "ultr_prof.h"
+
+#define LPW ULTR_LOSS_LISTS_PER_WG  // lists per workgroup
+#ifndef LOSS_JW
+#define LOSS_JW 16  // wavefronts per list of the pair-walk kernels (round 6: 4 -> 16, one list per CU keeps four waves per SIMD busy:
+#endif              // pairdebias 7.6 -> 6.2 us, lambdarank 15.3 -> 12.7 us at config 4; tools/ab.sh "--config 4lambda" product jw8 jw16)
+
+#define PDGD_MAX_L 256    // one thread per position in the gradient phase
+#define PDGD_THREADS 256
+#define PDGD_WAVES (PDGD_THREADS / 64)
+__host__ __device__ static inline int pdgd_row(int l) { return l * (l + 3) / 2; }  // row l of the pair weights holds k = 0 .. l+1
+
+#define LOSS_LDS_DEFAULT (64 * 1024)  // dynamic LDS a kernel gets without asking
+#define LOSS_LDS_MAX (160 * 1024)     // ... and with hipFuncAttributeMaxDynamicSharedMemorySize: the CU's whole LDS
+
+// ------------------------------------------------------------------------------------------------
+// LDS layouts: the float offset of every array of a kernel's dynamic LDS, in allocation order, and the total in bytes
+// ------------------------------------------------------------------------------------------------
+struct LdsCarve {
+  int L;
+  int64_t at = 0;
+  __host__ __device__ explicit LdsCarve(int L_) : L(L_) {}
+  __host__ __device__ int take(int64_t n) {  // n floats, once per workgroup
+    const int o = (int)at;
+    at += n;
+    return o;
+  }
+  __host__ __device__ int per_list(int64_t n) { return take(LPW * n); }
+  __host__ __device__ int64_t end() const { return at * (int64_t)sizeof(float); }
+};
+
+struct SoftmaxLds : LdsCarve {  // list_size <= 4095
+  static constexpr int64_t limit = LOSS_LDS_DEFAULT;
+  int tail = per_list(ultr_tail_len(L));  // [LPW][tail]
+  int s = per_list(L);                    // [LPW][L] scores
+  int w = per_list(L);                    // [LPW][L] weights
+  int64_t bytes = end();
+  __host__ __device__ explicit SoftmaxLds(int L_) : LdsCarve(L_) {}
+};
+
+struct RegemLds : LdsCarve {  // list_size <= 8190
+  static constexpr int64_t limit = LOSS_LDS_DEFAULT;
+  int tail = per_list(ultr_tail_len(L));  // [LPW][tail]
+  int64_t bytes = end();
+  __host__ __device__ explicit RegemLds(int L_) : LdsCarve(L_) {}
+};
+
+struct DlaLds : LdsCarve {  // list_size <= 3276
+  static constexpr int64_t limit = LOSS_LDS_DEFAULT;
+  int tail = per_list(ultr_tail_len(L));  // [LPW][tail]
+  int s = per_list(L);                    // [LPW][L] scores
+  int y = per_list(L);                    // [LPW][L] clicks
+  int p = per_list(L);                    // [LPW][L] propensity logits ELU(W_l + b)  (batch independent)
+  int64_t bytes = end();
+  __host__ __device__ explicit DlaLds(int L_) : LdsCarve(L_) {}
+};
+
+struct PairDebiasLds : LdsCarve {  // list_size <= 585
+  static constexpr int64_t limit = LOSS_LDS_MAX;
+  int tail = per_list(ultr_tail_len(L));          // [LPW][tail]
+  int s = per_list(L);                            // [LPW][L] scores
+  int c = per_list(L);                            // [LPW][L] clicks
+  int rtp = take(L);                              // [L] 1 / t_plus
+  int rtm = take(L);                              // [L] 1 / t_minus
+  int acc = per_list((int64_t)LOSS_JW * L * 4);   // [LPW][LOSS_JW][L][4]: g, t_plus_loss, t_minus_loss, loss per (slice, position)
+  int64_t bytes = end();
+  __host__ __device__ explicit PairDebiasLds(int L_) : LdsCarve(L_) {}
+};
+
+struct SortedListLds : LdsCarve {  // what lambdarank_kernel and prs_loss_kernel both begin with
+  int tail = per_list(ultr_tail_len(L));  // [LPW][tail]
+  int s = per_list(L);                    // [LPW][L] raw scores, later d(loss)/d(sorted score)
+  int y = per_list(L);                    // [LPW][L] raw labels
+  int ps = per_list(L);                   // [LPW][L] scores sorted desc
+  int ls = per_list(L);                   // [LPW][L] labels in score order
+  int g = per_list(L);                    // [LPW][L] gains 2^l - 1 in score order
+  __host__ __device__ explicit SortedListLds(int L_) : LdsCarve(L_) {}
+};
+
+struct LambdaRankLds : SortedListLds {  // list_size <= 531
+  static constexpr int64_t limit = LOSS_LDS_MAX;
+  int tp = take(L);                               // [L] t_plus
+  int tm = take(L);                               // [L] t_minus
+  int rtp = take(L);                              // [L] 1 / t_plus
+  int rtm = take(L);                              // [L] 1 / t_minus
+  int d = take(L);                                // [L] discount 1 / log2(rank + 2)
+  int pos = per_list(L);                          // [LPW][L] int: sorted position of original index
+  int acc = per_list((int64_t)LOSS_JW * L * 4);   // [LPW][LOSS_JW][L][4]: g, t_plus_loss, t_minus_loss, loss
+  int64_t bytes = end();
+  __host__ __device__ explicit LambdaRankLds(int L_) : SortedListLds(L_) {}
+};
+
+struct PrsLds : SortedListLds {  // list_size <= 952
+  static constexpr int64_t limit = LOSS_LDS_MAX;
+  int ipw = per_list(L);                          // [LPW][L] ipw of the presentation position, in score order
+  int pw = per_list(L);                           // [LPW][L] pw = 1 / ipw (0 where ipw == 0), in score order
+  int d = take(L);                                // [L] discount 1 / log2(rank + 2)
+  int pos = per_list(L);                          // [LPW][L] int: sorted position of original index
+  int acc = per_list((int64_t)LOSS_JW * L * 2);   // [LPW][LOSS_JW][L][2]: g, loss
+  int64_t bytes = end();
+  __host__ __device__ explicit PrsLds(int L_) : SortedListLds(L_) {}
+};
+
+struct PdgdLds : LdsCarve {  // list_size <= PDGD_MAX_L (the entry refuses beyond: pdgd_row is 32-bit; 136 KiB there)
+  static constexpr int64_t limit = LOSS_LDS_MAX;
+  int s = take(L);             // [L] raw scores
+  int x = take(L);             // [L] exp of the raw scores (the pair loss)
+  int y = take(L);             // [L] labels
+  int e = take(L);             // [L] exp-scores
+  int D = take(L + 1);         // [L + 1] suffix sums of the exp-scores, D[L] = 0
+  int v = take(L);             // [L] int: 1 = a valid document
+  int red = take(PDGD_WAVES);  // [PDGD_WAVES]
+  int w = take(pdgd_row(L));   // [pdgd_row(L)] pair weights, row l = the clicked document
+  int64_t bytes = end();
+  __host__ __device__ explicit PdgdLds(int L_) : LdsCarve(L_) {}
+};
+
+// ------------------------------------------------------------------------------------------------
+// the one launcher: ultr_loss_parts(batch) workgroups of `threads`, under the ULTR_K_LOSS profiling scope
+// ------------------------------------------------------------------------------------------------
+template <class... KArgs, class... Args>
+static int launch_list_loss(void (*kernel)(KArgs...), int threads, int64_t lds_bytes, int64_t lds_limit, int32_t batch, void* stream,
+                            Args... args) {
+  if (lds_bytes > lds_limit) return ULTR_E_UNSUPPORTED;
+  if (lds_bytes > LOSS_LDS_DEFAULT && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+    return ULTR_E_UNSUPPORTED;
+  UltrProfScope prof(ULTR_K_LOSS, (hipStream_t)stream);
+  ULTR_LAUNCH(prof, kernel, dim3((unsigned)ultr_loss_parts(batch)), dim3(threads), (size_t)lds_bytes, (hipStream_t)stream,
+              static_cast<KArgs>(args)...);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// device pieces
+// ------------------------------------------------------------------------------------------------
+// sum the per-wave tails of a workgroup in fixed order and store the workgroup's partial
+__device__ __forceinline__ void store_wg_tail(const float* sm_tail /*[LPW][tail]*/, int tail, float* part) {
+  __syncthreads();
+  for (int t = threadIdx.x; t < tail; t += blockDim.x) {
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < LPW; ++w) s += sm_tail[w * tail + t];
+    part[t] = s;
+  }
+}
+
+// where a wavefront of a pair-walk kernel stands: LOSS_JW wavefronts share a list, each walks a slice of the partner positions
+struct ListWave {
+  int lane, wave;
+  int lw, jw;  // list of the workgroup, slice of the list
+  int b;       // list of the batch
+  int lo, hi;  // the slice's partner positions [lo, hi): empty for the last slices of a short list
+};
+__device__ __forceinline__ ListWave list_wave(int L) {
+  ListWave w;
+  w.lane = threadIdx.x & 63, w.wave = threadIdx.x >> 6;
+  w.lw = w.wave / LOSS_JW, w.jw = w.wave - w.lw * LOSS_JW;
+  w.b = blockIdx.x * LPW + w.lw;
+  const int len = (L + LOSS_JW - 1) / LOSS_JW;
+  w.lo = w.jw * len, w.hi = (w.lo + len < L) ? w.lo + len : L;
+  return w;
+}
+
+// wave 0 of a list zeroes the list's tail and stages its raw scores [B, L] and labels [L, B]
+__device__ __forceinline__ void stage_list(const ListWave& w, const float* __restrict__ scores, const float* __restrict__ labels, int B,
+                                           int L, int tail, float* mt, float* ms, float* my) {
+  if (w.jw == 0) {
+    for (int t = w.lane; t < tail; t += 64) mt[t] = 0.f;
+    if (w.b < B)
+      for (int l = w.lane; l < L; l += 64) {
+        ms[l] = scores[(int64_t)w.b * L + l];
+        my[l] = labels[(int64_t)l * B + w.b];
+      }
+  }
+}
+
+// Rank by counting, stable (ties broken by original index): position i's rank rs among the scores and ry among the labels, L
+// compares each from LDS; with its gain 2^y - 1 and its term of the ideal DCG
+struct Ranked {
+  float s, y;  // the position's own score and label
+  int rs, ry;
+  float gain, idcg;
+};
+__device__ __forceinline__ Ranked rank_by_counting(const float* ms, const float* my, int L, int i) {
+  const float si = ms[i], yi = my[i];
+  int rs = 0, ry = 0;
+  for (int j = 0; j < L; ++j) {
+    const float sj = ms[j], yj = my[j];
+    rs += (sj > si || (sj == si && j < i)) ? 1 : 0;
+    ry += (yj > yi || (yj == yi && j < i)) ? 1 : 0;
+  }
+  // dcg(): sum (2^l - 1) / ln(rank + 1), rank 1-based -> ln(ry + 2)   (lambda_rank.py:262-266, prs_rank.py:207-226)
+  return Ranked{si, yi, rs, ry, exp2f(yi) - 1.0f, (exp2f(yi) - 1.0f) / logf((float)ry + 2.0f)};
+}
+
+// the NV partial sums of (list lw, slice jw, position i) in sm_acc [LPW][LOSS_JW][L][NV]
+template <int NV>
+__device__ __forceinline__ float* slice_acc(float* sm_acc, int lw, int jw, int L, int i) {
+  return sm_acc + ((size_t)(lw * LOSS_JW + jw) * L + i) * NV;
+}
+
+// v[k] = position i's k-th partial summed over the slices in the order 0, 1, ..., LOSS_JW - 1
+template <int NV>
+__device__ __forceinline__ void fold_slices(float* sm_acc, int lw, int L, int i, float (&v)[NV]) {
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    float t = slice_acc<NV>(sm_acc, lw, 0, L, i)[k];
+#pragma unroll
+    for (int w = 1; w < LOSS_JW; ++w) t += slice_acc<NV>(sm_acc, lw, w, L, i)[k];
+    v[k] = t;
+  }
+}
+
+// gradients by sorted position (ms[], written by the lane of the sorted position) to presentation order: read by the lane owning
+// the original index
+__device__ __forceinline__ void scatter_sorted(const ListWave& w, int B, int L, const float* ms, const int* pos,
+                                               float* __restrict__ dscores) {
+  __syncthreads();
+  if (w.b < B && w.jw == 0)
+    for (int i = w.lane; i < L; i += 64) dscores[(int64_t)w.b * L + i] = ms[pos[i]];
+}

@@ -10,12 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/ultr_hip.h"
-#include "ultr_device.h"
-#include "ultr_plan.h"
-#include "ultr_prof.h"
-
-#define LPW ULTR_LOSS_LISTS_PER_WG  // lists (= waves) per workgroup
+#include "ultr_listloss.h"
 
 extern "C" int64_t ultr_loss_part_count(int64_t batch) { return batch > 0 ? ultr_loss_parts(batch) : 0; }
 
@@ -29,14 +24,23 @@ extern "C" int64_t ultr_loss_workspace_bytes(int64_t batch, int32_t list_size) {
   return (parts * ultr_tail_len(list_size) + 4) * (int64_t)sizeof(float);
 }
 
-// sum the per-wave tails of a workgroup in fixed order and store the workgroup's partial
-__device__ __forceinline__ void store_wg_tail(const float* sm_tail /*[LPW][tail]*/, int tail, float* part) {
-  __syncthreads();
-  for (int t = threadIdx.x; t < tail; t += blockDim.x) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < LPW; ++w) s += sm_tail[w * tail + t];
-    part[t] = s;
+template <class Lds>
+static int64_t lds_bytes_or_refusal(int32_t list_size) {
+  const Lds lay(list_size);
+  return lay.bytes > Lds::limit ? ULTR_E_UNSUPPORTED : lay.bytes;
+}
+
+extern "C" int64_t ultr_loss_lds_bytes(int32_t algo, int32_t list_size) {
+  if (list_size <= 0) return ULTR_E_BADARG;
+  switch (algo) {
+    case ULTR_ALGO_SOFTMAX: return lds_bytes_or_refusal<SoftmaxLds>(list_size);
+    case ULTR_ALGO_DLA: return lds_bytes_or_refusal<DlaLds>(list_size);
+    case ULTR_ALGO_PAIRDEBIAS: return lds_bytes_or_refusal<PairDebiasLds>(list_size);
+    case ULTR_ALGO_LAMBDARANK: return lds_bytes_or_refusal<LambdaRankLds>(list_size);
+    case ULTR_ALGO_REGEM: return lds_bytes_or_refusal<RegemLds>(list_size);
+    case ULTR_ALGO_PRS: return lds_bytes_or_refusal<PrsLds>(list_size);
+    case ULTR_ALGO_PDGD: return list_size > PDGD_MAX_L ? ULTR_E_UNSUPPORTED : lds_bytes_or_refusal<PdgdLds>(list_size);
+    default: return ULTR_E_BADARG;
   }
 }
 
@@ -52,13 +56,12 @@ __global__ __launch_bounds__(LPW * 64) void softmax_ce_kernel(const float* __res
                                                              float* __restrict__ dscores, float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tail = (int)ultr_tail_len(L);
-  float* sm_tail = smem;                       // [LPW][tail]
-  float* sm_s = sm_tail + LPW * tail;          // [LPW][L]
-  float* sm_w = sm_s + LPW * L;                // [LPW][L]
+  const SoftmaxLds lay(L);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x * LPW + wave;
-  float* ms = sm_s + wave * L;
-  float* mw = sm_w + wave * L;
+  float* sm_tail = smem + lay.tail;
+  float* ms = smem + lay.s + wave * L;
+  float* mw = smem + lay.w + wave * L;
   float* mt = sm_tail + wave * tail;
   for (int t = lane; t < tail; t += 64) mt[t] = 0.f;
   if (b < B) {
@@ -104,15 +107,9 @@ extern "C" int ultr_softmax_ce(const float* scores, const float* labels, const f
                                void* stream) {
   if (!scores || !labels || !dscores || !loss_ws || batch <= 0 || list_size <= 0 || (ipw_table && n_ipw <= 0))
     return ULTR_E_BADARG;
-  const int tail = (int)ultr_tail_len(list_size);
-  const size_t lds = (size_t)LPW * (tail + 2 * list_size) * sizeof(float);
-  if (lds > 64 * 1024) return ULTR_E_UNSUPPORTED;
-  UltrProfScope prof(ULTR_K_LOSS, (hipStream_t)stream);
-  ULTR_LAUNCH(prof, softmax_ce_kernel, dim3((unsigned)ultr_loss_parts(batch)), dim3(LPW * 64), lds, (hipStream_t)stream,
-                     scores, labels, pw, ipw_table, (int)n_ipw, (int)batch, (int)list_size, dscores, (float*)loss_ws);
-  return (int)hipGetLastError();
+  return launch_list_loss(softmax_ce_kernel, LPW * 64, SoftmaxLds(list_size).bytes, SoftmaxLds::limit, batch, stream, scores, labels,
+                          pw, ipw_table, n_ipw, batch, list_size, dscores, (float*)loss_ws);
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // next row 8f.3: RegressionEM                                         regression_EM.py:108-193
@@ -128,9 +125,10 @@ __global__ __launch_bounds__(LPW * 64) void regem_kernel(const float* __restrict
                                                         float* __restrict__ pseudo, float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tail = (int)ultr_tail_len(L);
-  float* sm_tail = smem;  // [LPW][tail]
+  const RegemLds lay(L);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x * LPW + wave;
+  float* sm_tail = smem + lay.tail;
   float* mt = sm_tail + wave * tail;
   for (int t = lane; t < tail; t += 64) mt[t] = 0.f;
   if (b < B) {
@@ -174,14 +172,8 @@ extern "C" int ultr_regem_loss(const float* scores, const float* labels, const f
                                uint64_t seed, uint64_t step, int32_t batch, int32_t list_size, float* dscores,
                                float* pseudo_labels_out, void* loss_ws, void* stream) {
   if (!scores || !labels || !propensity || !dscores || !loss_ws || batch <= 0 || list_size <= 0) return ULTR_E_BADARG;
-  const int tail = (int)ultr_tail_len(list_size);
-  const size_t lds = (size_t)LPW * tail * sizeof(float);
-  if (lds > 64 * 1024) return ULTR_E_UNSUPPORTED;
-  UltrProfScope prof(ULTR_K_LOSS, (hipStream_t)stream);
-  ULTR_LAUNCH(prof, regem_kernel, dim3((unsigned)ultr_loss_parts(batch)), dim3(LPW * 64), lds, (hipStream_t)stream, scores,
-              labels, propensity, uniforms, seed, step, (int)batch, (int)list_size, dscores, pseudo_labels_out,
-              (float*)loss_ws);
-  return (int)hipGetLastError();
+  return launch_list_loss(regem_kernel, LPW * 64, RegemLds(list_size).bytes, RegemLds::limit, batch, stream, scores, labels, propensity,
+                          uniforms, seed, step, batch, list_size, dscores, pseudo_labels_out, (float*)loss_ws);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -193,15 +185,13 @@ __global__ __launch_bounds__(LPW * 64) void dla_loss_kernel(const float* __restr
                                                            float* __restrict__ dscores, float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tail = (int)ultr_tail_len(L);
-  float* sm_tail = smem;               // [LPW][tail]
-  float* sm_s = sm_tail + LPW * tail;  // [LPW][L] scores
-  float* sm_y = sm_s + LPW * L;        // [LPW][L] clicks
-  float* sm_p = sm_y + LPW * L;        // [LPW][L] propensity logits ELU(W_l + b)  (batch independent)
+  const DlaLds lay(L);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x * LPW + wave;
-  float* ms = sm_s + wave * L;
-  float* my = sm_y + wave * L;
-  float* mp = sm_p + wave * L;
+  float* sm_tail = smem + lay.tail;
+  float* ms = smem + lay.s + wave * L;
+  float* my = smem + lay.y + wave * L;
+  float* mp = smem + lay.p + wave * L;
   float* mt = sm_tail + wave * tail;
   for (int t = lane; t < tail; t += 64) mt[t] = 0.f;
   if (b < B) {
@@ -267,14 +257,8 @@ __global__ __launch_bounds__(LPW * 64) void dla_loss_kernel(const float* __restr
 extern "C" int ultr_dla_loss(const float* scores, const float* labels, const float* prop_params, int32_t logits_to_prob,
                              int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream) {
   if (!scores || !labels || !prop_params || !dscores || !loss_ws || batch <= 0 || list_size <= 0) return ULTR_E_BADARG;
-  const int tail = (int)ultr_tail_len(list_size);
-  const size_t lds = (size_t)LPW * (tail + 3 * list_size) * sizeof(float);
-  if (lds > 64 * 1024) return ULTR_E_UNSUPPORTED;
-  UltrProfScope prof(ULTR_K_LOSS, (hipStream_t)stream);
-  ULTR_LAUNCH(prof, dla_loss_kernel, dim3((unsigned)ultr_loss_parts(batch)), dim3(LPW * 64), lds, (hipStream_t)stream,
-                     scores, labels, prop_params, (int)logits_to_prob, (int)batch, (int)list_size, dscores,
-                     (float*)loss_ws);
-  return (int)hipGetLastError();
+  return launch_list_loss(dla_loss_kernel, LPW * 64, DlaLds(list_size).bytes, DlaLds::limit, batch, stream, scores, labels, prop_params,
+                          logits_to_prob, batch, list_size, dscores, (float*)loss_ws);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -284,12 +268,9 @@ extern "C" int ultr_dla_loss(const float* scores, const float* labels, const flo
 // "wavefront pair-diff kernel").  Of the ordered pairs (i,j) and (j,i) at most one is valid (c_i > c_j or c_j > c_i): ONE
 // branch-free evaluation per unordered pair - e = exp(-|x|) gives both softplus(x) = max(x,0) + log1p(e) and sigmoid(x) -
 // with the reciprocals of t_plus / t_minus staged once.  A list is small (L^2 pairs) and there are only `batch` of them, so
-// the kernel is one wavefront's instruction stream long: PD_JW wavefronts share a list (each a slice of the j range; their
+// the kernel is one wavefront's instruction stream long: LOSS_JW wavefronts share a list (each a slice of the j range; their
 // four partial sums per position are combined in fixed order through LDS).
-#ifndef PD_JW
-#define PD_JW 16  // wavefronts per list (round 6: 4 -> 16, one list per CU keeps four waves per SIMD busy: pairdebias 7.6 -> 6.2 us,
-#endif           // lambdarank 15.3 -> 12.7 us at config 4; tools/ab.sh "--config 4lambda" product jw8 jw16)
-__global__ __launch_bounds__(LPW * PD_JW * 64) void pairdebias_kernel(const float* __restrict__ scores,
+__global__ __launch_bounds__(LPW * LOSS_JW * 64) void pairdebias_kernel(const float* __restrict__ scores,
                                                                      const float* __restrict__ labels,
                                                                      const float* __restrict__ t_plus,
                                                                      const float* __restrict__ t_minus, int B, int L,
@@ -297,32 +278,23 @@ __global__ __launch_bounds__(LPW * PD_JW * 64) void pairdebias_kernel(const floa
                                                                      float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tail = (int)ultr_tail_len(L);
-  float* sm_tail = smem;               // [LPW][tail]
-  float* sm_s = sm_tail + LPW * tail;  // [LPW][L]
-  float* sm_c = sm_s + LPW * L;        // [LPW][L]
-  float* sm_rtp = sm_c + LPW * L;      // [L] 1 / t_plus
-  float* sm_rtm = sm_rtp + L;          // [L] 1 / t_minus
-  float* sm_acc = sm_rtm + L;          // [LPW][PD_JW][L][4]: g, t_plus_loss, t_minus_loss, loss per (slice, position)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lw = wave / PD_JW, jw = wave - lw * PD_JW;   // list of the workgroup, slice of the j range
-  const int b = blockIdx.x * LPW + lw;
-  float* ms = sm_s + lw * L;
-  float* mc = sm_c + lw * L;
+  const PairDebiasLds lay(L);
+  const ListWave at = list_wave(L);
+  const int lane = at.lane, lw = at.lw, jw = at.jw, b = at.b;
+  float* sm_tail = smem + lay.tail;
+  float* sm_rtp = smem + lay.rtp;
+  float* sm_rtm = smem + lay.rtm;
+  float* sm_acc = smem + lay.acc;
+  float* ms = smem + lay.s + lw * L;
+  float* mc = smem + lay.c + lw * L;
   float* mt = sm_tail + lw * tail;
   for (int t = threadIdx.x; t < L; t += blockDim.x) {
     sm_rtp[t] = 1.0f / t_plus[t];
     sm_rtm[t] = 1.0f / t_minus[t];
   }
-  if (jw == 0) {
-    for (int t = lane; t < tail; t += 64) mt[t] = 0.f;
-    if (b < B)
-      for (int l = lane; l < L; l += 64) {
-        ms[l] = scores[(int64_t)b * L + l];
-        mc[l] = labels[(int64_t)l * B + b];
-      }
-  }
+  stage_list(at, scores, labels, B, L, tail, mt, ms, mc);
   __syncthreads();
-  const int jlen = (L + PD_JW - 1) / PD_JW, j0 = jw * jlen, j1 = (j0 + jlen < L) ? j0 + jlen : L;
+  const int j0 = at.lo, j1 = at.hi;
   if (b < B) {
     for (int i = lane; i < L; i += 64) {
       const float si = ms[i], ci = mc[i], rtpi = sm_rtp[i], rtmi = sm_rtm[i];
@@ -347,7 +319,7 @@ __global__ __launch_bounds__(LPW * PD_JW * 64) void pairdebias_kernel(const floa
         li += fwd ? plr * rtpi : 0.f;
         g += fwd ? -(gw * rj * rtpi) : gw * rj * rtmi;
       }
-      float* a = sm_acc + ((size_t)(lw * PD_JW + jw) * L + i) * 4;
+      float* a = slice_acc<4>(sm_acc, lw, jw, L, i);
       a[0] = g; a[1] = tpl; a[2] = tml; a[3] = li;
     }
   }
@@ -356,13 +328,7 @@ __global__ __launch_bounds__(LPW * PD_JW * 64) void pairdebias_kernel(const floa
     float lsum = 0.f;
     for (int i = lane; i < L; i += 64) {
       float v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float t = sm_acc[((size_t)(lw * PD_JW + 0) * L + i) * 4 + k];
-#pragma unroll
-        for (int w = 1; w < PD_JW; ++w) t += sm_acc[((size_t)(lw * PD_JW + w) * L + i) * 4 + k];
-        v[k] = t;
-      }
+      fold_slices<4>(sm_acc, lw, L, i, v);
       dscores[(int64_t)b * L + i] = v[0];
       mt[ULTR_TAIL_FIXED + i] = v[1];
       mt[ULTR_TAIL_FIXED + L + i] = v[2];
@@ -382,17 +348,8 @@ extern "C" int ultr_pairdebias_loss(const float* scores, const float* labels, co
                                     void* stream) {
   if (!scores || !labels || !t_plus || !t_minus || !dscores || !loss_ws || batch <= 0 || list_size <= 0 || batch_total <= 0)
     return ULTR_E_BADARG;
-  const int tail = (int)ultr_tail_len(list_size);
-  const size_t lds = ((size_t)LPW * (tail + 2 * list_size) + 2 * list_size + (size_t)LPW * PD_JW * list_size * 4) * sizeof(float);
-  if (lds > 160 * 1024) return ULTR_E_UNSUPPORTED;
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(pairdebias_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return ULTR_E_UNSUPPORTED;
-  UltrProfScope prof(ULTR_K_LOSS, (hipStream_t)stream);
-  ULTR_LAUNCH(prof, pairdebias_kernel, dim3((unsigned)ultr_loss_parts(batch)), dim3(LPW * PD_JW * 64), lds, (hipStream_t)stream,
-                     scores, labels, t_plus, t_minus, (int)batch, (int)list_size, (float)batch_total, dscores,
-                     (float*)loss_ws);
-  return (int)hipGetLastError();
+  return launch_list_loss(pairdebias_kernel, LPW * LOSS_JW * 64, PairDebiasLds(list_size).bytes, PairDebiasLds::limit, batch, stream,
+                          scores, labels, t_plus, t_minus, batch, list_size, batch_total, dscores, (float*)loss_ws);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -402,12 +359,12 @@ extern "C" int ultr_pairdebias_loss(const float* scores, const float* labels, co
 // LDS; the same trick orders the labels for the ideal DCG.  Then the pair walk of PairDebias on the SORTED
 // list, with delta-NDCG weights and the reference's BCE-with-logits-on-a-probability quirk.
 
-// PD_JW wavefronts share a list: wave 0 of the list sorts (rank by counting), then every wave walks a slice of the
+// LOSS_JW wavefronts share a list: wave 0 of the list sorts (rank by counting), then every wave walks a slice of the
 // partner positions c for all positions r; the four partial sums per position are combined in fixed order through
 // LDS.  Per pair ONE exp gives both probabilities without cancellation - with ez = exp(-|z|), z = sigma (s_r - s_c):
 // sigmoid(|z|) = 1 / (1 + ez), sigmoid(-|z|) = ez / (1 + ez) - and one more exp per probability gives both its
 // BCE-with-logits value and its derivative (sigmoid(x) - target).  Discounts and reciprocals are staged per position.
-__global__ __launch_bounds__(LPW * PD_JW * 64) void lambdarank_kernel(const float* __restrict__ scores,
+__global__ __launch_bounds__(LPW * LOSS_JW * 64) void lambdarank_kernel(const float* __restrict__ scores,
                                                                      const float* __restrict__ labels,
                                                                      const float* __restrict__ t_plus,
                                                                      const float* __restrict__ t_minus, float sigma, int B,
@@ -415,28 +372,22 @@ __global__ __launch_bounds__(LPW * PD_JW * 64) void lambdarank_kernel(const floa
                                                                      float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tail = (int)ultr_tail_len(L);
-  float* sm_tail = smem;                // [LPW][tail]
-  float* sm_s = sm_tail + LPW * tail;   // [LPW][L] raw scores, later d(loss)/d(sorted score)
-  float* sm_y = sm_s + LPW * L;         // [LPW][L] raw labels
-  float* sm_ps = sm_y + LPW * L;        // [LPW][L] scores sorted desc
-  float* sm_ls = sm_ps + LPW * L;       // [LPW][L] labels in score order
-  float* sm_g = sm_ls + LPW * L;        // [LPW][L] gains 2^l - 1 in score order
-  float* sm_tp = sm_g + LPW * L;        // [L] t_plus
-  float* sm_tm = sm_tp + L;             // [L] t_minus
-  float* sm_rtp = sm_tm + L;            // [L] 1 / t_plus
-  float* sm_rtm = sm_rtp + L;           // [L] 1 / t_minus
-  float* sm_d = sm_rtm + L;             // [L] discount 1 / log2(rank + 2)
-  int* sm_pos = reinterpret_cast<int*>(sm_d + L);             // [LPW][L] sorted position of original index
-  float* sm_acc = reinterpret_cast<float*>(sm_pos + LPW * L); // [LPW][PD_JW][L][4]: g, t_plus_loss, t_minus_loss, loss
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lw = wave / PD_JW, jw = wave - lw * PD_JW;
-  const int b = blockIdx.x * LPW + lw;
-  float* ms = sm_s + lw * L;
-  float* my = sm_y + lw * L;
-  float* ps = sm_ps + lw * L;
-  float* ls = sm_ls + lw * L;
-  float* gs = sm_g + lw * L;
-  int* pos = sm_pos + lw * L;
+  const LambdaRankLds lay(L);
+  const ListWave at = list_wave(L);
+  const int lane = at.lane, lw = at.lw, jw = at.jw, b = at.b;
+  float* sm_tail = smem + lay.tail;
+  float* sm_tp = smem + lay.tp;
+  float* sm_tm = smem + lay.tm;
+  float* sm_rtp = smem + lay.rtp;
+  float* sm_rtm = smem + lay.rtm;
+  float* sm_d = smem + lay.d;
+  float* sm_acc = smem + lay.acc;
+  float* ms = smem + lay.s + lw * L;
+  float* my = smem + lay.y + lw * L;
+  float* ps = smem + lay.ps + lw * L;
+  float* ls = smem + lay.ls + lw * L;
+  float* gs = smem + lay.g + lw * L;
+  int* pos = reinterpret_cast<int*>(smem + lay.pos) + lw * L;
   float* mt = sm_tail + lw * tail;
   for (int t = threadIdx.x; t < L; t += blockDim.x) {
     const float tp = t_plus[t], tm = t_minus[t];
@@ -446,36 +397,22 @@ __global__ __launch_bounds__(LPW * PD_JW * 64) void lambdarank_kernel(const floa
     sm_rtm[t] = 1.0f / tm;
     sm_d[t] = 1.0f / log2f((float)t + 2.0f);
   }
-  if (jw == 0) {
-    for (int t = lane; t < tail; t += 64) mt[t] = 0.f;
-    if (b < B)
-      for (int l = lane; l < L; l += 64) {
-        ms[l] = scores[(int64_t)b * L + l];
-        my[l] = labels[(int64_t)l * B + b];
-      }
-  }
+  stage_list(at, scores, labels, B, L, tail, mt, ms, my);
   __syncthreads();
   float idcg = 0.f;
   if (b < B && jw == 0) {
     for (int i = lane; i < L; i += 64) {
-      const float si = ms[i], yi = my[i];
-      int rs = 0, ry = 0;
-      for (int j = 0; j < L; ++j) {
-        const float sj = ms[j], yj = my[j];
-        rs += (sj > si || (sj == si && j < i)) ? 1 : 0;
-        ry += (yj > yi || (yj == yi && j < i)) ? 1 : 0;
-      }
-      pos[i] = rs;
-      ps[rs] = si;
-      ls[rs] = yi;
-      gs[rs] = exp2f(yi) - 1.0f;
-      // dcg(): sum (2^l - 1) / ln(rank + 1), rank 1-based -> ln(ry + 2)   (lambda_rank.py:262-266)
-      idcg += (exp2f(yi) - 1.0f) / logf((float)ry + 2.0f);
+      const Ranked k = rank_by_counting(ms, my, L, i);
+      pos[i] = k.rs;
+      ps[k.rs] = k.s;
+      ls[k.rs] = k.y;
+      gs[k.rs] = k.gain;
+      idcg += k.idcg;
     }
     idcg = wave_sum(idcg);
   }
   __syncthreads();  // the sorted arrays are visible to the list's other waves
-  const int clen = (L + PD_JW - 1) / PD_JW, c0 = jw * clen, c1 = (c0 + clen < L) ? c0 + clen : L;
+  const int c0 = at.lo, c1 = at.hi;
   if (b < B) {
     for (int r = lane; r < L; r += 64) {
       const float sr = ps[r], lr_ = ls[r], gr = gs[r], tpr = sm_tp[r], tmr = sm_tm[r], rtpr = sm_rtp[r], rtmr = sm_rtm[r];
@@ -506,7 +443,7 @@ __global__ __launch_bounds__(LPW * PD_JW * 64) void lambdarank_kernel(const floa
         g += ok_rc ? d_rc * rtpr * rtmc : 0.f;
         g -= ok_cr ? d_cr * rtpc * rtmr : 0.f;
       }
-      float* a = sm_acc + ((size_t)(lw * PD_JW + jw) * L + r) * 4;
+      float* a = slice_acc<4>(sm_acc, lw, jw, L, r);
       a[0] = g; a[1] = tpl; a[2] = tml; a[3] = li;
     }
   }
@@ -515,13 +452,7 @@ __global__ __launch_bounds__(LPW * PD_JW * 64) void lambdarank_kernel(const floa
     float lsum = 0.f;
     for (int r = lane; r < L; r += 64) {
       float v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float t = sm_acc[((size_t)(lw * PD_JW + 0) * L + r) * 4 + k];
-#pragma unroll
-        for (int w = 1; w < PD_JW; ++w) t += sm_acc[((size_t)(lw * PD_JW + w) * L + r) * 4 + k];
-        v[k] = t;
-      }
+      fold_slices<4>(sm_acc, lw, L, r, v);
       mt[ULTR_TAIL_FIXED + r] = v[1];
       mt[ULTR_TAIL_FIXED + L + r] = v[2];
       ms[r] = v[0];  // raw scores are dead after the sort: reuse as d(loss)/d(sorted score r)
@@ -533,10 +464,7 @@ __global__ __launch_bounds__(LPW * PD_JW * 64) void lambdarank_kernel(const floa
       mt[1] = idcg;
     }
   }
-  // ms[] (now gradients by sorted position) written by lane r, read by the lane owning the original index
-  __syncthreads();
-  if (b < B && jw == 0)
-    for (int i = lane; i < L; i += 64) dscores[(int64_t)b * L + i] = ms[pos[i]];
+  scatter_sorted(at, B, L, ms, pos, dscores);
   store_wg_tail(sm_tail, tail, part + (int64_t)blockIdx.x * tail);
 }
 
@@ -545,14 +473,6 @@ extern "C" int ultr_lambdarank_loss(const float* scores, const float* labels, co
                                     void* stream) {
   if (!scores || !labels || !t_plus || !t_minus || !dscores || !loss_ws || batch <= 0 || list_size <= 0)
     return ULTR_E_BADARG;
-  const int tail = (int)ultr_tail_len(list_size);
-  const size_t lds = ((size_t)LPW * (tail + 6 * list_size) + 5 * list_size + (size_t)LPW * PD_JW * list_size * 4) * sizeof(float);
-  if (lds > 160 * 1024) return ULTR_E_UNSUPPORTED;
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(lambdarank_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return ULTR_E_UNSUPPORTED;
-  UltrProfScope prof(ULTR_K_LOSS, (hipStream_t)stream);
-  ULTR_LAUNCH(prof, lambdarank_kernel, dim3((unsigned)ultr_loss_parts(batch)), dim3(LPW * PD_JW * 64), lds, (hipStream_t)stream,
-                     scores, labels, t_plus, t_minus, sigma, (int)batch, (int)list_size, dscores, (float*)loss_ws);
-  return (int)hipGetLastError();
+  return launch_list_loss(lambdarank_kernel, LPW * LOSS_JW * 64, LambdaRankLds(list_size).bytes, LambdaRankLds::limit, batch, stream,
+                          scores, labels, t_plus, t_minus, sigma, batch, list_size, dscores, (float*)loss_ws);
 }

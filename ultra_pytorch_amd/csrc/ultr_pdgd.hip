@@ -24,14 +24,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/ultr_hip.h"
-#include "ultr_device.h"
-#include "ultr_plan.h"
-#include "ultr_prof.h"
+#include "ultr_listloss.h"
 
-#define PDGD_MAX_L 256    // one thread per position in the gradient phase
-#define PDGD_THREADS 256
-#define PDGD_WAVES (PDGD_THREADS / 64)
 static_assert(ULTR_LOSS_LISTS_PER_WG == 1, "pdgd_loss_kernel writes one loss partial per list");
 
 // delta of the flipped list, positions a < b swapped.  Only the suffix sums in (a, b] differ; the flipped ones are summed from
@@ -51,22 +45,21 @@ __device__ __forceinline__ float pdgd_delta(const float* __restrict__ e, const f
   return delta;
 }
 
-__host__ __device__ static inline int pdgd_row(int l) { return l * (l + 3) / 2; }  // row l holds k = 0 .. l+1
-
 __global__ __launch_bounds__(PDGD_THREADS) void pdgd_loss_kernel(const float* __restrict__ scores,
                                                                  const float* __restrict__ labels,
                                                                  const int32_t* __restrict__ docids, int64_t n_docs,
                                                                  float tau, int cutoff, int B, int L,
                                                                  float* __restrict__ dscores, float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sm_s = smem;                 // [L] raw scores
-  float* sm_x = sm_s + L;             // [L] exp of the raw scores (the pair loss)
-  float* sm_y = sm_x + L;             // [L] labels
-  float* sm_e = sm_y + L;             // [L] exp-scores
-  float* sm_D = sm_e + L;             // [L + 1] suffix sums of the exp-scores, D[L] = 0
-  int* sm_v = reinterpret_cast<int*>(sm_D + L + 1);  // [L] 1 = a valid document
-  float* sm_red = reinterpret_cast<float*>(sm_v + L);  // [PDGD_WAVES]
-  float* sm_w = sm_red + PDGD_WAVES;  // [pdgd_row(L)] pair weights, row l = the clicked document
+  const PdgdLds lay(L);
+  float* sm_s = smem + lay.s;
+  float* sm_x = smem + lay.x;
+  float* sm_y = smem + lay.y;
+  float* sm_e = smem + lay.e;
+  float* sm_D = smem + lay.D;
+  int* sm_v = reinterpret_cast<int*>(smem + lay.v);
+  float* sm_red = smem + lay.red;
+  float* sm_w = smem + lay.w;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int b = blockIdx.x;
   const int tail = (int)ultr_tail_len(L);
@@ -147,8 +140,6 @@ __global__ __launch_bounds__(PDGD_THREADS) void pdgd_loss_kernel(const float* __
   }
 }
 
-static size_t pdgd_lds_bytes(int32_t L) { return ((size_t)6 * L + 1 + PDGD_WAVES + (size_t)pdgd_row(L)) * sizeof(float); }
-
 extern "C" int ultr_pdgd_loss(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, float tau,
                               int32_t cutoff, int32_t batch, int32_t list_size, float* dscores, void* loss_ws,
                               void* stream) {
@@ -156,12 +147,6 @@ extern "C" int ultr_pdgd_loss(const float* scores, const float* labels, const in
     return ULTR_E_BADARG;
   if (list_size > PDGD_MAX_L) return ULTR_E_UNSUPPORTED;
   const int c = cutoff < list_size ? cutoff : list_size;
-  const size_t lds = pdgd_lds_bytes(list_size);  // 136 KiB at L = 256
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(pdgd_loss_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return ULTR_E_UNSUPPORTED;
-  UltrProfScope prof(ULTR_K_LOSS, (hipStream_t)stream);
-  ULTR_LAUNCH(prof, pdgd_loss_kernel, dim3((unsigned)ultr_loss_parts(batch)), dim3(PDGD_THREADS), lds, (hipStream_t)stream,
-              scores, labels, docids, n_docs, tau, c, (int)batch, (int)list_size, dscores, (float*)loss_ws);
-  return (int)hipGetLastError();
+  return launch_list_loss(pdgd_loss_kernel, PDGD_THREADS, PdgdLds(list_size).bytes, PdgdLds::limit, batch, stream, scores, labels, docids,
+                          n_docs, tau, c, batch, list_size, dscores, (float*)loss_ws);
 }

@@ -249,6 +249,14 @@ def loss_part_count(B):
     return int(_lib.load().ultr_loss_part_count(int(B)))
 
 
+def loss_lds_bytes(algo, L):
+    """Dynamic LDS in bytes the stand-alone loss kernel of `algo` (a _lib.ALGO_* id) requests at list size L (ultr_loss_lds_bytes).
+    Host-only: needs no GPU and launches nothing.  A list size the entry would refuse raises UltrHipError, as the call itself would."""
+    n = int(_lib.load().ultr_loss_lds_bytes(int(algo), int(L)))
+    check(min(n, 0), "ultr_loss_lds_bytes")
+    return n
+
+
 H3_KNOBS = ("ULTR_FB_H3", "ULTR_FWD_H3", "ULTR_BWD_H3")
 SR_H3_KNOBS = ("ULTR_SR_H3",)
 
