@@ -405,6 +405,39 @@ int ultr_setrank_backward_dropout(const ultr_setrank_desc* c, const float* param
                                   const float* dscores, const void* loss_ws, int32_t n_loss_parts, void* workspace, float* grads,
                                   const ultr_setrank_dropout* dropout, void* stream);
 
+/* ---- the DLCM ranking model (additive within ABI 8) --------------------------------------------
+ * Deep Listwise Context Model (Ai, Bi, Guo, Croft, SIGIR 2018); the reference names it (ultra.ranking_model.DLCM) and ships no code.
+ * Per list: xh_l = LayerNorm_F(x_l) (eps 1e-5, PAD = the zero row -> beta); a one-layer GRU (torch.nn.GRU's law and layout, gates
+ * r, z, n) reads the list from the LAST position to the FIRST from h = 0, o_l = the state after position l, s = o_0;
+ * M = tanh(W_phi s + b_phi) as [num_heads, H], m = sum_j v_j M_j, score_l = o_l . m.
+ * params: one flat vector, offsets by ultr_dlcm_param_offsets: layer_norm.weight / .bias [F], gru.weight_ih_l0 [3H, F],
+ * gru.weight_hh_l0 [3H, H], gru.bias_ih_l0 / .bias_hh_l0 [3H], att_linear.weight [num_heads H, H], att_linear.bias [num_heads H],
+ * att_v.weight [1, num_heads].
+ * feature_size and hidden_size are multiples of 4 (16-byte rows); every other model is ULTR_E_UNSUPPORTED from the size queries and
+ * from the calls, before anything is launched or written.  list_size >= 1 with no bound of the model's own; the recurrent kernels keep
+ * 16 lists in LDS: hidden_size <= 848 trains (above 624 the carried state gradient sits in `workspace`), the forward runs up to 1264.
+ * forward: docids [L, B] position-major (PAD = n_docs), scores [B, L].  saved != NULL (ultr_dlcm_saved_bytes): the training form, `work`
+ * is not read; saved == NULL: the scoring form, the same launches with the same bits writing only what one launch hands to the next
+ * into `work` (ultr_dlcm_score_bytes).
+ * backward: dscores [B, L] from any ultr_*_loss kernel (x D convention); loss_ws / n_loss_parts: that kernel's partials, folded into
+ * the step tail grads [P ..) (NULL / 0: the tail is left alone); workspace: ultr_dlcm_workspace_bytes.  Writes all P gradients; follow
+ * with ultr_grad_sumsq + ultr_apply_update(d = NULL, wt = NULL).  No atomics: the same inputs give the same bits.
+ * Every buffer is to be 16-byte aligned (ULTR_E_BADARG otherwise). */
+typedef struct ultr_dlcm_desc {
+  int32_t feature_size, hidden_size, num_heads;
+} ultr_dlcm_desc;
+/* offsets[0 .. 9) of the nine parameter tensors in the order above, offsets[9] = P; ULTR_E_BADARG on a bad desc */
+int ultr_dlcm_param_offsets(const ultr_dlcm_desc* c, int64_t* offsets);
+/* bytes for any batch x list_size = n_rows; ULTR_E_BADARG / ULTR_E_UNSUPPORTED as the calls */
+int64_t ultr_dlcm_saved_bytes(const ultr_dlcm_desc* c, int64_t n_rows);
+int64_t ultr_dlcm_score_bytes(const ultr_dlcm_desc* c, int64_t n_rows);
+int64_t ultr_dlcm_workspace_bytes(const ultr_dlcm_desc* c, int32_t batch, int32_t list_size);
+int ultr_dlcm_forward(const ultr_dlcm_desc* c, const float* params, const float* features, int64_t n_docs, const int32_t* docids,
+                      int32_t batch, int32_t list_size, float* scores, void* saved, void* work, void* stream);
+int ultr_dlcm_backward(const ultr_dlcm_desc* c, const float* params, const float* features, int64_t n_docs, const int32_t* docids,
+                       int32_t batch, int32_t list_size, const void* saved, const float* dscores, const void* loss_ws,
+                       int32_t n_loss_parts, void* workspace, float* grads, void* stream);
+
 /* ---- a5 (clip) + a6 (optimizer) + EM / propensity updates ----------------------------
  * Replaces torch.nn.utils.clip_grad_norm_ + Adagrad.step / SGD.step
  * (base_algorithm.py:223-226; ipw_rank.py:96), DLA.separate_gradient_update

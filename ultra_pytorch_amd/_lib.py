@@ -121,6 +121,10 @@ class SetRankDropout(ctypes.Structure):  # ultr_setrank_dropout
                 ("scratch_bytes", c_i64)]
 
 
+class DlcmDesc(ctypes.Structure):  # ultr_dlcm_desc
+    _fields_ = [("feature_size", c_i32), ("hidden_size", c_i32), ("num_heads", c_i32)]
+
+
 class StepArgs(ctypes.Structure):
     _fields_ = [("desc", ctypes.POINTER(DnnDesc)), ("upd", ctypes.POINTER(UpdateDesc)), ("params", c_vp), ("wt", c_vp),
                 ("state", c_vp), ("aux", c_vp), ("features", c_vp), ("docids", c_vp), ("labels", c_vp), ("pw", c_vp),
@@ -180,6 +184,13 @@ SIGNATURES = {
                                              ctypes.POINTER(SetRankDropout), c_vp]),
     "ultr_setrank_backward_dropout": (c_i32, [ctypes.POINTER(SetRankDesc), c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
                                               ctypes.POINTER(SetRankDropout), c_vp]),
+    "ultr_dlcm_param_offsets": (c_i32, [ctypes.POINTER(DlcmDesc), ctypes.POINTER(c_i64)]),
+    "ultr_dlcm_saved_bytes": (c_i64, [ctypes.POINTER(DlcmDesc), c_i64]),
+    "ultr_dlcm_score_bytes": (c_i64, [ctypes.POINTER(DlcmDesc), c_i64]),
+    "ultr_dlcm_workspace_bytes": (c_i64, [ctypes.POINTER(DlcmDesc), c_i32, c_i32]),
+    "ultr_dlcm_forward": (c_i32, [ctypes.POINTER(DlcmDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "ultr_dlcm_backward": (c_i32, [ctypes.POINTER(DlcmDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
+                                   c_vp]),
     "ultr_apply_update": (c_i32, [ctypes.POINTER(UpdateDesc), ctypes.POINTER(DnnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp]),
     "ultr_train_step": (c_i32, [ctypes.POINTER(StepArgs), c_vp]),

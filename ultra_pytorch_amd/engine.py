@@ -578,10 +578,45 @@ def _setrank_draw(list_size):
     random.shuffle(list(range(int(list_size))))
 
 
-class SetRankStepEngine(StepEngine):
+class StagedStepEngine(StepEngine):
+    """A step issued as stage calls instead of ONE C call, for the ranking models whose forward and backward are entries of their own
+    (SetRank, DLCM): forward(train=True) -> loss -> backward -> ultr_apply_update on the flat vector (no k-major weight copy).  At
+    their size (hundreds of microseconds to milliseconds per step) the host is not on the critical path.  A subclass supplies _alloc,
+    forward and backward (which leaves the sum-of-squares partials in self.bwd_ws)."""
+
+    def _range_flag(self):
+        """Device address of the model's split-half range word (ultr_update_desc::range_flag), None: it builds no such planes."""
+        return None
+
+    def update(self, params, state, aux=None):
+        check = _lib.check
+        self.udesc.range_flag = self._range_flag()
+        check(self.shape.lib.ultr_apply_update(ctypes.byref(self.udesc), None, ctypes.c_void_p(params.data_ptr()), None,
+                                               ctypes.c_void_p(state.data_ptr()) if state is not None else None,
+                                               ctypes.c_void_p(self.grads.data_ptr()),
+                                               ctypes.c_void_p(aux.data_ptr()) if aux is not None else None,
+                                               ctypes.c_void_p(self.bwd_ws.data_ptr()), ctypes.c_void_p(self.scalars.data_ptr()),
+                                               hip_ops.raw_stream()), "ultr_apply_update")
+
+    def train_step(self, params, state, features, n_docs, docids, labels, aux=None, ipw_table=None, pw=None, uniforms=None):
+        self._next_seq()
+        self.forward(params, features, n_docs, docids, train=True)
+        if self.algo == "regem":
+            self.loss(labels, aux=aux, uniforms=uniforms)
+        else:
+            self.loss(labels, aux=aux, ipw_table=ipw_table, pw=pw, docids=docids, n_docs=n_docs)
+        self.backward(params, features, n_docs, docids)
+        self.update(params, state, aux)
+        src = self.next_click_source
+        nxt = src.next_click_args() if src is not None else None
+        if nxt is not None:
+            _lib.check(self.shape.lib.ultr_click_batch_args(nxt, hip_ops.raw_stream()), "ultr_click_batch")
+        return self.scalars
+
+
+class SetRankStepEngine(StagedStepEngine):
     """The same step for the SetRank ranking model: ultr_setrank_forward -> ultr_<loss> ->
-    ultr_setrank_backward -> [all-reduce] -> ultr_grad_sumsq -> ultr_apply_update.  Stage calls instead of ONE C call:
-    at SetRank's size (hundreds of microseconds to milliseconds per step) the host is not on the critical path.
+    ultr_setrank_backward -> [all-reduce] -> ultr_grad_sumsq -> ultr_apply_update, as stage calls (StagedStepEngine).
 
     Dropout (shape.rate > 0): forward(train=True) takes the model's next dropout step (shape.next_dropout_step()) and passes
     (rate, shape.dropout_seed, step, dropout_stream) to ultr_setrank_forward_dropout; backward() hands the same struct, with the
@@ -623,31 +658,9 @@ class SetRankStepEngine(StepEngine):
         else:
             hip_ops.grad_sumsq(self.grads, self.P, self.L, self.bwd_ws)
 
-    def update(self, params, state, aux=None):
-        check = _lib.check
+    def _range_flag(self):
         # the range word of this step's split-half planes (raised by ultr_setrank_forward) travels in the step report
-        self.udesc.range_flag = self.saved.data_ptr() + 4 * self._flag_off
-        check(self.shape.lib.ultr_apply_update(ctypes.byref(self.udesc), None, ctypes.c_void_p(params.data_ptr()), None,
-                                               ctypes.c_void_p(state.data_ptr()) if state is not None else None,
-                                               ctypes.c_void_p(self.grads.data_ptr()),
-                                               ctypes.c_void_p(aux.data_ptr()) if aux is not None else None,
-                                               ctypes.c_void_p(self.bwd_ws.data_ptr()), ctypes.c_void_p(self.scalars.data_ptr()),
-                                               hip_ops.raw_stream()), "ultr_apply_update")
-
-    def train_step(self, params, state, features, n_docs, docids, labels, aux=None, ipw_table=None, pw=None, uniforms=None):
-        self._next_seq()
-        self.forward(params, features, n_docs, docids, train=True)
-        if self.algo == "regem":
-            self.loss(labels, aux=aux, uniforms=uniforms)
-        else:
-            self.loss(labels, aux=aux, ipw_table=ipw_table, pw=pw, docids=docids, n_docs=n_docs)
-        self.backward(params, features, n_docs, docids)
-        self.update(params, state, aux)
-        src = self.next_click_source
-        nxt = src.next_click_args() if src is not None else None
-        if nxt is not None:
-            _lib.check(self.shape.lib.ultr_click_batch_args(nxt, hip_ops.raw_stream()), "ultr_click_batch")
-        return self.scalars
+        return self.saved.data_ptr() + 4 * self._flag_off
 
 
 class SetRankEvalEngine(EvalEngine):
@@ -678,6 +691,49 @@ class SetRankEvalEngine(EvalEngine):
     def forward(self, params, features, n_docs, docids):
         _setrank_draw(self.L)
         hip_ops.setrank_score(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, self.work)
+        return self.scores
+
+
+class DlcmStepEngine(StagedStepEngine):
+    """The step for the DLCM ranking model: ultr_dlcm_forward -> ultr_<loss> -> ultr_dlcm_backward -> ultr_grad_sumsq ->
+    ultr_apply_update.  One GPU: a process_group is refused."""
+
+    def __init__(self, shape, batch, list_size, device, **kw):
+        if kw.get("process_group") is not None:
+            raise NotImplementedError("DLCM has no data-parallel step: train it on one GPU (process_group=None)")
+        super().__init__(shape, batch, list_size, device, **kw)
+
+    def _alloc(self, shape, device):
+        self.saved = _f32(shape.saved_bytes(self.N) // 4, device)
+        self.dl_ws = _f32(shape.workspace_bytes(self.B, self.L) // 4, device)
+        # sum-of-squares partials of ultr_grad_sumsq / ultr_apply_update
+        self.bwd_ws = _f32((self.P + self.tail + 63) // 64 + self.P // 4096 + 16, device)
+
+    def forward(self, params, features, n_docs, docids, scores=None, train=False):
+        scores = self.scores if scores is None else scores
+        hip_ops.dlcm_forward(self.shape, params, features, n_docs, docids, self.B, self.L, scores, saved=self.saved)
+        return scores
+
+    def backward(self, params, features, n_docs, docids):
+        hip_ops.dlcm_backward(self.shape, params, features, n_docs, docids, self.B, self.L, self.saved, self.dscores, self.loss_ws,
+                              hip_ops.loss_part_count(self.B), self.dl_ws, self.grads)
+        hip_ops.grad_sumsq(self.grads, self.P, self.L, self.bwd_ws)
+
+
+class DlcmEvalEngine(EvalEngine):
+    """validation() for DLCM: the scoring form of ultr_dlcm_forward (no record for a backward), then the metric launch."""
+
+    def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10), metrics=("ndcg",)):
+        super().__init__(shape, batch, list_size, device, topn=topn, metrics=metrics)
+        self.work = _f32(shape.score_bytes(self.B * self.L) // 4, device)
+
+    def run(self, params, features, n_docs, docids, labels):
+        self.forward(params, features, n_docs, docids)
+        self._ndcg(labels, docids, n_docs)
+        return self.scores, self.ndcg
+
+    def forward(self, params, features, n_docs, docids):
+        hip_ops.dlcm_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, work=self.work)
         return self.scores
 
 

@@ -236,6 +236,59 @@ def setrank_attn_path(shape, L, backward=False):
     return _lib.SR_ATTN_PATHS[rc]
 
 
+class DlcmShape:
+    """Host-side geometry of one DLCM model (include/ultr_hip.h: ultr_dlcm_*): descriptor + flat parameter layout in state_dict order.
+    `hidden_size` 0 means feature_size (the paper's choice).  feature_size and hidden_size must be multiples of 4: the size queries of
+    any other model raise UltrHipError ("unsupported shape"), as the calls do; the layout is defined for every model."""
+
+    NAMES = ("layer_norm.weight", "layer_norm.bias", "gru.weight_ih_l0", "gru.weight_hh_l0", "gru.bias_ih_l0", "gru.bias_hh_l0",
+             "att_linear.weight", "att_linear.bias", "att_v.weight")
+
+    def __init__(self, feature_size, hidden_size=0, num_heads=3):
+        self.lib = _lib.load()
+        self.feature_size, self.num_heads = int(feature_size), int(num_heads)
+        self.hidden_size = int(hidden_size) if int(hidden_size) > 0 else self.feature_size
+        self.desc = _lib.DlcmDesc(self.feature_size, self.hidden_size, self.num_heads)
+        offs = (ctypes.c_int64 * 10)()
+        if int(self.lib.ultr_dlcm_param_offsets(ctypes.byref(self.desc), offs)) != 0:
+            raise ValueError("bad DLCM description (feature_size, hidden_size and num_heads must be positive)")
+        self.offsets = list(offs)
+        self.n_params = int(offs[9])
+
+    def layout(self):
+        """[(state_dict key, shape, offset)] in parameter order."""
+        F, H, hd = self.feature_size, self.hidden_size, self.num_heads
+        shapes = ((F,), (F,), (3 * H, F), (3 * H, H), (3 * H,), (3 * H,), (hd * H, H), (hd * H,), (1, hd))
+        return [(n, s, o) for n, s, o in zip(self.NAMES, shapes, self.offsets)]
+
+    def _bytes(self, fn, *args):
+        n = int(getattr(self.lib, fn)(ctypes.byref(self.desc), *args))
+        check(min(n, 0), fn)
+        return n
+
+    def saved_bytes(self, n_rows):
+        return self._bytes("ultr_dlcm_saved_bytes", int(n_rows))
+
+    def score_bytes(self, n_rows):
+        """Bytes of the scoring form's buffer: what one launch hands to the next, nothing for a backward."""
+        return self._bytes("ultr_dlcm_score_bytes", int(n_rows))
+
+    def workspace_bytes(self, B, L):
+        return self._bytes("ultr_dlcm_workspace_bytes", int(B), int(L))
+
+
+def dlcm_forward(shape, params, features, n_docs, docids, B, L, scores, saved=None, work=None):
+    """saved: the training form; saved None: the scoring form on `work` (shape.score_bytes) - the same scores bit for bit."""
+    check(shape.lib.ultr_dlcm_forward(ctypes.byref(shape.desc), _p(params), _p(features) if n_docs > 0 else None, int(n_docs), _p(docids),
+                                      int(B), int(L), _p(scores), _p(saved), _p(work), _stream()), "ultr_dlcm_forward")
+
+
+def dlcm_backward(shape, params, features, n_docs, docids, B, L, saved, dscores, loss_ws, n_loss_parts, ws, grads):
+    check(shape.lib.ultr_dlcm_backward(ctypes.byref(shape.desc), _p(params), _p(features) if n_docs > 0 else None, int(n_docs), _p(docids),
+                                       int(B), int(L), _p(saved), _p(dscores), _p(loss_ws), int(n_loss_parts), _p(ws), _p(grads),
+                                       _stream()), "ultr_dlcm_backward")
+
+
 def tail_floats(L):
     return int(_lib.load().ultr_step_tail_floats(int(L)))
 
