@@ -106,6 +106,35 @@ def test_click_models_and_estimator():
     assert w[0] == est.IPW_list[0] and w[1] == 0.0 and w[2] == est.IPW_list[2] and w[-1] == est.IPW_list[-1]
 
 
+def test_click_model_load_and_tables_for_the_device(tmp_path):
+    """click_models.load_for_device / device_tables, what every GPU click simulation loads and uploads: the shipped JSONs by bare
+    file name, ids 0 / 1 / 2, the refusal that names its caller, [n] tables for PBM / cascade and the dense [n, n] image for UBM."""
+    import torch
+    from ultra_pytorch_amd.utils import click_models as cm
+    files = {"pbm_0.1_1.0_4_1.0.json": 0, "cascade_0.1_1.0_4_1.0.json": 1, "ubm_0.1_1_4_1.0.json": 2}
+    for name, mid in files.items():
+        desc, model, model_id = cm.load_for_device(os.path.join("no", "such", "dir", name), "Somebody")  # falls back to the package's data/
+        assert model_id == mid == cm.CLICK_MODEL_IDS[desc["model_name"]] and model.model_name == desc["model_name"]
+        assert model.exam_prob == desc["exam_prob"] and model.click_prob == desc["click_prob"] and model.eta == desc["eta"]
+        exam, n_exam, cprob = cm.device_tables(model, model_id, "cpu")
+        assert exam.dtype == cprob.dtype == torch.float32 and exam.is_contiguous() and n_exam == len(desc["exam_prob"])
+        np.testing.assert_array_equal(cprob.numpy(), np.asarray(desc["click_prob"], np.float32))
+        if mid == 2:
+            assert tuple(exam.shape) == (n_exam, n_exam)
+            for r, row in enumerate(desc["exam_prob"]):
+                np.testing.assert_array_equal(exam[r].numpy(), np.asarray(list(row) + [0.0] * (n_exam - len(row)), np.float32))
+        else:
+            assert tuple(exam.shape) == (n_exam,)
+            np.testing.assert_array_equal(exam.numpy(), np.asarray(desc["exam_prob"], np.float32))
+    odd = tmp_path / "odd.json"
+    odd.write_text(json.dumps({"model_name": "dependent_click_model", "eta": 1.0, "click_prob": [0.1, 1.0], "exam_prob": [1.0]}))
+    with pytest.raises(NotImplementedError, match="^Somebody simulates"):
+        cm.load_for_device(str(odd), "Somebody")
+    from ultra_pytorch_amd.learning_algorithm import dbgd
+    from ultra_pytorch_amd.utils import propensity_estimator
+    assert dbgd.CLICK_MODEL_IDS is cm.CLICK_MODEL_IDS and propensity_estimator.CLICK_MODEL_IDS is cm.CLICK_MODEL_IDS
+
+
 def test_click_models_draw_the_reference_stream():
     """PBM, the user-browsing model and the cascade model against the reference's own simulators (tests/golden/click_models.npz:
     click_models.py:68-110, 113-186, 187-236 run on its example JSONs): same `random` seed -> the same clicks, examination and

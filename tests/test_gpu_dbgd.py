@@ -177,6 +177,30 @@ def test_interleave_long_lists_and_injection():
         np.testing.assert_array_equal(g, r_, err_msg=name)
 
 
+@pytest.mark.parametrize("cm", ["cascade", "ubm"])
+def test_interleave_clicks_across_chunks(cm):
+    """The two models that carry state from one chunk of 64 positions to the next, on lists of 130 positions with a few clickable
+    documents each (label 0 is never clicked): the cascade's `a click in an earlier chunk` and the user-browsing model's `rank of the
+    last click` must cross the chunk boundary as the restatement's sequential walk does."""
+    NR, B, M, n_docs = 3, 48, 130, 10000
+    rng = np.random.RandomState(11)
+    sc = rng.standard_normal((NR, B, M)).astype(np.float32)
+    ids = rng.randint(0, n_docs, size=(M, B)).astype(np.int32)
+    y = np.zeros((M, B), np.float32)
+    for b in range(B):
+        y[rng.choice(M, 4 if b % 2 else 2, replace=False), b] = 4.0
+    model, ex, n_exam, cprob = _click_model(cm, never=True)
+    got = run_interleave(sc, ids, y, n_docs, M, O.DETERMINISTIC, 1.0, SEED, STEP, 100, model, ex, n_exam, cprob)
+    ref = R.interleave(sc, ids, y, n_docs, M, O.DETERMINISTIC, 1.0, SEED, STEP, 100, model, ex.cpu().numpy(), n_exam, cprob)
+    for g, r_, name in zip(got, ref, ("winners", "interleaved", "teams", "clicks")):
+        np.testing.assert_array_equal(g, r_, err_msg=name)
+    low, high = got[3][:64].sum(0), got[3][64:].sum(0)
+    if cm == "cascade":
+        assert ((low == 0) & (high == 1)).any()  # a list whose only click lies behind the first chunk
+    else:
+        assert ((low > 0) & (high > 0)).any()  # a list whose walk carries a click into the next chunk
+
+
 @pytest.mark.parametrize("tau", [1.0, 3.0])
 def test_interleave_stochastic_matches_where_keys_are_separated(tau):
     rng = np.random.RandomState(int(tau))

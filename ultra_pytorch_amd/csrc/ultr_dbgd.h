@@ -1,5 +1,5 @@
 // ultr_dbgd.h - what the weight-perturbing learners share (ultr_dbgd.hip: DBGD / MGD, ultr_nsgd.hip: NSGD): the Linear layout of the
-// flat DNN vector and the Philox key and Box-Muller normal of their noise.
+// flat DNN vector and the Box-Muller normal of their noise.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -17,10 +17,6 @@ struct DbgdLayout {
   int tiles[ULTR_MAXL];  // workgroups of layer j: ceil(K_j / 16) column tiles + one for the bias and the LayerNorm entries
   int64_t P;
 };
-
-__device__ __forceinline__ Philox dbgd_rng(uint64_t seed, uint64_t step) {
-  return Philox{(uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step};
-}
 
 // the standard normal of element e of ranker r under counter tag `tag`: Box-Muller on two uniforms of one Philox draw
 // (u1 in (0, 1], u2 in [0, 1))

@@ -21,9 +21,9 @@
 #include <string.h>
 
 #include "../../include/ultr_hip.h"
+#include "ultr_click.h"
 #include "ultr_dbgd.h"
 #include "ultr_device.h"
-#include "ultr_feed.h"
 #include "ultr_plan.h"
 #include "ultr_rank.h"
 
@@ -46,7 +46,7 @@ __device__ __forceinline__ float dbgd_normal(const ultr_dbgd_args& a, const Phil
 __global__ __launch_bounds__(1024) void dbgd_noise_kernel(ultr_dbgd_args a, DbgdLayout ly) {
   __shared__ float sm[64][DBGD_TILE_COLS];
   const int r = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const Philox rng = dbgd_rng(a.seed, a.step);
+  const Philox rng = philox_step_key(a.seed, a.step);
   const int64_t P = ly.P;
   float* __restrict__ u = a.noise + (int64_t)r * P;
   float* __restrict__ th = a.cand_params + (int64_t)r * (a.cand_stride > 0 ? a.cand_stride : P);
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64) void dbgd_interleave_kernel(ultr_dbgd_args a) {
   const int lane = threadIdx.x, b = blockIdx.x;
   const int B = a.batch, M = a.max_candidates, NR = a.n_rankers + 1, rls = a.rank_list_size;
   const int32_t pad = (int32_t)a.n_docs;
-  const Philox rng = dbgd_rng(a.seed, a.step);
+  const Philox rng = philox_step_key(a.seed, a.step);
 
   int last = -1;
   for (int l = lane; l < M; l += 64)
@@ -203,32 +203,15 @@ __global__ __launch_bounds__(64) void dbgd_interleave_kernel(ultr_dbgd_args a) {
 
   // clicks on the labels of the multileaved order (dbgd.py:311-324), redrawn while the list has none
   const int cut = len < rls ? len : rls;
-  const int rounds = a.clicks_in != nullptr ? 1 : 1 + a.max_redraws;
-  for (int attempt = 0; attempt < rounds && cut > 0; ++attempt) {
-    float any = 0.f;
-    bool clicked_before = false;
-    int last_click = -1;
-    for (int l0 = 0; l0 < cut; l0 += 64) {
-      const int l = l0 + lane;
-      const bool in = l < cut;
-      float ck;
-      if (a.clicks_in != nullptr) {
-        ck = in ? a.clicks_in[(int64_t)l * B + b] : 0.f;
-      } else {
-        const float y = in ? a.labels[(int64_t)ml[l] * B + b] : 0.f;
-        float uu = 0.f;
-        if (in) {
-          uint32_t c[4] = {(uint32_t)b, (uint32_t)attempt, (uint32_t)(l >> 2), DBGD_CLICK_TAG};
-          rng(c);
-          uu = u01(c[l & 3]);
-        }
-        ck = click_decide(a.click_model, a.exam_prob, a.n_exam, a.click_prob, a.n_rel, cut, l0, lane, in, y, uu, clicked_before,
-                          last_click);
-      }
-      if (in) ck_s[l] = ck;
-      any += ck;
-    }
-    if (wave_sum(any) > 0.f) break;
+  if (a.clicks_in != nullptr) {
+    for (int l = lane; l < cut; l += 64) ck_s[l] = a.clicks_in[(int64_t)l * B + b];
+  } else {
+    const ClickModel cm = click_model_of(a);
+    for (int attempt = 0; attempt <= a.max_redraws && cut > 0; ++attempt)
+      if (wave_click_walk(
+              cm, rng, (uint32_t)b, (uint32_t)attempt, DBGD_CLICK_TAG, cut, lane, [&](int l) { return a.labels[(int64_t)ml[l] * B + b]; },
+              [&](int l, float ck) { ck_s[l] = ck; }) > 0.f)
+        break;
   }
   wave_lds_sync();
 
@@ -311,11 +294,7 @@ extern "C" int ultr_dbgd_interleave_args(const ultr_dbgd_args* a, void* stream) 
   if (!dbgd_shape_ok(a) || !a->scores || !a->docids || !a->labels || !a->winners || a->max_redraws < 0 || a->n_docs < 0 ||
       a->n_docs >= ((int64_t)1 << 31) || (a->mode != ULTR_ONLINE_DETERMINISTIC && a->mode != ULTR_ONLINE_STOCHASTIC))
     return ULTR_E_BADARG;
-  if (!a->clicks_in &&
-      (!a->exam_prob || !a->click_prob || a->n_exam <= 0 || a->n_rel <= 0 ||
-       (a->click_model != ULTR_CLICK_PBM && a->click_model != ULTR_CLICK_CASCADE && a->click_model != ULTR_CLICK_UBM) ||
-       (a->click_model == ULTR_CLICK_UBM && a->n_exam < 2)))
-    return ULTR_E_BADARG;
+  if (!a->clicks_in && !click_model_ok(click_model_of(*a))) return ULTR_E_BADARG;
   hipLaunchKernelGGL(dbgd_interleave_kernel, dim3(a->batch), dim3(64), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }

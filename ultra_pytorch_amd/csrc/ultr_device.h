@@ -328,6 +328,16 @@ struct Philox {
     }
   }
 };
+// the key of every draw of training step `step` under `seed`
+__host__ __device__ __forceinline__ Philox philox_step_key(uint64_t seed, uint64_t step) {
+  return Philox{(uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step};
+}
+// the word of position l of a list: word l % 4 of counter (c0, c1, l / 4, tag) - c0, c1 name the list, tag the stream
+__device__ __forceinline__ uint32_t philox_word(const Philox& rng, uint32_t c0, uint32_t c1, int l, uint32_t tag) {
+  uint32_t c[4] = {c0, c1, (uint32_t)(l >> 2), tag};
+  rng(c);
+  return c[l & 3];
+}
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }  // [0, 1)
 
 __device__ __forceinline__ float quad_max(float v) {  // over the 4 lanes {i, i+16, i+32, i+48}

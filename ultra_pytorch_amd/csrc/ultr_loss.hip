@@ -132,7 +132,7 @@ __global__ __launch_bounds__(LPW * 64) void regem_kernel(const float* __restrict
   float* mt = sm_tail + wave * tail;
   for (int t = lane; t < tail; t += 64) mt[t] = 0.f;
   if (b < B) {
-    const Philox rng{(uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step};
+    const Philox rng = philox_step_key(seed, step);
     float lsum = 0.f, cnt = 0.f;
     for (int l = lane; l < L; l += 64) {
       const float s = scores[(int64_t)b * L + l];

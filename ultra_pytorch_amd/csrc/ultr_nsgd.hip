@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void nsgd_dot_kernel(ultr_dbgd_args a, ultr_ns
   const int t = nsgd_tensor(ly, c);
   const int64_t base = ly.off[t] + (int64_t)(c - ly.c0[t]) * NSGD_CHUNK, P = ly.P;
   const int len = nsgd_chunk_len(ly, t, base);
-  const Philox rng = dbgd_rng(a.seed, a.step);
+  const Philox rng = philox_step_key(a.seed, a.step);
   for (int r = 0; r < R; ++r) {
     float z = 0.f, m = 0.f;
     if (tid < len) {

@@ -15,7 +15,7 @@
 //                         (log p < ln 2^-150) gets key 0, below every drawn one, so those follow in index order (the reference's
 //                         `unused` tail);
 //   rank by counting over the first list_len keys (ties by index: stable), as ndcg_list_kernel does;
-//   clicks on the first min(list_len, rank_list_size) positions of the new order with click_decide (ultr_feed.h) - the same
+//   clicks on the first min(list_len, rank_list_size) positions of the new order with wave_click_walk (ultr_click.h) - the same
 //   per-position decisions as ultr_click_batch - redrawn on the SAME order while the list has no click (check_validation).
 // Randomness: Philox-4x32-10 keyed by (seed, step); counters (slot, 0, ~0, QUERY) for the pick, (slot, 0, l / 4, RACE) for the
 // race and (slot, attempt, l / 4, CLICK) for the clicks, word l % 4 for position l.  The tags differ from ultr_click_batch's and
@@ -25,8 +25,8 @@
 #include <stdint.h>
 
 #include "../../include/ultr_hip.h"
+#include "ultr_click.h"
 #include "ultr_device.h"
-#include "ultr_feed.h"
 #include "ultr_rank.h"
 
 #define ONLINE_MAX_M 256
@@ -34,17 +34,13 @@
 #define ONLINE_RACE_TAG 0x0F1A3E02u
 #define ONLINE_CLICK_TAG 0x0F1A3E03u
 
-__device__ __forceinline__ Philox online_rng(uint64_t seed, uint64_t step) {
-  return Philox{(uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step};
-}
-
 // one workgroup of 256 threads = four batch slots (one per wave)
 __global__ __launch_bounds__(256) void online_pick_kernel(ultr_online_args a) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int B = a.batch, M = a.max_candidates, lmax = a.lmax;
   if (b >= B) return;
-  const Philox rng = online_rng(a.seed, a.step);
+  const Philox rng = philox_step_key(a.seed, a.step);
   uint32_t c[4] = {(uint32_t)b, 0u, 0xFFFFFFFFu, ONLINE_QUERY_TAG};
   rng(c);
   const int64_t n = a.eligible != nullptr ? a.n_eligible : a.n_queries;
@@ -76,7 +72,7 @@ __global__ __launch_bounds__(256) void online_rerank_kernel(ultr_online_args a) 
   const int32_t pad = (int32_t)a.n_docs;
   unsigned* key = sm_key[w];
   int* perm = sm_perm[w];
-  const Philox rng = online_rng(a.seed, a.step);
+  const Philox rng = philox_step_key(a.seed, a.step);
 
   int last = -1;
   for (int l = lane; l < M; l += 64)
@@ -98,33 +94,15 @@ __global__ __launch_bounds__(256) void online_rerank_kernel(ultr_online_args a) 
   const int cut = len < a.rank_list_size ? len : a.rank_list_size;
   for (int l = cut + lane; l < M; l += 64) a.out_labels[(int64_t)l * B + b] = 0.f;
   if (cut <= 0) return;
-  const int rounds = a.oracle_mode ? 1 : 1 + a.max_redraws;
-  for (int attempt = 0; attempt < rounds; ++attempt) {
-    float any = 0.f;
-    bool clicked_before = false;  // cascade: a click in an earlier chunk of 64 positions
-    int last_click = -1;          // user-browsing model: rank of the last click so far
-    for (int l0 = 0; l0 < cut; l0 += 64) {
-      const int l = l0 + lane;
-      const bool in = l < cut;
-      const float y = in ? a.cand_labels[(int64_t)perm[l] * B + b] : 0.f;
-      float ck;
-      if (a.oracle_mode) {
-        ck = y;  // oracle_mode: the clicks are the relevance labels of the new order
-      } else {
-        float u = 0.f;
-        if (in) {
-          uint32_t r[4] = {(uint32_t)b, (uint32_t)attempt, (uint32_t)(l >> 2), ONLINE_CLICK_TAG};
-          rng(r);
-          u = u01(r[l & 3]);
-        }
-        ck = click_decide(a.click_model, a.exam_prob, a.n_exam, a.click_prob, a.n_rel, cut, l0, lane, in, y, u, clicked_before,
-                          last_click);
-      }
-      if (in) a.out_labels[(int64_t)l * B + b] = ck;
-      any += ck;
-    }
-    if (wave_sum(any) > 0.f) break;  // check_validation: only the clicks are redrawn, on the same order
+  const auto label = [&](int l) { return a.cand_labels[(int64_t)perm[l] * B + b]; };
+  const auto store = [&](int l, float ck) { a.out_labels[(int64_t)l * B + b] = ck; };
+  if (a.oracle_mode) {  // the clicks are the relevance labels of the new order
+    for (int l = lane; l < cut; l += 64) store(l, label(l));
+    return;
   }
+  const ClickModel cm = click_model_of(a);
+  for (int attempt = 0; attempt <= a.max_redraws; ++attempt)  // check_validation: only the clicks are redrawn, on the same order
+    if (wave_click_walk(cm, rng, (uint32_t)b, (uint32_t)attempt, ONLINE_CLICK_TAG, cut, lane, label, store) > 0.f) break;
 }
 
 static bool online_args_ok(const ultr_online_args* a) {
@@ -144,11 +122,7 @@ extern "C" int ultr_online_rerank_args(const ultr_online_args* a, void* stream) 
   if (!online_args_ok(a) || !a->scores || !a->docids || !a->out_labels || a->rank_list_size < 0 || a->max_redraws < 0 ||
       (a->mode != ULTR_ONLINE_DETERMINISTIC && a->mode != ULTR_ONLINE_STOCHASTIC))
     return ULTR_E_BADARG;
-  if (!a->oracle_mode &&
-      (!a->exam_prob || !a->click_prob || a->n_exam <= 0 || a->n_rel <= 0 ||
-       (a->click_model != ULTR_CLICK_PBM && a->click_model != ULTR_CLICK_CASCADE && a->click_model != ULTR_CLICK_UBM) ||
-       (a->click_model == ULTR_CLICK_UBM && a->n_exam < 2)))
-    return ULTR_E_BADARG;
+  if (!a->oracle_mode && !click_model_ok(click_model_of(*a))) return ULTR_E_BADARG;
   hipLaunchKernelGGL(online_rerank_kernel, dim3((a->batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }

@@ -10,13 +10,14 @@
 //     click to global memory directly would be the whole run time);
 //   - lmax <= 32: a wavefront runs 64 / W sessions at once in segments of W = 8 / 16 / 32 lanes (one lane per position, all per-lane
 //     arithmetic; the cascade's first click is a ballot cut to the segment, the user-browsing walk steps all segments together);
-//     lmax > 32: one session per wavefront in chunks of 64 positions through click_decide, as click_draw does.
+//     lmax > 32: one session per wavefront through wave_click_walk (ultr_click.h), as click_draw does.
 // Which wave or segment runs session s does not enter the draw: counters are (lo32(s), hi32(s), group, tag) under click_draw's key
 // with step = 0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ultr_hip.h"
+#include "ultr_click.h"
 #include "ultr_device.h"
 #include "ultr_feed.h"
 #include "ultr_rank.h"
@@ -42,18 +43,15 @@ __device__ __forceinline__ PropSession prop_pick(const ultr_propensity_args& a, 
   p.n = n < 0 ? 0 : (n > a.lmax ? a.lmax : n);
   return p;
 }
-__device__ __forceinline__ uint32_t prop_word(const Philox& rng, uint64_t s, int l, uint32_t tag) {
-  uint32_t c[4] = {(uint32_t)s, (uint32_t)(s >> 32), (uint32_t)(l >> 2), tag};
-  rng(c);
-  return c[l & 3];
-}
 
 // 64 / W sessions per wavefront trip, lmax <= W <= 32
 template <int W>
 __device__ __forceinline__ void prop_packed(const ultr_propensity_args& a, const Philox& rng, unsigned* hist, unsigned* key, int* perm) {
   constexpr int SPW = 64 / W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, seg = lane / W, pos = lane % W, base = seg * W;
-  const int model = a.click_model;
+  const ClickModel cm = click_model_of(a);
+  ClickModel each = cm;  // the decision of each position on its own: the cascade's cut and the user-browsing walk run per segment below
+  each.model = ULTR_CLICK_PBM;
   const uint64_t stride = (uint64_t)gridDim.x * PROP_WAVES * SPW;
   const uint64_t slot = ((uint64_t)blockIdx.x * PROP_WAVES + wave) * SPW + seg;
   const int64_t trips = (a.n_sessions + (int64_t)stride - 1) / (int64_t)stride;
@@ -64,25 +62,25 @@ __device__ __forceinline__ void prop_packed(const ultr_propensity_args& a, const
     const PropSession p = prop_pick(a, rng, s, active);
     const int n = p.n;
     const bool in = pos < n;
-    if (in) key[lane] = prop_word(rng, s, pos, ULTR_SHUFFLE_TAG);
+    if (in) key[lane] = philox_word(rng, (uint32_t)s, (uint32_t)(s >> 32), pos, ULTR_SHUFFLE_TAG);
     wave_lds_sync();
     wave_rank_by_count(key + base, n, perm + base, pos);
     wave_lds_sync();
     float y = 0.f, u = 0.f;
     if (in) {
       y = a.labels[p.q * a.lmax + perm[lane]];
-      u = u01(prop_word(rng, s, pos, ULTR_CLICK_TAG));
+      u = u01(philox_word(rng, (uint32_t)s, (uint32_t)(s >> 32), pos, ULTR_CLICK_TAG));
     }
     float ck;
-    if (model == ULTR_CLICK_UBM) {
+    if (cm.model == ULTR_CLICK_UBM) {
       // click_decide's walk with a `last click` per segment: every lane follows its own segment's list
-      const float ratio = in ? u / click_prob_of(a.click_prob, a.n_rel, y) : 0.f;
+      const float ratio = in ? u / click_prob_of(cm, y) : 0.f;
       int last = -1;
       ck = 0.f;
       for (int r = 0; r < W; ++r) {
         const float rk = __shfl(ratio, base + r);
         if (r < n) {
-          const bool hit = rk < ubm_exam_prob(a.exam_prob, a.n_exam, r, r - last);
+          const bool hit = rk < ubm_exam_prob(cm, r, r - last);
           if (hit) last = r;
           if (hit && pos == r) ck = 1.f;
         }
@@ -90,8 +88,8 @@ __device__ __forceinline__ void prop_packed(const ultr_propensity_args& a, const
     } else {
       bool cb = false;
       int lc = -1;
-      ck = click_decide(ULTR_CLICK_PBM, a.exam_prob, a.n_exam, a.click_prob, a.n_rel, n, 0, pos, in, y, u, cb, lc);
-      if (model == ULTR_CLICK_CASCADE) {  // only the first click of the list counts: the ballot of click_decide, cut to the segment
+      ck = click_decide(each, n, 0, pos, in, y, u, cb, lc);
+      if (cm.model == ULTR_CLICK_CASCADE) {  // only the first click of the list counts: the ballot of click_decide, cut to the segment
         const uint64_t hit = (__ballot(ck > 0.f) >> base) & ((1ull << W) - 1ull);
         const int first = hit ? (int)__builtin_ctzll(hit) : W;
         if (pos > first) ck = 0.f;
@@ -106,29 +104,23 @@ __device__ __forceinline__ void prop_packed(const ultr_propensity_args& a, const
 // one session per wavefront trip, lmax <= 128
 __device__ __forceinline__ void prop_wave(const ultr_propensity_args& a, const Philox& rng, unsigned* hist, unsigned* key, int* perm) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const ClickModel cm = click_model_of(a);
   const uint64_t stride = (uint64_t)gridDim.x * PROP_WAVES;
   const uint64_t slot = (uint64_t)blockIdx.x * PROP_WAVES + wave;
   for (uint64_t k = slot; k < (uint64_t)a.n_sessions; k += stride) {
     const uint64_t s = a.first_session + k;
+    const uint32_t c0 = (uint32_t)s, c1 = (uint32_t)(s >> 32);
     const PropSession p = prop_pick(a, rng, s, true);
     const int n = __builtin_amdgcn_readfirstlane(p.n);
-    for (int l = lane; l < n; l += 64) key[l] = prop_word(rng, s, l, ULTR_SHUFFLE_TAG);
+    for (int l = lane; l < n; l += 64) key[l] = philox_word(rng, c0, c1, l, ULTR_SHUFFLE_TAG);
     wave_lds_sync();
     wave_rank_by_count(key, n, perm, lane);
     wave_lds_sync();
-    bool clicked_before = false;
-    int last_click = -1;
-    for (int l0 = 0; l0 < n; l0 += 64) {
-      const int l = l0 + lane;
-      float y = 0.f, u = 0.f;
-      if (l < n) {
-        y = a.labels[p.q * a.lmax + perm[l]];
-        u = u01(prop_word(rng, s, l, ULTR_CLICK_TAG));
-      }
-      const float ck = click_decide(a.click_model, a.exam_prob, a.n_exam, a.click_prob, a.n_rel, n, l0, lane, l < n, y, u, clicked_before,
-                                    last_click);
-      if (ck > 0.f) atomicAdd(&hist[(n - 1) * n / 2 + l], 1u);
-    }
+    wave_click_walk(
+        cm, rng, c0, c1, ULTR_CLICK_TAG, n, lane, [&](int l) { return a.labels[p.q * a.lmax + perm[l]]; },
+        [&](int l, float ck) {
+          if (ck > 0.f) atomicAdd(&hist[(n - 1) * n / 2 + l], 1u);
+        });
     wave_lds_sync();  // perm is read above and rewritten by the next session
   }
 }
@@ -156,10 +148,8 @@ __global__ __launch_bounds__(PROP_WAVES * 64) void propensity_count_kernel(ultr_
 }
 
 static bool propensity_args_ok(const ultr_propensity_args* a) {
-  return a && a->labels && a->lengths && a->exam_prob && a->click_prob && a->click_count && a->n_queries > 0 && a->lmax > 0 && a->n_exam > 0 &&
-         a->n_rel > 0 && a->n_sessions >= 0 &&
-         (a->click_model == ULTR_CLICK_PBM || a->click_model == ULTR_CLICK_CASCADE || a->click_model == ULTR_CLICK_UBM) &&
-         !(a->click_model == ULTR_CLICK_UBM && a->n_exam < 2);
+  return a && a->labels && a->lengths && a->click_count && a->n_queries > 0 && a->lmax > 0 && a->n_sessions >= 0 &&
+         click_model_ok(click_model_of(*a));
 }
 
 extern "C" int ultr_propensity_count(const ultr_propensity_args* a, void* stream) {

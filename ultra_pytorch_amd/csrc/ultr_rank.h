@@ -37,8 +37,8 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// key[l] for l < len of the scores s[0 .. len) (one list, whole wave).  Stochastic: the race uniform of position l is word l % 4 of
-// Philox(c0, c1, l / 4, tag) - the caller's counter words name the list (and ranker) and the stream.
+// key[l] for l < len of the scores s[0 .. len) (one list, whole wave).  Stochastic: the race uniform of position l is
+// philox_word(c0, c1, l, tag) - the caller's counter words name the list (and ranker) and the stream.
 __device__ __forceinline__ void wave_rank_keys(const float* __restrict__ s, int len, bool stochastic, float tau, const Philox& rng,
                                                uint32_t c0, uint32_t c1, uint32_t tag, unsigned* key, int lane) {
   float sum = 0.f, mxs = -INFINITY;
@@ -53,9 +53,7 @@ __device__ __forceinline__ void wave_rank_keys(const float* __restrict__ s, int 
     unsigned k;
     if (stochastic) {
       const float lw = tau * (v - mxs);
-      uint32_t r[4] = {c0, c1, (uint32_t)(l >> 2), tag};
-      rng(r);
-      const float e = -logf(1.0f - u01(r[l & 3]));  // Exp(1); 1 - u is exact for u = k 2^-24
+      const float e = -logf(1.0f - u01(philox_word(rng, c0, c1, l, tag)));  // Exp(1); 1 - u is exact for u = k 2^-24
       // fp32 probability 0: exp(lw) / sum rounds to 0 below 2^-150, judged in the log domain (exp in the subnormal range is not
       // reproducible across implementations; log p = lw - log sum is)
       k = (lw - logf(sum) < ULTR_RANK_LN_ZERO_PROB) ? 0u : rank_order_key(lw - logf(e));

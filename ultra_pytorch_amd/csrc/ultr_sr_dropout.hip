@@ -217,8 +217,9 @@ __global__ __launch_bounds__(256) void sr_drop_mask_kernel(SrDropArgs a, uint32_
 
 int sr_drop_args(float rate, uint64_t seed, uint64_t step, uint32_t stream, int B, int L, SrDropArgs* out) {
   if (!(rate >= 0.0f && rate < 1.0f) || B <= 0 || L <= 0 || stream >= (1u << 24) || out == nullptr) return ULTR_E_BADARG;
-  out->k0 = (uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32);
-  out->k1 = (uint32_t)(seed >> 32) ^ (uint32_t)step;
+  const Philox key = philox_step_key(seed, step);
+  out->k0 = key.k0;
+  out->k1 = key.k1;
   out->stream = stream;
   out->rate = rate;
   out->scale = 1.0f / (1.0f - rate);

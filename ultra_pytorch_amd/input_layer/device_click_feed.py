@@ -13,8 +13,6 @@ changes nothing but when the kernel runs - under the step's reduction / update i
 then only hands out the buffer that is already filled (and draws on the spot when nobody drew ahead, or when its arguments differ
 from what was assumed).  The feed dictionaries are cached per buffer: no per-step ctypes / dict construction."""
 import ctypes
-import json
-import os
 
 import numpy as np
 import torch
@@ -53,21 +51,13 @@ class DeviceClickFeed(object):
         self.hparams = HParams(click_model_json="./example/ClickModel/pbm_0.1_1.0_4_1.0.json", max_tries=100,
                                dynamic_bias_eta_change=0.0, dynamic_bias_step_interval=1000)
         self.hparams.parse(hparam_str)
-        path = self.hparams.click_model_json
-        if not os.path.exists(path):
-            alt = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", os.path.basename(path))
-            path = alt if os.path.exists(alt) else path
-        desc = json.load(open(path))
-        if desc["model_name"] not in ("position_biased_model", "cascade_model", "user_browsing_model"):
-            raise NotImplementedError("DeviceClickFeed simulates the position-biased, the cascade and the user-browsing model")
-        self.click_model = click_models.loadModelFromJson(desc)  # host twin: owns eta and the examination table
-        self.model_id = {"position_biased_model": 0, "cascade_model": 1, "user_browsing_model": 2}[desc["model_name"]]
+        # click_model is the host twin: it owns eta and the examination table
+        _, self.click_model, self.model_id = click_models.load_for_device(self.hparams.click_model_json, "DeviceClickFeed")
         self.model, self.batch_size = model, int(batch_size)
         self.rank_list_size = model.rank_list_size
         self.device = model.cuda
-        self.exam, self.n_exam = self._exam_tensor()
+        self.exam, self.n_exam, self.cprob = click_models.device_tables(self.click_model, self.model_id, self.device)
         self.global_batch_count = 0
-        self.cprob = torch.tensor(desc["click_prob"], dtype=torch.float32, device=self.device)
         self.seed, self.step = int(seed), 0
         self.lib = _lib.load()
         self._resident = {}
@@ -84,14 +74,8 @@ class DeviceClickFeed(object):
         self.docids, self.clicks, self.qidx = self._bufs[0]
 
     def _exam_tensor(self):
-        """The examination table on the device: [n] for PBM / cascade, a dense [n][n] image of the triangular rank x distance table
-        for the user-browsing model (ULTR_CLICK_UBM)."""
-        ep = self.click_model.exam_prob
-        if self.model_id == 2:
-            n = len(ep)
-            dense = [[(row[c] if c < len(row) else 0.0) for c in range(n)] for row in ep]
-            return torch.tensor(dense, dtype=torch.float32, device=self.device).contiguous(), n
-        return torch.tensor(ep, dtype=torch.float32, device=self.device), len(ep)
+        """(examination table on the device, n_exam): click_models.device_tables' image of the host twin as it is now."""
+        return click_models.device_tables(self.click_model, self.model_id, self.device)[:2]
 
     @staticmethod
     def preprocess_data(data_set, hparam_str, exp_settings):

@@ -13,8 +13,6 @@ The result is the `device_feed` dict the plugin algorithms take (docids / labels
 past selection_bias_cutoff).  Same per-list distribution as the host feeds, not the same random stream: a batch is a pure function
 of (seed, batch counter, parameters) - Philox-4x32-10 on the device."""
 import ctypes
-import json
-import os
 
 import torch
 
@@ -22,7 +20,7 @@ from .. import _lib
 from .. import hip_ops
 from ..utils import HParams
 from ..utils import click_models
-from .device_click_feed import DeviceClickFeed, ResidentDataset
+from .device_click_feed import ResidentDataset
 
 
 class DeviceOnlineSimulationFeed(object):
@@ -46,17 +44,8 @@ class DeviceOnlineSimulationFeed(object):
         if self.need_interleave and not getattr(model, "INTERLEAVES_IN_TRAIN", False):
             raise NotImplementedError("result interleaving (TeamDraftInterleaving) is done by DBGD / MGD inside train(); %s does "
                                       "not interleave" % type(model).__name__)
-        path = self.hparams.click_model_json
-        if not os.path.exists(path):
-            alt = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", os.path.basename(path))
-            path = alt if os.path.exists(alt) else path
-        with open(path) as fin:
-            desc = json.load(fin)
-        ids = {"position_biased_model": 0, "cascade_model": 1, "user_browsing_model": 2}
-        if desc["model_name"] not in ids:
-            raise NotImplementedError("DeviceOnlineSimulationFeed simulates the position-biased, the cascade and the user-browsing model")
-        self.click_model = click_models.loadModelFromJson(desc)  # host twin: owns eta and the examination table
-        self.model_id = ids[desc["model_name"]]
+        # click_model is the host twin: it owns eta and the examination table
+        _, self.click_model, self.model_id = click_models.load_for_device(self.hparams.click_model_json, "DeviceOnlineSimulationFeed")
         self.model, self.batch_size = model, int(batch_size)
         self.rank_list_size = int(model.rank_list_size)
         self.max_candidate_num = int(model.max_candidate_num)
@@ -64,8 +53,7 @@ class DeviceOnlineSimulationFeed(object):
             raise ValueError("DeviceOnlineSimulationFeed supports max_candidate_num up to %d (got %d)"
                              % (self.MAX_CANDIDATES, self.max_candidate_num))
         self.device = model.cuda
-        self.exam, self.n_exam = DeviceClickFeed._exam_tensor(self)
-        self.cprob = torch.tensor(desc["click_prob"], dtype=torch.float32, device=self.device)
+        self.exam, self.n_exam, self.cprob = click_models.device_tables(self.click_model, self.model_id, self.device)
         self.seed, self.step, self.global_batch_count = int(seed), 0, 0
         self.lib = _lib.load()
         self._resident = {}
@@ -140,7 +128,7 @@ class DeviceOnlineSimulationFeed(object):
         if self.hparams.dynamic_bias_eta_change != 0 and self.global_batch_count % self.hparams.dynamic_bias_step_interval == 0:
             self.click_model.eta += self.hparams.dynamic_bias_eta_change
             self.click_model.setExamProb(self.click_model.eta)
-            self.exam, self.n_exam = DeviceClickFeed._exam_tensor(self)
+            self.exam, self.n_exam = click_models.device_tables(self.click_model, self.model_id, self.device)[:2]
         feed = {"device_feed": True, "features": rd.features, "n_docs": rd.n_docs, "docids": buf["docids"], "labels": buf["labels"],
                 "batch_size": self.batch_size, "feed_obj": None}
         # device tensors: query index [B], the candidates before the re-ranking [M, B] and the candidate index at each rank [M, B]

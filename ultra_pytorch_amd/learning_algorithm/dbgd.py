@@ -1,9 +1,6 @@
 """DBGD and MGD - Dueling Bandit Gradient Descent (Yue & Joachims, ICML 2009) and Multileave Gradient Descent (Schuth et al.,
 WSDM 2016), the weight-perturbing online learners.  Drop-in for ultra.learning_algorithm.DBGD / MGD (reference dbgd.py:27-330,
 mgd.py:23-232, team_draft_interleave.py)."""
-import json
-import os
-
 import torch
 
 from .. import engine
@@ -11,7 +8,7 @@ from ..utils import HParams
 from ..utils import click_models
 from .base_algorithm import BaseAlgorithm
 
-CLICK_MODEL_IDS = {"position_biased_model": 0, "cascade_model": 1, "user_browsing_model": 2}  # include/ultr_hip.h: ULTR_CLICK_*
+CLICK_MODEL_IDS = click_models.CLICK_MODEL_IDS
 
 
 class DBGD(BaseAlgorithm):
@@ -53,24 +50,8 @@ class DBGD(BaseAlgorithm):
         self._load_click_model()
 
     def _load_click_model(self):
-        path = self.hparams.click_model_json
-        if not os.path.exists(path):  # the reference's default is relative to its repo root; the same file ships here
-            alt = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", os.path.basename(path))
-            path = alt if os.path.exists(alt) else path
-        with open(path) as fin:
-            desc = json.load(fin)
-        if desc["model_name"] not in CLICK_MODEL_IDS:
-            raise NotImplementedError("%s simulates the position-biased, the cascade and the user-browsing model"
-                                      % type(self).__name__)
-        self.click_model = click_models.loadModelFromJson(desc)
-        self.click_model_id = CLICK_MODEL_IDS[desc["model_name"]]
-        ep = self.click_model.exam_prob
-        if self.click_model_id == 2:  # user-browsing model: dense [n][n] image of the triangular rank x distance table
-            n = len(ep)
-            ep = [[(row[c] if c < len(row) else 0.0) for c in range(n)] for row in ep]
-        self.exam = torch.tensor(ep, dtype=torch.float32, device=self.cuda).contiguous()
-        self.n_exam = len(self.click_model.exam_prob)
-        self.cprob = torch.tensor(desc["click_prob"], dtype=torch.float32, device=self.cuda)
+        _, self.click_model, self.click_model_id = click_models.load_for_device(self.hparams.click_model_json, type(self).__name__)
+        self.exam, self.n_exam, self.cprob = click_models.device_tables(self.click_model, self.click_model_id, self.cuda)
 
     def _dbgd_engine(self, B, M):
         key = (B, M)

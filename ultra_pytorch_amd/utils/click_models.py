@@ -1,6 +1,9 @@
 """Click simulators (host side): position-biased, user-browsing and cascade models driven by Python's `random` stream, so that
 a seeded run draws the same clicks as the reference's simulators (ultra/utils/click_models.py:7-16, 68-110, 113-186, 187-236):
-one `random.random()` per list position, click iff u < exam_prob * click_prob[label]."""
+one `random.random()` per list position, click iff u < exam_prob * click_prob[label].  Below them: how a model reaches the GPU
+(CLICK_MODEL_IDS, load_for_device, device_tables) - the device feeds, DBGD / MGD / NSGD and the propensity estimator all go through it."""
+import json
+import os
 import random
 
 
@@ -132,3 +135,33 @@ def loadModelFromJson(model_desc):
     model.click_prob = model_desc["click_prob"]
     model.exam_prob = model_desc["exam_prob"]
     return model
+
+
+# The click models the GPU simulates (include/ultr_hip.h: ULTR_CLICK_PBM / _CASCADE / _UBM), and how one gets there.
+CLICK_MODEL_IDS = {"position_biased_model": 0, "cascade_model": 1, "user_browsing_model": 2}
+
+
+def load_for_device(path, who):
+    """(desc, model, model_id) of the click-model JSON at `path`; a path that does not exist falls back to the file of that name in the
+    package's data/ (the reference's defaults are relative to its repository root; the same files ship here).  `who` is the subject
+    of the refusal of a model the GPU does not simulate."""
+    if not os.path.exists(path):
+        alt = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", os.path.basename(path))
+        path = alt if os.path.exists(alt) else path
+    with open(path) as fin:
+        desc = json.load(fin)
+    if desc["model_name"] not in CLICK_MODEL_IDS:
+        raise NotImplementedError("%s simulates the position-biased, the cascade and the user-browsing model" % who)
+    return desc, loadModelFromJson(desc), CLICK_MODEL_IDS[desc["model_name"]]
+
+
+def device_tables(model, model_id, device):
+    """(exam tensor, n_exam, cprob tensor) of `model` on `device` as the kernels read them: the examination table [n] for PBM /
+    cascade, a dense [n][n] image of the triangular rank x distance table for the user-browsing model; the click probabilities [n_rel]."""
+    import torch
+    ep = model.exam_prob
+    n = len(ep)
+    if model_id == CLICK_MODEL_IDS["user_browsing_model"]:
+        ep = [[(row[c] if c < len(row) else 0.0) for c in range(n)] for row in ep]
+    return (torch.tensor(ep, dtype=torch.float32, device=device).contiguous(), n,
+            torch.tensor(model.click_prob, dtype=torch.float32, device=device))

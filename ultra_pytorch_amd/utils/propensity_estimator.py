@@ -12,7 +12,7 @@ import os
 
 from . import click_models as CM
 
-CLICK_MODEL_IDS = {"position_biased_model": 0, "cascade_model": 1, "user_browsing_model": 2}  # ULTR_CLICK_PBM / _CASCADE / _UBM
+CLICK_MODEL_IDS = CM.CLICK_MODEL_IDS
 SESSIONS_PER_CALL = 1 << 24  # sessions per ultr_propensity_count call: the counter is (seed, session), the split changes nothing
 
 
@@ -83,17 +83,13 @@ class RandomizedPropensityEstimator(BasicPropensityEstimator):
         for q, lab in enumerate(label_lists):
             labels[q, :len(lab)] = lab
         model_id = CLICK_MODEL_IDS[click_model.model_name]
-        ep = click_model.exam_prob
-        if model_id == 2:  # dense [n][n] image of the triangular rank x distance table, as the device feeds upload it
-            ep = [[(row[c] if c < len(row) else 0.0) for c in range(len(ep))] for row in ep]
         with torch.cuda.device(device):
             d_labels = torch.tensor(labels, device=device)
             d_lengths = torch.tensor([len(x) for x in label_lists], dtype=torch.int32, device=device)
-            d_exam = torch.tensor(ep, dtype=torch.float32, device=device).contiguous()
-            d_cprob = torch.tensor(click_model.click_prob, dtype=torch.float32, device=device)
+            d_exam, n_exam, d_cprob = CM.device_tables(click_model, model_id, device)
             d_count = torch.zeros(L, L, dtype=torch.int64, device=device)
             for first in range(0, int(session_num), SESSIONS_PER_CALL):
-                hip_ops.propensity_count(d_labels, d_lengths, d_exam, len(click_model.exam_prob), d_cprob, model_id, seed, first,
+                hip_ops.propensity_count(d_labels, d_lengths, d_exam, n_exam, d_cprob, model_id, seed, first,
                                          min(SESSIONS_PER_CALL, int(session_num) - first), d_count)
             self.click_count = d_count.cpu().numpy()
         self.click_model = click_model
