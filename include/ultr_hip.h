@@ -438,6 +438,46 @@ int ultr_dlcm_backward(const ultr_dlcm_desc* c, const float* params, const float
                        int32_t batch, int32_t list_size, const void* saved, const float* dscores, const void* loss_ws,
                        int32_t n_loss_parts, void* workspace, float* grads, void* stream);
 
+/* ---- the GSF ranking model (additive within ABI 8) ---------------------------------------------
+ * Groupwise Scoring Function (Ai, Wang, Bendersky et al., ICTIR 2019); the reference's README lists it and ships no code.
+ * Per list of L presented positions (m = group_size): perm[p] = the presented position at place p (NULL: the identity); group g
+ * (one per place) holds in slot j the document at place (g + j) mod L, a PAD (document id n_docs) as the zero row;
+ * u_g = LayerNorm_{mF}(the m rows side by side), eps 1e-5; then the DNN's layers on it, [Linear -> act -> LayerNorm] x n_hidden and
+ * a Linear of m outputs o_g; score[perm[p]] = sum_j o_{(p - j) mod L}[j], summed in the order j = 0 .. m - 1.
+ * params: one flat vector in the DNN's order, offsets by ultr_gsf_param_offsets: per Linear layer LayerNorm weight / bias [K_j], weight
+ * [M_j, K_j], bias [M_j] with K_0 = m F and M_last = m; at m = 1 the layout and the model are ultr_dnn_desc's.
+ * feature_size and every hidden width are multiples of 4 (16-byte rows), 1 <= group_size <= 8; every other model is
+ * ULTR_E_UNSUPPORTED (not a model at all: ULTR_E_BADARG) from the size queries and from the calls, before anything is launched or
+ * written.  Any batch >= 1, list_size >= 1 (m > L: a document recurs in a group).
+ * shuffle: perm [B, L], list b by Fisher-Yates from the identity, i = L - 1 .. 1: r = philox_word(philox_step_key(seed, step), b, 0,
+ * i, ULTR_GSF_SHUFFLE_TAG), j = (r (i + 1)) >> 32, swap entries i and j.  A pure function of (seed, step, list).
+ * forward: docids [L, B] position-major (PAD = n_docs), scores [B, L].  saved != NULL (ultr_gsf_saved_bytes): the training form, `work`
+ * is not read; saved == NULL: the scoring form, the same launches with the same bits on `work` (ultr_gsf_score_bytes).  perm must be
+ * a permutation per list; an entry outside 0 .. L - 1 reads as a PAD and writes no score.
+ * backward: dscores [B, L] from any ultr_*_loss kernel (x D convention), d o_g[j] = dscores[perm[(g + j) mod L]]; perm as the forward's;
+ * loss_ws / n_loss_parts: that kernel's partials, folded into the step tail grads [P ..) (NULL / 0: the tail is left alone);
+ * workspace: ultr_gsf_workspace_bytes.  Writes all P gradients; follow with ultr_grad_sumsq + ultr_apply_update(d = NULL, wt = NULL).
+ * No atomics: the same inputs give the same bits.  Every buffer is to be 16-byte aligned (ULTR_E_BADARG otherwise). */
+typedef struct ultr_gsf_desc {
+  int32_t feature_size, group_size, n_hidden;
+  int32_t hidden[ULTR_MAX_HIDDEN];
+  int32_t activation; /* as ultr_dnn_desc: 0 elu, 1 relu, 2 tanh, 3 sigmoid */
+} ultr_gsf_desc;
+/* P, or 0 on a bad desc */
+int64_t ultr_gsf_param_count(const ultr_gsf_desc* c);
+/* offsets[4 j .. 4 j + 4) = LayerNorm weight, LayerNorm bias, Linear weight, Linear bias of layer j <= n_hidden; ULTR_E_BADARG on a bad desc */
+int ultr_gsf_param_offsets(const ultr_gsf_desc* c, int64_t* offsets);
+/* bytes for any batch x list_size = n_rows; ULTR_E_BADARG / ULTR_E_UNSUPPORTED as the calls */
+int64_t ultr_gsf_saved_bytes(const ultr_gsf_desc* c, int64_t n_rows);
+int64_t ultr_gsf_score_bytes(const ultr_gsf_desc* c, int64_t n_rows);
+int64_t ultr_gsf_workspace_bytes(const ultr_gsf_desc* c, int32_t batch, int32_t list_size);
+int ultr_gsf_shuffle(uint64_t seed, uint64_t step, int32_t batch, int32_t list_size, int32_t* perm, void* stream);
+int ultr_gsf_forward(const ultr_gsf_desc* c, const float* params, const float* features, int64_t n_docs, const int32_t* docids,
+                     const int32_t* perm, int32_t batch, int32_t list_size, float* scores, void* saved, void* work, void* stream);
+int ultr_gsf_backward(const ultr_gsf_desc* c, const float* params, const float* features, int64_t n_docs, const int32_t* docids,
+                      const int32_t* perm, int32_t batch, int32_t list_size, const void* saved, const float* dscores, const void* loss_ws,
+                      int32_t n_loss_parts, void* workspace, float* grads, void* stream);
+
 /* ---- a5 (clip) + a6 (optimizer) + EM / propensity updates ----------------------------
  * Replaces torch.nn.utils.clip_grad_norm_ + Adagrad.step / SGD.step
  * (base_algorithm.py:223-226; ipw_rank.py:96), DLA.separate_gradient_update

@@ -125,6 +125,14 @@ class DlcmDesc(ctypes.Structure):  # ultr_dlcm_desc
     _fields_ = [("feature_size", c_i32), ("hidden_size", c_i32), ("num_heads", c_i32)]
 
 
+class GsfDesc(ctypes.Structure):  # ultr_gsf_desc
+    _fields_ = [("feature_size", c_i32), ("group_size", c_i32), ("n_hidden", c_i32), ("hidden", c_i32 * ULTR_MAX_HIDDEN),
+                ("activation", c_i32)]
+
+
+GSF_MAX_GROUP = 8  # csrc/ultr_gsf_plan.h: documents per group the kernels take
+
+
 class StepArgs(ctypes.Structure):
     _fields_ = [("desc", ctypes.POINTER(DnnDesc)), ("upd", ctypes.POINTER(UpdateDesc)), ("params", c_vp), ("wt", c_vp),
                 ("state", c_vp), ("aux", c_vp), ("features", c_vp), ("docids", c_vp), ("labels", c_vp), ("pw", c_vp),
@@ -191,6 +199,15 @@ SIGNATURES = {
     "ultr_dlcm_forward": (c_i32, [ctypes.POINTER(DlcmDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "ultr_dlcm_backward": (c_i32, [ctypes.POINTER(DlcmDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
                                    c_vp]),
+    "ultr_gsf_param_count": (c_i64, [ctypes.POINTER(GsfDesc)]),
+    "ultr_gsf_param_offsets": (c_i32, [ctypes.POINTER(GsfDesc), ctypes.POINTER(c_i64)]),
+    "ultr_gsf_saved_bytes": (c_i64, [ctypes.POINTER(GsfDesc), c_i64]),
+    "ultr_gsf_score_bytes": (c_i64, [ctypes.POINTER(GsfDesc), c_i64]),
+    "ultr_gsf_workspace_bytes": (c_i64, [ctypes.POINTER(GsfDesc), c_i32, c_i32]),
+    "ultr_gsf_shuffle": (c_i32, [ctypes.c_uint64, ctypes.c_uint64, c_i32, c_i32, c_vp, c_vp]),
+    "ultr_gsf_forward": (c_i32, [ctypes.POINTER(GsfDesc), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "ultr_gsf_backward": (c_i32, [ctypes.POINTER(GsfDesc), c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp,
+                                  c_vp, c_vp]),
     "ultr_apply_update": (c_i32, [ctypes.POINTER(UpdateDesc), ctypes.POINTER(DnnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp]),
     "ultr_train_step": (c_i32, [ctypes.POINTER(StepArgs), c_vp]),

@@ -338,6 +338,11 @@ __device__ __forceinline__ uint32_t philox_word(const Philox& rng, uint32_t c0, 
   rng(c);
   return c[l & 3];
 }
+// Word 3 of the counter names the stream.  The tags live with their kernels - ULTR_QUERY_TAG / ULTR_CLICK_TAG / ULTR_SHUFFLE_TAG
+// (ultr_feed.h), ONLINE_*_TAG (ultr_online.hip), DBGD_*_TAG (ultr_dbgd.hip), NSGD_NOISE_TAG (ultr_nsgd.hip), SR_DROPOUT_TAG
+// (ultr_sr_dropout.h) - except this one, which has no header of its own: GSF's training shuffle (ultr_gsf.hip), counter
+// (list b, 0, i / 4, tag), word i % 4 for the Fisher-Yates step i.
+#define ULTR_GSF_SHUFFLE_TAG 0x47534653u
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }  // [0, 1)
 
 __device__ __forceinline__ float quad_max(float v) {  // over the 4 lanes {i, i+16, i+32, i+48}

@@ -580,7 +580,7 @@ def _setrank_draw(list_size):
 
 class StagedStepEngine(StepEngine):
     """A step issued as stage calls instead of ONE C call, for the ranking models whose forward and backward are entries of their own
-    (SetRank, DLCM): forward(train=True) -> loss -> backward -> ultr_apply_update on the flat vector (no k-major weight copy).  At
+    (SetRank, DLCM, GSF): forward(train=True) -> loss -> backward -> ultr_apply_update on the flat vector (no k-major weight copy).  At
     their size (hundreds of microseconds to milliseconds per step) the host is not on the critical path.  A subclass supplies _alloc,
     forward and backward (which leaves the sum-of-squares partials in self.bwd_ws)."""
 
@@ -734,6 +734,57 @@ class DlcmEvalEngine(EvalEngine):
 
     def forward(self, params, features, n_docs, docids):
         hip_ops.dlcm_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, work=self.work)
+        return self.scores
+
+
+class GsfStepEngine(StagedStepEngine):
+    """The step for the GSF ranking model: [ultr_gsf_shuffle] -> ultr_gsf_forward -> ultr_<loss> -> ultr_gsf_backward ->
+    ultr_grad_sumsq -> ultr_apply_update.  forward(train=True) of a model that shuffles (shape.train_shuffle) draws the step's
+    permutations from (shape.shuffle_seed, shape.next_shuffle_step()) - the key is the model's, so another batch shape continues the
+    stream - and backward() reads the same draw; every other forward runs in presented order.  One GPU: a process_group is refused."""
+
+    def __init__(self, shape, batch, list_size, device, **kw):
+        if kw.get("process_group") is not None:
+            raise NotImplementedError("GSF has no data-parallel step: train it on one GPU (process_group=None)")
+        super().__init__(shape, batch, list_size, device, **kw)
+
+    def _alloc(self, shape, device):
+        self.saved = _f32(shape.saved_bytes(self.N) // 4, device)
+        self.gsf_ws = _f32(shape.workspace_bytes(self.B, self.L) // 4, device)
+        # sum-of-squares partials of ultr_grad_sumsq / ultr_apply_update
+        self.bwd_ws = _f32((self.P + self.tail + 63) // 64 + self.P // 4096 + 16, device)
+        self.perm = torch.zeros(self.B, self.L, dtype=torch.int32, device=device)
+        self._perm = None  # the draw of the forward in flight (None: presented order)
+
+    def forward(self, params, features, n_docs, docids, scores=None, train=False):
+        scores = self.scores if scores is None else scores
+        self._perm = None
+        if train and getattr(self.shape, "train_shuffle", False):
+            hip_ops.gsf_shuffle(self.shape.shuffle_seed, self.shape.next_shuffle_step(), self.B, self.L, self.perm)
+            self._perm = self.perm
+        hip_ops.gsf_forward(self.shape, params, features, n_docs, docids, self.B, self.L, scores, perm=self._perm, saved=self.saved)
+        return scores
+
+    def backward(self, params, features, n_docs, docids):
+        hip_ops.gsf_backward(self.shape, params, features, n_docs, docids, self.B, self.L, self.saved, self.dscores, self.loss_ws,
+                             hip_ops.loss_part_count(self.B), self.gsf_ws, self.grads, perm=self._perm)
+        hip_ops.grad_sumsq(self.grads, self.P, self.L, self.bwd_ws)
+
+
+class GsfEvalEngine(EvalEngine):
+    """validation() for GSF: the scoring form of ultr_gsf_forward in presented order (no record for a backward), then the metric launch."""
+
+    def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10), metrics=("ndcg",)):
+        super().__init__(shape, batch, list_size, device, topn=topn, metrics=metrics)
+        self.work = _f32(shape.score_bytes(self.B * self.L) // 4, device)
+
+    def run(self, params, features, n_docs, docids, labels):
+        self.forward(params, features, n_docs, docids)
+        self._ndcg(labels, docids, n_docs)
+        return self.scores, self.ndcg
+
+    def forward(self, params, features, n_docs, docids):
+        hip_ops.gsf_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, work=self.work)
         return self.scores
 
 

@@ -289,6 +289,87 @@ def dlcm_backward(shape, params, features, n_docs, docids, B, L, saved, dscores,
                                        _stream()), "ultr_dlcm_backward")
 
 
+class GsfShape:
+    """Host-side geometry of one GSF model (include/ultr_hip.h: ultr_gsf_*): descriptor + flat parameter layout, the DNN's keys in the
+    DNN's order with layer 0 reading group_size * feature_size inputs and the last layer writing group_size outputs.  feature_size and
+    every hidden width must be multiples of 4 and group_size at most 8: the size queries of any other model raise UltrHipError
+    ("unsupported shape"), as the calls do; the layout is defined for every model.
+
+    The training shuffle's key rides along, as SetRankShape's dropout key does: `train_shuffle`, `shuffle_seed` (the owner of the shape
+    sets it; ranking_model.GSF captures torch.initial_seed()) and `shuffle_step`, the count of shuffled training forwards so far -
+    engines are per batch shape, cached and evicted, so the counter is the model's, shared through this object."""
+
+    def __init__(self, feature_size, hidden, activation="elu", group_size=2, train_shuffle=True):
+        self.lib = _lib.load()
+        self.feature_size, self.group_size = int(feature_size), int(group_size)
+        self.hidden = [int(h) for h in (hidden or [])]
+        self.activation = activation
+        if len(self.hidden) > _lib.ULTR_MAX_HIDDEN:
+            raise ValueError("at most %d hidden layers are supported" % _lib.ULTR_MAX_HIDDEN)
+        if activation not in _lib.ACT:
+            raise ValueError("activation_func must be one of %s (got %r)" % (sorted(_lib.ACT), activation))
+        d = self.desc = _lib.GsfDesc()
+        d.feature_size, d.group_size, d.n_hidden, d.activation = self.feature_size, self.group_size, len(self.hidden), _lib.ACT[activation]
+        for i, h in enumerate(self.hidden):
+            d.hidden[i] = h
+        self.n_params = int(self.lib.ultr_gsf_param_count(ctypes.byref(d)))
+        if self.n_params <= 0:
+            raise ValueError("bad GSF description (feature_size, group_size and the hidden widths must be positive)")
+        nl = len(self.hidden) + 1
+        offs = (ctypes.c_int64 * (4 * nl))()
+        check(self.lib.ultr_gsf_param_offsets(ctypes.byref(d), offs), "ultr_gsf_param_offsets")
+        self.offsets = list(offs)
+        dims, k = [], self.feature_size * self.group_size
+        for m in self.hidden + [self.group_size]:
+            dims.append((k, m))
+            k = m
+        self.dims = dims
+        self.train_shuffle, self.shuffle_seed, self.shuffle_step = bool(train_shuffle), 0, 0
+
+    layout = DnnShape.layout
+
+    def _bytes(self, fn, *args):
+        n = int(getattr(self.lib, fn)(ctypes.byref(self.desc), *args))
+        check(min(n, 0), fn)
+        return n
+
+    def saved_bytes(self, n_rows):
+        return self._bytes("ultr_gsf_saved_bytes", int(n_rows))
+
+    def score_bytes(self, n_rows):
+        """Bytes of the scoring form's buffer: the layer outputs alternate between two buffers, nothing is kept for a backward."""
+        return self._bytes("ultr_gsf_score_bytes", int(n_rows))
+
+    def workspace_bytes(self, B, L):
+        return self._bytes("ultr_gsf_workspace_bytes", int(B), int(L))
+
+    def next_shuffle_step(self):
+        """The step number of the shuffled training forward about to run; counts it."""
+        step = self.shuffle_step
+        self.shuffle_step = step + 1
+        return step
+
+
+def gsf_shuffle(seed, step, B, L, perm):
+    """perm [B, L] int32: the Philox Fisher-Yates draw of (seed, step), one permutation of 0 .. L - 1 per list."""
+    _req(perm, torch.int32, "perm")
+    check(_lib.load().ultr_gsf_shuffle(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(B), int(L), _p(perm), _stream()),
+          "ultr_gsf_shuffle")
+
+
+def gsf_forward(shape, params, features, n_docs, docids, B, L, scores, perm=None, saved=None, work=None):
+    """perm [B, L] int32 or None (the identity).  saved: the training form; saved None: the scoring form on `work` (shape.score_bytes) -
+    the same scores bit for bit."""
+    check(shape.lib.ultr_gsf_forward(ctypes.byref(shape.desc), _p(params), _p(features) if n_docs > 0 else None, int(n_docs), _p(docids),
+                                     _p(perm), int(B), int(L), _p(scores), _p(saved), _p(work), _stream()), "ultr_gsf_forward")
+
+
+def gsf_backward(shape, params, features, n_docs, docids, B, L, saved, dscores, loss_ws, n_loss_parts, ws, grads, perm=None):
+    check(shape.lib.ultr_gsf_backward(ctypes.byref(shape.desc), _p(params), _p(features) if n_docs > 0 else None, int(n_docs), _p(docids),
+                                      _p(perm), int(B), int(L), _p(saved), _p(dscores), _p(loss_ws), int(n_loss_parts), _p(ws), _p(grads),
+                                      _stream()), "ultr_gsf_backward")
+
+
 def tail_floats(L):
     return int(_lib.load().ultr_step_tail_floats(int(L)))
 
