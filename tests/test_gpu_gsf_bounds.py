@@ -35,19 +35,24 @@ def bits(t):
 
 @pytest.mark.parametrize("k,algo", [(0, "softmax"), (4, "softmax"), (0, "dla"), (0, "lambdarank")])
 def test_two_guarded_steps_are_two_plain_steps(k, algo):
+    two_guarded_steps_are_two_plain_steps(R.SHAPES[k], "elu", k, algo)
+
+
+def two_guarded_steps_are_two_plain_steps(dims, act, k, algo):
+    """dims = (B, L, F, m, hidden); k seeds the inputs, the labels and the parameters."""
     from ultra_pytorch_amd import engine, hip_ops
-    B, L, F, m, hidden = R.SHAPES[k]
+    B, L, F, m, hidden = dims
     d = torch.device("cuda")
     feats, ids, _ = R.make_inputs(B, L, F, seed=k)
     g = torch.Generator().manual_seed(77 + k)
     labels = (torch.rand(L, B, generator=g) < 0.4).float().to(d)
-    n_params = hip_ops.GsfShape(F, hidden, "elu", m).n_params
+    n_params = hip_ops.GsfShape(F, hidden, act, m).n_params
     p0 = (0.2 * torch.randn(n_params, generator=g)).to(d)
     aux0 = {"softmax": None, "dla": 0.1 * torch.randn(L + 1, generator=g), "lambdarank": torch.ones(2 * L)}[algo]
     x, docids = feats.to(d), torch.as_tensor(ids).to(d)
     runs = []
     for guarded in (False, True):
-        shape = hip_ops.GsfShape(F, hidden, "elu", m)  # a fresh shuffle stream per run: the same draws
+        shape = hip_ops.GsfShape(F, hidden, act, m)  # a fresh shuffle stream per run: the same draws
         shape.shuffle_seed = 5
         eng = engine.GsfStepEngine(shape, B, L, d, algo=algo)
         arena = guard(eng, STEP_BUFFERS) if guarded else None

@@ -156,7 +156,7 @@ struct AAffine {
 };
 
 // ---- epilogues: called with the global row, the first of four consecutive columns (all < N unless noted) -------------
-// y = act(c + bias); act: -1 none, 0 elu, 1 relu.  n_valid = columns of this piece that exist (1..4)
+// y = act(c + bias); act: -1 none, 0 elu, 1 relu, 2 tanh, 3 sigmoid.  n_valid = columns of this piece that exist (1..4)
 struct EBiasAct {
   float* y;
   const float* bias;  // may be nullptr
