@@ -289,6 +289,39 @@ int ultr_prs_loss_pw(const float* scores, const float* labels, const float* ipw_
 int ultr_pdgd_loss(const float* scores, const float* labels, const int32_t* docids, int64_t n_docs, float tau,
                    int32_t cutoff, int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
 
+/* ---- long lists: PairDebias, LambdaRank, PRSrank beyond 585 / 531 / 952 documents (additive within ABI 8) ----
+ * The same losses from kernels that split the OWNED positions over the workgroup's 16 waves (each lane walks every partner, its
+ * sums stay in registers), so their LDS is O(list_size).  Arguments, outputs, the step tail and the ULTR_E_BADARG rules are those
+ * of the short entries above; a position's sums are one ascending fp32 chain over the partners, so the results agree with the
+ * short kernels' to rounding, not bit for bit.  Every list_size from 1 up to the bound is accepted.  One workgroup and one tail
+ * partial per list (ultr_loss_part_count, ultr_loss_workspace_bytes as before); no atomics, the same inputs give the same bits.
+ * ultr_train_step takes these for a list the short kernel refuses, and only for such a list (decided before anything is launched).
+ *
+ * Dynamic LDS in bytes of the long kernel of `algo` at list_size, read from the layout the kernel carves its LDS with (host-only).
+ * ULTR_E_UNSUPPORTED beyond 160 KiB; ULTR_E_BADARG: list_size <= 0, an algorithm other than ULTR_ALGO_PAIRDEBIAS,
+ * ULTR_ALGO_LAMBDARANK, ULTR_ALGO_PRS. */
+int64_t ultr_loss_long_lds_bytes(int32_t algo, int32_t list_size);
+/* the longest list the long kernel of `algo` accepts (6823 / 3149 / 3721); ULTR_E_BADARG for an algorithm without one */
+int32_t ultr_loss_long_max_list(int32_t algo);
+/* ultr_pairdebias_loss for long lists.
+ * list_size up to 6823 (160 KiB of LDS, ultr_loss_long_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
+int ultr_pairdebias_loss_long(const float* scores, const float* labels, const float* t_plus, const float* t_minus,
+                              int32_t batch, int32_t list_size, int32_t batch_total, float* dscores, void* loss_ws,
+                              void* stream);
+/* ultr_lambdarank_loss for long lists.
+ * list_size up to 3149 (160 KiB of LDS, ultr_loss_long_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
+int ultr_lambdarank_loss_long(const float* scores, const float* labels, const float* t_plus, const float* t_minus,
+                              float sigma, int32_t batch, int32_t list_size, float* dscores, void* loss_ws,
+                              void* stream);
+/* ultr_prs_loss for long lists.
+ * list_size up to 3721 (160 KiB of LDS, ultr_loss_long_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
+int ultr_prs_loss_long(const float* scores, const float* labels, const float* ipw_table, int32_t n_ipw, float sigma,
+                       int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
+/* ultr_prs_loss_pw for long lists.
+ * list_size up to 3721 (160 KiB of LDS, ultr_loss_long_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched. */
+int ultr_prs_loss_pw_long(const float* scores, const float* labels, const float* ipw_bl, float sigma, int32_t batch,
+                          int32_t list_size, float* dscores, void* loss_ws, void* stream);
+
 /* ---- next row 8f.1: the SetRank ranking model --------------------------------------------
  * Replaces SetRank.build / Encoder.forward (ranking_model/SetRank.py:143-156, 229-255) and its autograd
  * backward: input LayerNorm (eps 1e-6) -> FFN(F -> dff -> d_model) -> num_layers x [multi-head self-attention

@@ -174,6 +174,12 @@ SIGNATURES = {
     "ultr_prs_loss": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_prs_loss_pw": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_pdgd_loss": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ultr_loss_long_lds_bytes": (c_i64, [c_i32, c_i32]),
+    "ultr_loss_long_max_list": (c_i32, [c_i32]),
+    "ultr_pairdebias_loss_long": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ultr_lambdarank_loss_long": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ultr_prs_loss_long": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ultr_prs_loss_pw_long": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_regem_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "ultr_setrank_param_count": (c_i64, [ctypes.POINTER(SetRankDesc)]),
     "ultr_setrank_saved_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),

@@ -5,6 +5,8 @@
 //   * the flat pieces of the pair-walk kernels (pairdebias_kernel, lambdarank_kernel, prs_loss_kernel): indices and slice
 //     bounds, staging, rank by counting, the fixed-order fold of the slice partials, the scatter, the workgroup tail store.
 // The kernels call the pieces in sequence and keep their own per-pair bodies.
+//   * the layouts of the three long-list pair-walk kernels (ultr_loss_long.hip) and loss_route, the host rule that hands a list to them:
+//     only a list the short kernel's layout refuses (ultr_step.hip decides with it before the forward is launched).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -128,6 +130,86 @@ struct PdgdLds : LdsCarve {  // list_size <= PDGD_MAX_L (the entry refuses beyon
   int64_t bytes = end();
   __host__ __device__ explicit PdgdLds(int L_) : LdsCarve(L_) {}
 };
+
+// The long-list kernels (ultr_loss_long.hip): the workgroup's LOSS_LONG_WAVES waves split the OWNED positions, each lane walks every
+// partner, so the sums per position stay in registers and no [LOSS_JW][L][NV] array exists: O(L) floats of LDS.  One list per workgroup.
+#define LOSS_LONG_WAVES 16
+#define LOSS_LONG_THREADS (LOSS_LONG_WAVES * 64)
+// A position's sums are formed in two levels, both ascending: LOSS_LONG_CHUNK consecutive partners into a chunk sum, the chunk sums
+// into the position's sum - the rounding of an fp32 chain grows with its length: 32 + L / 32 additions deep instead of L.
+#define LOSS_LONG_CHUNK 32
+static_assert(LPW == 1, "the long-list loss kernels own one list per workgroup: one tail partial per list");
+
+struct PairDebiasLongLds : LdsCarve {  // list_size <= 6823
+  static constexpr int64_t limit = LOSS_LDS_MAX;
+  int tail = take(ultr_tail_len(L));  // [tail]
+  int s = take(L);                    // [L] scores
+  int c = take(L);                    // [L] clicks
+  int rtp = take(L);                  // [L] 1 / t_plus
+  int rtm = take(L);                  // [L] 1 / t_minus
+  int red = take(LOSS_LONG_WAVES);    // [LOSS_LONG_WAVES] one partial per wave of a workgroup-wide sum
+  int64_t bytes = end();
+  __host__ __device__ explicit PairDebiasLongLds(int L_) : LdsCarve(L_) {}
+};
+
+struct LambdaRankLongLds : SortedListLds {  // list_size <= 3149
+  static constexpr int64_t limit = LOSS_LDS_MAX;
+  int tp = take(L);                 // [L] t_plus
+  int tm = take(L);                 // [L] t_minus
+  int rtp = take(L);                // [L] 1 / t_plus
+  int rtm = take(L);                // [L] 1 / t_minus
+  int d = take(L);                  // [L] discount 1 / log2(rank + 2)
+  int pos = take(L);                // [L] int: sorted position of original index
+  int red = take(LOSS_LONG_WAVES);  // [LOSS_LONG_WAVES]
+  int64_t bytes = end();
+  __host__ __device__ explicit LambdaRankLongLds(int L_) : SortedListLds(L_) {}
+};
+
+struct PrsLongLds : SortedListLds {  // list_size <= 3721
+  static constexpr int64_t limit = LOSS_LDS_MAX;
+  int ipw = take(L);                // [L] ipw of the presentation position, in score order
+  int pw = take(L);                 // [L] pw = 1 / ipw (0 where ipw == 0), in score order
+  int d = take(L);                  // [L] discount 1 / log2(rank + 2)
+  int pos = take(L);                // [L] int: sorted position of original index
+  int red = take(LOSS_LONG_WAVES);  // [LOSS_LONG_WAVES]
+  int64_t bytes = end();
+  __host__ __device__ explicit PrsLongLds(int L_) : SortedListLds(L_) {}
+};
+
+// ------------------------------------------------------------------------------------------------
+// routing (host): a list the short pair-walk kernel of `algo` takes runs that kernel; only a list it refuses goes to the long one
+// ------------------------------------------------------------------------------------------------
+enum LossRoute { LOSS_ROUTE_SHORT = 0, LOSS_ROUTE_LONG = 1 };
+
+// dynamic LDS of the long kernel of `algo` at L, ULTR_E_UNSUPPORTED beyond its limit, ULTR_E_BADARG where `algo` has none
+static inline int64_t loss_long_bytes(int algo, int L) {
+  if (L <= 0) return ULTR_E_BADARG;
+  int64_t n;
+  switch (algo) {
+    case ULTR_ALGO_PAIRDEBIAS: n = PairDebiasLongLds(L).bytes; break;
+    case ULTR_ALGO_LAMBDARANK: n = LambdaRankLongLds(L).bytes; break;
+    case ULTR_ALGO_PRS: n = PrsLongLds(L).bytes; break;
+    default: return ULTR_E_BADARG;
+  }
+  return n > LOSS_LDS_MAX ? ULTR_E_UNSUPPORTED : n;
+}
+
+// "the short layout of `algo` does not fit at L": false for an algorithm without a long kernel (its short entry answers for itself)
+static inline bool loss_short_refuses(int algo, int L) {
+  if (L <= 0) return false;
+  switch (algo) {
+    case ULTR_ALGO_PAIRDEBIAS: return PairDebiasLds(L).bytes > PairDebiasLds::limit;
+    case ULTR_ALGO_LAMBDARANK: return LambdaRankLds(L).bytes > LambdaRankLds::limit;
+    case ULTR_ALGO_PRS: return PrsLds(L).bytes > PrsLds::limit;
+    default: return false;
+  }
+}
+
+// LOSS_ROUTE_SHORT, LOSS_ROUTE_LONG, or ULTR_E_UNSUPPORTED for a list neither kernel takes
+static inline int loss_route(int algo, int L) {
+  if (!loss_short_refuses(algo, L)) return LOSS_ROUTE_SHORT;
+  return loss_long_bytes(algo, L) >= 0 ? LOSS_ROUTE_LONG : ULTR_E_UNSUPPORTED;
+}
 
 // ------------------------------------------------------------------------------------------------
 // the one launcher: ultr_loss_parts(batch) workgroups of `threads`, under the ULTR_K_LOSS profiling scope

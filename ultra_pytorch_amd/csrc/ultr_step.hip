@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/ultr_hip.h"
+#include "ultr_listloss.h"
 #include "ultr_plan.h"
 #include "ultr_prof.h"
 
@@ -54,6 +55,11 @@ int ultr_train_step_ctx(const ultr_step_args* a, StepCtx* ctx, void* stream) {
   ctx->comm = dp ? a->comm : nullptr;
   ctx->comm_step = a->comm_step;
   ctx->early_dp = {early_dp ? u->host_scalars : nullptr, u->seq, u->algo, u->ranker_loss_weight};
+  // pair-walk losses: the short kernel for every list it takes, the long one only for a list it refuses (loss_route,
+  // ultr_listloss.h) - decided here, so that a list neither takes is refused before the forward is launched
+  const int route = loss_route(a->upd->algo, a->list_size);
+  if (route < 0) return route;
+  const bool long_list = route == LOSS_ROUTE_LONG;
   int rc;
   if (a->upd->algo == ULTR_ALGO_SOFTMAX) {
     // small batches (NA / IPW): forward + loss + backward as ONE launch when the shape qualifies
@@ -81,19 +87,22 @@ int ultr_train_step_ctx(const ultr_step_args* a, StepCtx* ctx, void* stream) {
                          a->loss_ws, stream);
       break;
     case ULTR_ALGO_PAIRDEBIAS:
-      rc = ultr_pairdebias_loss(a->scores, a->labels, a->aux, a->aux ? a->aux + a->list_size : nullptr, a->batch,
-                                a->list_size, a->batch_total > 0 ? a->batch_total : a->batch, a->dscores, a->loss_ws, stream);
+      rc = (long_list ? ultr_pairdebias_loss_long : ultr_pairdebias_loss)(
+          a->scores, a->labels, a->aux, a->aux ? a->aux + a->list_size : nullptr, a->batch, a->list_size,
+          a->batch_total > 0 ? a->batch_total : a->batch, a->dscores, a->loss_ws, stream);
       break;
     case ULTR_ALGO_LAMBDARANK:
-      rc = ultr_lambdarank_loss(a->scores, a->labels, a->aux, a->aux ? a->aux + a->list_size : nullptr, a->sigma, a->batch,
-                                a->list_size, a->dscores, a->loss_ws, stream);
+      rc = (long_list ? ultr_lambdarank_loss_long : ultr_lambdarank_loss)(
+          a->scores, a->labels, a->aux, a->aux ? a->aux + a->list_size : nullptr, a->sigma, a->batch, a->list_size, a->dscores,
+          a->loss_ws, stream);
       break;
     case ULTR_ALGO_PRS:
       // pw: a weight per list entry (an estimator that reads the list's clicks) instead of the position table
       rc = a->pw != nullptr
-               ? ultr_prs_loss_pw(a->scores, a->labels, a->pw, a->sigma, a->batch, a->list_size, a->dscores, a->loss_ws, stream)
-               : ultr_prs_loss(a->scores, a->labels, a->ipw_table, a->n_ipw, a->sigma, a->batch, a->list_size, a->dscores,
-                               a->loss_ws, stream);
+               ? (long_list ? ultr_prs_loss_pw_long : ultr_prs_loss_pw)(a->scores, a->labels, a->pw, a->sigma, a->batch, a->list_size,
+                                                                        a->dscores, a->loss_ws, stream)
+               : (long_list ? ultr_prs_loss_long : ultr_prs_loss)(a->scores, a->labels, a->ipw_table, a->n_ipw, a->sigma, a->batch,
+                                                                  a->list_size, a->dscores, a->loss_ws, stream);
       break;
     case ULTR_ALGO_PDGD:
       rc = ultr_pdgd_loss(a->scores, a->labels, a->docids, a->n_docs, a->sigma, a->n_ipw, a->batch, a->list_size, a->dscores,

@@ -108,6 +108,7 @@ class StepEngine:
         u.seq = 0
         self.udesc = u
         self._args = None
+        self._loss_route = None  # "short" | "long": which loss kernel the pair-walk algorithms run at this list size (_loss_is_long)
         self._cached = (None,) * 8  # the tensor objects behind the pointer fields of self._args (train_step)
         self.next_click_source = None  # a DeviceClickFeed (set per step by the plugin algorithm): its next batch is drawn behind the step
 
@@ -129,17 +130,23 @@ class StepEngine:
             hip_ops.softmax_ce(self.scores, labels, B, L, self.dscores, self.loss_ws, pw=pw, ipw_table=ipw_table)
         elif self.algo == "dla":
             hip_ops.dla_loss(self.scores, labels, aux, self.l2p, B, L, self.dscores, self.loss_ws)
-        elif self.algo == "pairdebias":
-            hip_ops.pairdebias_loss(self.scores, labels, aux[:L], aux[L:], B, L, self.batch_total, self.dscores, self.loss_ws)
-        elif self.algo == "lambdarank":
-            hip_ops.lambdarank_loss(self.scores, labels, aux[:L], aux[L:], self.sigma, B, L, self.dscores, self.loss_ws)
-        elif self.algo == "prs":
-            if pw is not None:  # a weight per list entry [B, L] (hip_ops.history_pw) instead of the position table
-                hip_ops.prs_loss_pw(self.scores, labels, pw, self.sigma, B, L, self.dscores, self.loss_ws)
+        elif self.algo in ("pairdebias", "lambdarank", "prs"):
+            # the short kernel for every list it takes, the long one only for a list it refuses (the rule of ultr_train_step)
+            long_list = self._loss_is_long()
+            if self.algo == "pairdebias":
+                fn = hip_ops.pairdebias_loss_long if long_list else hip_ops.pairdebias_loss
+                fn(self.scores, labels, aux[:L], aux[L:], B, L, self.batch_total, self.dscores, self.loss_ws)
+            elif self.algo == "lambdarank":
+                fn = hip_ops.lambdarank_loss_long if long_list else hip_ops.lambdarank_loss
+                fn(self.scores, labels, aux[:L], aux[L:], self.sigma, B, L, self.dscores, self.loss_ws)
+            elif pw is not None:  # a weight per list entry [B, L] (hip_ops.history_pw) instead of the position table
+                fn = hip_ops.prs_loss_pw_long if long_list else hip_ops.prs_loss_pw
+                fn(self.scores, labels, pw, self.sigma, B, L, self.dscores, self.loss_ws)
             elif ipw_table is None:
                 raise ValueError("PRSrank's loss needs the IPW table (ipw_table=) or per-entry weights (pw=)")
             else:
-                hip_ops.prs_loss(self.scores, labels, ipw_table, self.sigma, B, L, self.dscores, self.loss_ws)
+                fn = hip_ops.prs_loss_long if long_list else hip_ops.prs_loss
+                fn(self.scores, labels, ipw_table, self.sigma, B, L, self.dscores, self.loss_ws)
         elif self.algo == "pdgd":
             if docids is None or n_docs is None:
                 raise ValueError("PDGD's loss needs the docids and n_docs (its PADs)")
@@ -150,6 +157,12 @@ class StepEngine:
             self.rng_step += 1
         else:
             raise ValueError(self.algo)
+
+    def _loss_is_long(self):
+        """hip_ops.loss_route of this engine's algorithm and list size, asked once (raises for a list neither kernel takes)."""
+        if self._loss_route is None:
+            self._loss_route = hip_ops.loss_route(ALGOS[self.algo], self.L)
+        return self._loss_route == "long"
 
     def backward(self, params, features, n_docs, docids):
         hip_ops.dnn_backward(self.shape, params, features, n_docs, docids, self.B, self.L, self.saved, self.dscores,

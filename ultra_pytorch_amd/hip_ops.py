@@ -391,6 +391,34 @@ def loss_lds_bytes(algo, L):
     return n
 
 
+def loss_long_lds_bytes(algo, L):
+    """Dynamic LDS in bytes the LONG-list loss kernel of `algo` (ALGO_PAIRDEBIAS, ALGO_LAMBDARANK, ALGO_PRS) requests at list size L
+    (ultr_loss_long_lds_bytes).  Host-only.  Raises UltrHipError beyond its bound, or for an algorithm without a long kernel."""
+    n = int(_lib.load().ultr_loss_long_lds_bytes(int(algo), int(L)))
+    check(min(n, 0), "ultr_loss_long_lds_bytes")
+    return n
+
+
+def loss_long_max_list(algo):
+    """The longest list the long-list loss kernel of `algo` accepts (ultr_loss_long_max_list).  Host-only."""
+    n = int(_lib.load().ultr_loss_long_max_list(int(algo)))
+    check(min(n, 0), "ultr_loss_long_max_list")
+    return n
+
+
+def loss_route(algo, L):
+    """Which stand-alone loss kernel of `algo` (a _lib.ALGO_* id) a list of L documents runs: "short" for every list the short
+    kernel takes, "long" only for a list it refuses and the long kernel (PairDebias, LambdaRank, PRSrank) takes.  Raises
+    UltrHipError where neither does.  The rule ultr_train_step follows, read from the same LDS layouts; host-only."""
+    lib = _lib.load()
+    n = int(lib.ultr_loss_lds_bytes(int(algo), int(L)))
+    if n >= 0:
+        return "short"
+    if n == -2 and int(lib.ultr_loss_long_lds_bytes(int(algo), int(L))) >= 0:  # (ULTR_E_UNSUPPORTED: the short layout does not fit)
+        return "long"
+    check(n, "ultr_loss_lds_bytes")
+
+
 H3_KNOBS = ("ULTR_FB_H3", "ULTR_FWD_H3", "ULTR_BWD_H3")
 SR_H3_KNOBS = ("ULTR_SR_H3",)
 
@@ -554,6 +582,27 @@ def prs_loss_pw(scores, labels, ipw_bl, sigma, B, L, dscores, loss_ws):
     """PRSrank with a weight per list entry: ipw_bl [B, L] (presentation order) instead of the position table (history_pw)."""
     check(_lib.load().ultr_prs_loss_pw(_p(scores), _p(labels), _p(ipw_bl), float(sigma), int(B), int(L), _p(dscores), _p(loss_ws),
                                        _stream()), "ultr_prs_loss_pw")
+
+
+# The long-list kernels (csrc/ultr_loss_long.hip): the arguments of the short wrappers above, every L from 1 up to loss_long_max_list.
+def pairdebias_loss_long(scores, labels, t_plus, t_minus, B, L, batch_total, dscores, loss_ws):
+    check(_lib.load().ultr_pairdebias_loss_long(_p(scores), _p(labels), _p(t_plus), _p(t_minus), int(B), int(L),
+                                                int(batch_total), _p(dscores), _p(loss_ws), _stream()), "ultr_pairdebias_loss_long")
+
+
+def lambdarank_loss_long(scores, labels, t_plus, t_minus, sigma, B, L, dscores, loss_ws):
+    check(_lib.load().ultr_lambdarank_loss_long(_p(scores), _p(labels), _p(t_plus), _p(t_minus), float(sigma), int(B), int(L),
+                                                _p(dscores), _p(loss_ws), _stream()), "ultr_lambdarank_loss_long")
+
+
+def prs_loss_long(scores, labels, ipw_table, sigma, B, L, dscores, loss_ws):
+    check(_lib.load().ultr_prs_loss_long(_p(scores), _p(labels), _p(ipw_table), int(ipw_table.numel()), float(sigma), int(B), int(L),
+                                         _p(dscores), _p(loss_ws), _stream()), "ultr_prs_loss_long")
+
+
+def prs_loss_pw_long(scores, labels, ipw_bl, sigma, B, L, dscores, loss_ws):
+    check(_lib.load().ultr_prs_loss_pw_long(_p(scores), _p(labels), _p(ipw_bl), float(sigma), int(B), int(L), _p(dscores), _p(loss_ws),
+                                            _stream()), "ultr_prs_loss_pw_long")
 
 
 def pdgd_loss(scores, labels, docids, n_docs, tau, cutoff, B, L, dscores, loss_ws):
