@@ -520,17 +520,25 @@ enum ultr_algo { ULTR_ALGO_SOFTMAX = 0, ULTR_ALGO_DLA = 1, ULTR_ALGO_PAIRDEBIAS 
                  ULTR_ALGO_PRS = 5, ULTR_ALGO_PDGD = 6,
                  /* DBGD / MGD: grads from ultr_dbgd_grad_args, loss in the step tail, D = 1 (no l2_loss) */
                  ULTR_ALGO_DBGD = 7 };
-enum ultr_opt { ULTR_OPT_ADAGRAD = 0, ULTR_OPT_SGD = 1 };
+/* ULTR_OPT_ADAM: torch.optim.Adam with its defaults (no weight decay, no amsgrad), applied to the gradient Adagrad / SGD get - after
+ * the 1 / D scaling, the l2_loss term and the clip.  For step t = 1, 2, ...:
+ *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ * The moments persist for every algorithm, DLA included (its Adagrad is stateless only because the reference rebuilds its optimizers
+ * every step); DLA's propensity parameters aux[0 .. L] keep moments of their own and step with propensity_learning_rate. */
+enum ultr_opt { ULTR_OPT_ADAGRAD = 0, ULTR_OPT_SGD = 1, ULTR_OPT_ADAM = 2 };
+#define ULTR_ADAM_BETA1 0.9
+#define ULTR_ADAM_BETA2 0.999
+#define ULTR_ADAM_EPS 1e-8
 
 typedef struct ultr_update_desc {
   int32_t algo;            /* ultr_algo */
-  int32_t optimizer;       /* ultr_opt (grad_strategy 'ada' / 'sgd') */
+  int32_t optimizer;       /* ultr_opt (grad_strategy 'ada' / 'sgd' / 'adam') */
   int32_t list_size;       /* L */
   int32_t logits_to_prob;  /* DLA only */
   int64_t n_params;        /* P */
   float learning_rate;
   float max_gradient_norm; /* <= 0 disables clipping */
-  float adagrad_eps;       /* 1e-10 */
+  float adagrad_eps;       /* 1e-10; ULTR_OPT_ADAM: Adam's eps (ULTR_ADAM_EPS) */
   float ranker_loss_weight;     /* DLA */
   float propensity_learning_rate; /* DLA */
   float em_step_size;      /* PairDebias / LambdaRank */
@@ -554,7 +562,9 @@ typedef struct ultr_update_desc {
   const uint32_t* guard;
   float* host_scalars;
   uint32_t seq;
-  uint32_t pad_;
+  /* (the four bytes that were reserved as pad_) ULTR_OPT_ADAM: the step count t >= 1 of this update, counted by the HOST beside the
+   *   state (one count per state vector, whatever workspace or batch shape a step runs in); ignored by Adagrad and SGD */
+  uint32_t adam_t;
   /* ABI 6 - range_flag: optional device word of ULTR_H3_FLAG_* bits raised by whatever builds split-half (fp16 hi / lo) weight
    *   planes for the caller's model; block 0 of the update reports them in host_scalars[8] as ULTR_STATUS_H3_NEAR / _RANGE.
    *   ultr_train_step / ultr_apply_update with `wt` find the DNN's own word themselves (NULL is fine); a SetRank caller passes
@@ -562,8 +572,14 @@ typedef struct ultr_update_desc {
   const uint32_t* range_flag;
 } ultr_update_desc;
 
-/* params/state [P] updated in place; grads = the buffer ultr_dnn_backward filled (possibly
- * all-reduced).  aux = prop_params[L+1] (DLA) or [t_plus(L) | t_minus(L)] (PairDebias /
+/* floats of `state` for this descriptor (host-only; reads algo, optimizer, list_size, n_params): SGD 0; Adagrad P; Adam 2 P as
+ * m[P] | v[P], and for DLA 2 (L + 1) more behind them, m_aux[L + 1] | v_aux[L + 1] (the propensity parameters' moments).  -1 on a
+ * bad descriptor.  A fresh state is all zeros. */
+int64_t ultr_opt_state_floats(const ultr_update_desc* u);
+
+/* params/state [P] (ultr_opt_state_floats) updated in place; grads = the buffer ultr_dnn_backward filled (possibly
+ * all-reduced).  ULTR_OPT_ADAM: state == NULL or adam_t == 0 is ULTR_E_BADARG (here and in ultr_train_step, before anything is
+ * launched), as is an optimizer outside ultr_opt.  aux = prop_params[L+1] (DLA) or [t_plus(L) | t_minus(L)] (PairDebias /
  * LambdaRank), updated in place; NULL for SOFTMAX and PRS.  d + wt (both may be NULL): keep the k-major weight copy
  * in sync with the updated parameters.  bwd_ws = the workspace ultr_dnn_backward (or
  * ultr_grad_sumsq) left the sum-of-squares partials in.

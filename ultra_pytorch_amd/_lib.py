@@ -14,7 +14,8 @@ COMM_HANDLE_BYTES, COMM_MAX_WORLD = 64, 8
 ACT = {"elu": 0, "relu": 1, "tanh": 2, "sigmoid": 3}  # base_ranking_model.py:63-69 ("selu" raises in the reference)
 ATTN_DTYPE = {"fp32": 0, "fp16": 1}
 ALGO_SOFTMAX, ALGO_DLA, ALGO_PAIRDEBIAS, ALGO_LAMBDARANK, ALGO_REGEM, ALGO_PRS, ALGO_PDGD, ALGO_DBGD = 0, 1, 2, 3, 4, 5, 6, 7
-OPT_ADAGRAD, OPT_SGD = 0, 1
+OPT_ADAGRAD, OPT_SGD, OPT_ADAM = 0, 1, 2
+ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-8  # include/ultr_hip.h: ULTR_ADAM_*
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -43,7 +44,7 @@ class UpdateDesc(ctypes.Structure):
                 ("n_params", c_i64), ("learning_rate", c_f32), ("max_gradient_norm", c_f32), ("adagrad_eps", c_f32),
                 ("ranker_loss_weight", c_f32), ("propensity_learning_rate", c_f32), ("em_step_size", c_f32),
                 ("regulation_p", c_f32), ("l2_loss", c_f32), ("guard", c_vp), ("host_scalars", c_vp),
-                ("seq", ctypes.c_uint32), ("pad_", ctypes.c_uint32), ("range_flag", c_vp)]
+                ("seq", ctypes.c_uint32), ("adam_t", ctypes.c_uint32), ("range_flag", c_vp)]
 
 
 class ClickArgs(ctypes.Structure):  # ultr_click_args (ABI 7)
@@ -216,6 +217,7 @@ SIGNATURES = {
                                   c_vp, c_vp]),
     "ultr_apply_update": (c_i32, [ctypes.POINTER(UpdateDesc), ctypes.POINTER(DnnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp]),
+    "ultr_opt_state_floats": (c_i64, [ctypes.POINTER(UpdateDesc)]),
     "ultr_train_step": (c_i32, [ctypes.POINTER(StepArgs), c_vp]),
     "ultr_click_batch": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint64,
                                  c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

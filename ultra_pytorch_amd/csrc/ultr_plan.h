@@ -306,6 +306,9 @@ int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const f
 // ultr_update.hip: ultr_apply_update with the step's level-2 partials and its waiting draw (*rider, cleared when the launch took it)
 int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state, const float* grads,
                          float* aux, const void* bwd_ws, float* scalars_out, int nsq2, const ultr_click_args** rider, void* stream);
+// ultr_update.hip: what the update launch would refuse about the optimizer (a value outside ultr_opt; Adam without state or with
+// adam_t == 0) - ultr_train_step asks before its first launch
+int ultr_update_check_opt(const ultr_update_desc* u, const float* state);
 
 #define ULTR_TAIL_FIXED 4
 __host__ __device__ static inline int64_t ultr_tail_len(int L) { return ULTR_TAIL_FIXED + 2 * (int64_t)L; }

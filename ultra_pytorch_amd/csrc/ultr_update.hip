@@ -55,6 +55,37 @@ __device__ __forceinline__ float opt_step(float p, float g, float* st, int opt, 
   return p - lr * (g / (sqrtf(s) + eps));
 }
 
+// ULTR_OPT_ADAM.  The bias corrections depend on the step count alone, so the HOST forms them, in double (adam_corr): a float32
+// pow(b2, t) in every thread would cost more than the rest of the step and lose digits as t grows.
+//   step  = lr / (1 - b1^t)   (step_aux: the same with propensity_learning_rate, for DLA's aux)
+//   rsq2  = 1 / sqrt(1 - b2^t)
+// The kernels are instantiated per optimizer class; the Adagrad / SGD instantiation carries an empty OptArgs.
+template <bool ADAM>
+struct OptArgs {};
+template <>
+struct OptArgs<true> {
+  float step, step_aux, rsq2;
+};
+static OptArgs<true> adam_corr(const ultr_update_desc& u) {
+  const double t = (double)u.adam_t;
+  const double bc1 = 1.0 - pow(ULTR_ADAM_BETA1, t), bc2 = 1.0 - pow(ULTR_ADAM_BETA2, t);
+  OptArgs<true> oa;
+  oa.step = (float)((double)u.learning_rate / bc1);
+  oa.step_aux = (float)((double)u.propensity_learning_rate / bc1);
+  oa.rsq2 = (float)(1.0 / sqrt(bc2));
+  return oa;
+}
+// torch.optim.Adam (weight_decay 0, amsgrad off): m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g;
+// p -= step * m / (sqrt(v) / sqrt(1 - b2^t) + eps).  g == 0 on fresh moments: m / eps = 0, p stays.
+__device__ __forceinline__ float adam_step(float p, float g, float* m, float* v, float step, float rsq2, float eps) {
+  const float b1 = (float)ULTR_ADAM_BETA1, b2 = (float)ULTR_ADAM_BETA2;
+  const float mn = b1 * *m + (float)(1.0 - ULTR_ADAM_BETA1) * g;
+  const float vn = b2 * *v + (float)(1.0 - ULTR_ADAM_BETA2) * (g * g);
+  *m = mn;
+  *v = vn;
+  return p - step * (mn / (sqrtf(vn) * rsq2 + eps));
+}
+
 // Step report into HOST-mapped pinned memory (ultr_update_desc::host_scalars): eight scalars + the guard word, waited for
 // (the stores are acknowledged by the host bridge), THEN the sequence number the host spins on - what loss.item() costs
 // becomes one posted PCIe write instead of a stream synchronisation and a device-to-host copy.
@@ -131,12 +162,15 @@ __global__ __launch_bounds__(1024) void l2_sums_kernel(const float* __restrict__
 // Everything after the gradient and the sum of squares are known: step scalars, clip, optimizer, k-major copy /
 // image, and (block 0) the per-position state.  EPT elements per thread, indices e_a (-1 = none); the new parameter
 // values come back in p_new_a for the caller's k-major / image writes.
-template <int EPT>
+// ADAM: s_old_a holds the first moments m = state[e] and v_old_a the second moments v = state[P + e]; DLA's aux moments follow at
+// state[2 P] (ultr_opt_state_floats).  Otherwise v_old_a is not read.
+template <int EPT, bool ADAM>
 __device__ __forceinline__ void update_body(const ultr_update_desc& u, const DnnPlan& dp, float* __restrict__ params,
                                             float* __restrict__ state, const float* __restrict__ tail,
                                             float* __restrict__ aux, float ss, const int64_t (&e_a)[EPT],
                                             const float (&g_raw_a)[EPT], const float (&p_old_a)[EPT],
-                                            const float (&s_old_a)[EPT], float (&p_new_a)[EPT], float* sm,
+                                            const float (&s_old_a)[EPT], const float (&v_old_a)[EPT], const OptArgs<ADAM>& oa,
+                                            float (&p_new_a)[EPT], float* sm,
                                             float* __restrict__ scalars_out, const float* __restrict__ l2_sums,
                                             const uint32_t* __restrict__ h3flag = nullptr) {
   const int64_t P = u.n_params;
@@ -207,11 +241,20 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
       float g = g_raw * gs;
       if (lam != 0.f) g += lam * p_old;
       g *= coef;
-      float s_new = s_old;
-      const float pn = opt_step(p_old, g, &s_new, u.optimizer, stateless || state == nullptr, u.learning_rate, u.adagrad_eps);
-      params[e] = pn;
-      if (state != nullptr && !stateless && u.optimizer != ULTR_OPT_SGD) state[e] = s_new;
-      p_new_a[k] = pn;
+      if constexpr (ADAM) {
+        float m_new = s_old, v_new = v_old_a[k];
+        const float pn = adam_step(p_old, g, &m_new, &v_new, oa.step, oa.rsq2, u.adagrad_eps);
+        params[e] = pn;
+        state[e] = m_new;
+        state[P + e] = v_new;
+        p_new_a[k] = pn;
+      } else {
+        float s_new = s_old;
+        const float pn = opt_step(p_old, g, &s_new, u.optimizer, stateless || state == nullptr, u.learning_rate, u.adagrad_eps);
+        params[e] = pn;
+        if (state != nullptr && !stateless && u.optimizer != ULTR_OPT_SGD) state[e] = s_new;
+        p_new_a[k] = pn;
+      }
     }
   }
   if (blockIdx.x != 0) return;
@@ -235,10 +278,30 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
     for (int l = threadIdx.x; l < L; l += 256) {
       const float z = aux[l] + bias;
       const float g = (tail[ULTR_TAIL_FIXED + l] / D2) * (z > 0.f ? 1.0f : expf(z)) * pc;
-      aux[l] = opt_step(aux[l], g, nullptr, u.optimizer, true, u.propensity_learning_rate, u.adagrad_eps);
+      if constexpr (ADAM) {  // the propensity parameters' own moments: m_aux[L + 1] | v_aux[L + 1] behind the ranker's
+        float* ma = state + 2 * P;
+        float* va = ma + (L + 1);
+        float m = ma[l], v = va[l];
+        aux[l] = adam_step(aux[l], g, &m, &v, oa.step_aux, oa.rsq2, u.adagrad_eps);
+        ma[l] = m;
+        va[l] = v;
+      } else {
+        aux[l] = opt_step(aux[l], g, nullptr, u.optimizer, true, u.propensity_learning_rate, u.adagrad_eps);
+      }
     }
     __syncthreads();  // every thread has read the old bias
-    if (threadIdx.x == 0) aux[L] = opt_step(bias, gsum * pc, nullptr, u.optimizer, true, u.propensity_learning_rate, u.adagrad_eps);
+    if constexpr (ADAM) {
+      if (threadIdx.x == 0) {
+        float* ma = state + 2 * P;
+        float* va = ma + (L + 1);
+        float m = ma[L], v = va[L];
+        aux[L] = adam_step(bias, gsum * pc, &m, &v, oa.step_aux, oa.rsq2, u.adagrad_eps);
+        ma[L] = m;
+        va[L] = v;
+      }
+    } else {
+      if (threadIdx.x == 0) aux[L] = opt_step(bias, gsum * pc, nullptr, u.optimizer, true, u.propensity_learning_rate, u.adagrad_eps);
+    }
   } else if ((u.algo == ULTR_ALGO_PAIRDEBIAS || u.algo == ULTR_ALGO_LAMBDARANK) && aux != nullptr) {
     // t <- (1 - a) t + a * (t_loss / t_loss[0]) ^ (1 / (p + 1));   LambdaRank divides with _safe_div
     const bool safe = (u.algo == ULTR_ALGO_LAMBDARANK);
@@ -281,10 +344,12 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
   }
 }
 
+template <bool ADAM>
 __global__ __launch_bounds__(256) void update_kernel(ultr_update_desc u, DnnPlan dp, float* __restrict__ params,
                                                      float* __restrict__ state, const float* __restrict__ grads,
                                                      float* __restrict__ aux, const float* __restrict__ sumsq_part, int nsq,
-                                                     float* __restrict__ scalars_out, const float* __restrict__ l2_sums, int nsq2) {
+                                                     float* __restrict__ scalars_out, const float* __restrict__ l2_sums, int nsq2,
+                                                     OptArgs<ADAM> oa) {
   if (update_guarded(u)) return;
   // flat variant (no k-major copy to maintain): one element per thread, loads issued BEFORE the norm reduction so
   // that the two memory round trips overlap
@@ -296,6 +361,8 @@ __global__ __launch_bounds__(256) void update_kernel(ultr_update_desc u, DnnPlan
   const float g_raw[1] = {live ? grads[e] : 0.f};
   const float p_old[1] = {live ? params[e] : 0.f};
   const float s_old[1] = {(live && state != nullptr) ? state[e] : 0.f};
+  float v_old[1] = {0.f};
+  if constexpr (ADAM) v_old[0] = live ? state[P + e] : 0.f;  // (Adam: s_old is m; the launcher refused a NULL state)
   float ss = 0.f;
   if (nsq2 > 0) {  // level-2 partials of this step's reduction launch (ultr_sumsq2_off)
     const float* s2 = sumsq_part + ultr_sumsq2_off(P);
@@ -305,7 +372,8 @@ __global__ __launch_bounds__(256) void update_kernel(ultr_update_desc u, DnnPlan
   }
   ss = block_sum256(ss, sm);
   float pn[1];
-  update_body<1>(u, dp, params, state, grads + P, aux, ss, ea, g_raw, p_old, s_old, pn, sm, scalars_out, l2_sums, u.range_flag);
+  update_body<1, ADAM>(u, dp, params, state, grads + P, aux, ss, ea, g_raw, p_old, s_old, v_old, oa, pn, sm, scalars_out, l2_sums,
+                       u.range_flag);
 }
 
 // The update's work map (DnnPlan::upd_* / vs_* and the K, M, off_w of the layers) in LDS.  DnnPlan is a by-value kernel
@@ -344,13 +412,14 @@ __device__ __forceinline__ int64_t upd_u64(const int* sm_plan, size_t off, int j
 // TPW tiles (or 256-element pieces of the vector parameters) per workgroup: every workgroup re-sums ALL sum-of-squares
 // partials (one per 64 parameters) for its copy of the clip coefficient - at 0.5 M parameters (config 4) that is 32 KB per
 // workgroup and 2050 workgroups; four units per workgroup quarter that traffic (update 14 -> 8 us there).
-template <int TPW>
+template <int TPW, bool ADAM>
 __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, DnnPlan dp, float* __restrict__ params,
                                                            float* __restrict__ state, const float* __restrict__ grads,
                                                            float* __restrict__ aux, float* __restrict__ wt,
                                                            const float* __restrict__ sumsq_part, int nsq,
                                                            float* __restrict__ scalars_out, int n_tile_blocks,
-                                                           const float* __restrict__ l2_sums, int nsq2, int rider_first, ultr_click_args rider) {
+                                                           const float* __restrict__ l2_sums, int nsq2, int rider_first, ultr_click_args rider,
+                                                           OptArgs<ADAM> oa) {
   __shared__ float sm[4];
   __shared__ float tile[TPW][16][17];
   __shared__ int sm_plan[UPD_A_DW + UPD_B_DW];
@@ -428,13 +497,15 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
   }
   UPD_AFTER((int)ea[0]);
   UPD_STAMP(1);
-  float g_raw[TPW], p_old[TPW], s_old[TPW];
+  float g_raw[TPW], p_old[TPW], s_old[TPW], v_old[TPW];
 #pragma unroll
   for (int q = 0; q < TPW; ++q) {
     const bool live = ea[q] >= 0;
     g_raw[q] = live ? grads[ea[q]] : 0.f;
     p_old[q] = live ? params[ea[q]] : 0.f;
     s_old[q] = (live && state != nullptr) ? state[ea[q]] : 0.f;
+    v_old[q] = 0.f;
+    if constexpr (ADAM) v_old[q] = live ? state[P + ea[q]] : 0.f;  // (Adam: s_old is m; the launcher refused a NULL state)
   }
 #ifdef ULTR_TRACE
   UPD_AFTER(g_raw[0] + p_old[0] + s_old[0]);
@@ -453,9 +524,9 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
   float pn[TPW];
   // block 0's extra duties (EM / propensity updates, step scalars) run inside update_body and need all 256 threads
   if (blockIdx.x != 0) {
-    update_body<TPW>(u, dp, params, state, grads + P, aux, ss, ea, g_raw, p_old, s_old, pn, sm, nullptr, l2_sums);
+    update_body<TPW, ADAM>(u, dp, params, state, grads + P, aux, ss, ea, g_raw, p_old, s_old, v_old, oa, pn, sm, nullptr, l2_sums);
   } else {
-    update_body<TPW>(u, dp, params, state, grads + P, aux, ss, ea, g_raw, p_old, s_old, pn, sm, scalars_out, l2_sums,
+    update_body<TPW, ADAM>(u, dp, params, state, grads + P, aux, ss, ea, g_raw, p_old, s_old, v_old, oa, pn, sm, scalars_out, l2_sums,
                      // (only a model whose weights some split-half product may READ reports: with the knobs off, or for a model
                      // switched to the fp32 products, a large weight is harmless)
                      (dp.h3_flag_off > 0 && dp.h3_watch) ? reinterpret_cast<const uint32_t*>(wt + dp.h3_flag_off) : u.range_flag);
@@ -532,6 +603,47 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
   UPD_STAMP(4);
 }
 
+extern "C" int64_t ultr_opt_state_floats(const ultr_update_desc* u) {
+  if (!u || u->n_params <= 0 || u->list_size <= 0 || u->algo < 0 || u->algo > ULTR_ALGO_DBGD) return -1;
+  switch (u->optimizer) {
+    case ULTR_OPT_SGD: return 0;
+    case ULTR_OPT_ADAGRAD: return u->n_params;
+    case ULTR_OPT_ADAM: return 2 * u->n_params + (u->algo == ULTR_ALGO_DLA ? 2 * ((int64_t)u->list_size + 1) : 0);
+  }
+  return -1;
+}
+
+int ultr_update_check_opt(const ultr_update_desc* u, const float* state) {
+  if (u->optimizer != ULTR_OPT_ADAGRAD && u->optimizer != ULTR_OPT_SGD && u->optimizer != ULTR_OPT_ADAM) return ULTR_E_BADARG;
+  if (u->optimizer == ULTR_OPT_ADAM && (!state || u->adam_t == 0u)) return ULTR_E_BADARG;
+  return 0;
+}
+
+// the three kernels of one optimizer class and their launch; the Adagrad / SGD class is the code as it was before Adam
+template <bool ADAM>
+static void launch_update(UltrProfScope& prof, const ultr_update_desc* u, const DnnPlan& dp, float* params, float* wt, float* state,
+                          const float* grads, float* aux, const void* bwd_ws, int nsq, float* scalars_out, const float* l2_sums, int nsq2,
+                          const ultr_click_args& rider, int rider_blocks, const OptArgs<ADAM>& oa, void* stream) {
+  if (wt != nullptr) {
+    const int n_tiles = dp.upd_tile_begin[dp.nl - 1], n_vec = dp.vs_begin[dp.n_vs];
+    if (n_tiles + (n_vec + 255) / 256 < 1536) {  // one unit per workgroup keeps the launch wide (config 2: 401 units, config 3: 940 -
+                                                 // four per workgroup left 235 workgroups for 256 CUs: 7.0 -> 9.0 us)
+      const int own = n_tiles + (n_vec + 255) / 256;
+      ULTR_LAUNCH(prof, (update_tiled_kernel<1, ADAM>), dim3(own + rider_blocks), dim3(256), 0, (hipStream_t)stream, *u, dp, params, state,
+                  grads, aux, wt, (const float*)bwd_ws, nsq, scalars_out, n_tiles, l2_sums, nsq2, own, rider, oa);
+    } else {
+      const int tb = (n_tiles + 3) / 4;
+      const int own = tb + (n_vec + 1023) / 1024;
+      ULTR_LAUNCH(prof, (update_tiled_kernel<4, ADAM>), dim3(own + rider_blocks), dim3(256), 0, (hipStream_t)stream, *u, dp, params, state,
+                  grads, aux, wt, (const float*)bwd_ws, nsq, scalars_out, tb, l2_sums, nsq2, own, rider, oa);
+    }
+  } else {
+    const int nblk = (int)((u->n_params + 255) / 256);
+    ULTR_LAUNCH(prof, update_kernel<ADAM>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, *u, dp, params, state, grads, aux,
+                (const float*)bwd_ws, nsq, scalars_out, l2_sums, nsq2, oa);
+  }
+}
+
 extern "C" int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state,
                                  const float* grads, float* aux, const void* bwd_ws, float* scalars_out, void* stream) {
   return ultr_apply_update_ex(u, d, params, wt, state, grads, aux, bwd_ws, scalars_out, 0, nullptr, stream);
@@ -545,8 +657,7 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
   if (wt != nullptr) {
     if (!ultr_make_dnn_plan(d, 0, &dp) || dp.P != u->n_params) return ULTR_E_BADARG;
   }
-  if (u->algo < 0 || u->algo > ULTR_ALGO_DBGD || (u->optimizer != ULTR_OPT_ADAGRAD && u->optimizer != ULTR_OPT_SGD))
-    return ULTR_E_BADARG;
+  if (u->algo < 0 || u->algo > ULTR_ALGO_DBGD || ultr_update_check_opt(u, state)) return ULTR_E_BADARG;
   if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && u->algo != ULTR_ALGO_PDGD && u->algo != ULTR_ALGO_DBGD && !aux)
     return ULTR_E_BADARG;
   if (u->optimizer == ULTR_OPT_ADAGRAD && u->algo != ULTR_ALGO_DLA && !state) return ULTR_E_BADARG;
@@ -562,32 +673,20 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
     l2_sums = scalars_out + 8;
   }
   UltrProfScope prof(ULTR_K_UPDATE, (hipStream_t)stream);
-  if (wt != nullptr) {
-    const int n_tiles = dp.upd_tile_begin[dp.nl - 1], n_vec = dp.vs_begin[dp.n_vs];
-    // a click draw waiting for a launch to ride on (ultr_feed_train_step): its (batch + 3) / 4 workgroups follow the update's
-    ultr_click_args rider;
-    memset(&rider, 0, sizeof(rider));
-    int rider_blocks = 0;
-    if (rider_io != nullptr && *rider_io != nullptr) {
-      rider = **rider_io;
-      rider_blocks = (rider.batch + 3) / 4;
-      *rider_io = nullptr;
-    }
-    if (n_tiles + (n_vec + 255) / 256 < 1536) {  // one unit per workgroup keeps the launch wide (config 2: 401 units, config 3: 940 -
-                                                 // four per workgroup left 235 workgroups for 256 CUs: 7.0 -> 9.0 us)
-      const int own = n_tiles + (n_vec + 255) / 256;
-      ULTR_LAUNCH(prof, update_tiled_kernel<1>, dim3(own + rider_blocks), dim3(256), 0, (hipStream_t)stream, *u, dp, params, state,
-                  grads, aux, wt, (const float*)bwd_ws, nsq, scalars_out, n_tiles, l2_sums, nsq2, own, rider);
-    } else {
-      const int tb = (n_tiles + 3) / 4;
-      const int own = tb + (n_vec + 1023) / 1024;
-      ULTR_LAUNCH(prof, update_tiled_kernel<4>, dim3(own + rider_blocks), dim3(256), 0, (hipStream_t)stream, *u, dp, params, state,
-                  grads, aux, wt, (const float*)bwd_ws, nsq, scalars_out, tb, l2_sums, nsq2, own, rider);
-    }
-  } else {
-    const int nblk = (int)((u->n_params + 255) / 256);
-    ULTR_LAUNCH(prof, update_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, *u, dp, params, state, grads, aux,
-                (const float*)bwd_ws, nsq, scalars_out, l2_sums, nsq2);
+  // a click draw waiting for a launch to ride on (ultr_feed_train_step): its (batch + 3) / 4 workgroups follow the update's
+  ultr_click_args rider;
+  memset(&rider, 0, sizeof(rider));
+  int rider_blocks = 0;
+  if (wt != nullptr && rider_io != nullptr && *rider_io != nullptr) {
+    rider = **rider_io;
+    rider_blocks = (rider.batch + 3) / 4;
+    *rider_io = nullptr;
   }
+  if (u->optimizer == ULTR_OPT_ADAM)
+    launch_update<true>(prof, u, dp, params, wt, state, grads, aux, bwd_ws, nsq, scalars_out, l2_sums, nsq2, rider, rider_blocks,
+                        adam_corr(*u), stream);
+  else
+    launch_update<false>(prof, u, dp, params, wt, state, grads, aux, bwd_ws, nsq, scalars_out, l2_sums, nsq2, rider, rider_blocks,
+                         OptArgs<false>(), stream);
   return (int)hipGetLastError();
 }

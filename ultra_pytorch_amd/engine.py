@@ -26,6 +26,23 @@ ALGOS = {"softmax": _lib.ALGO_SOFTMAX, "dla": _lib.ALGO_DLA, "pairdebias": _lib.
          "pdgd": _lib.ALGO_PDGD, "dbgd": _lib.ALGO_DBGD}
 
 
+def optimizer_id(name):
+    """grad_strategy -> ultr_opt for the engines whose state the learning algorithm sizes with opt_state_floats: 'sgd', 'adam', and
+    Adagrad for every other string (the reference's own rule, base_algorithm.py:208-226)."""
+    return {"sgd": _lib.OPT_SGD, "adam": _lib.OPT_ADAM}.get(name, _lib.OPT_ADAGRAD)
+
+
+def opt_state_floats(algo, optimizer, list_size, n_params):
+    """Floats of optimizer state (ultr_opt_state_floats; host-only) for an engine algorithm name, a grad_strategy, the list size and
+    the parameter count: SGD 0, Adagrad P, Adam 2 P (m | v) and 2 (L + 1) more for DLA's propensity parameters."""
+    u = _lib.UpdateDesc()
+    u.algo, u.optimizer, u.list_size, u.n_params = ALGOS[algo], optimizer_id(optimizer), int(list_size), int(n_params)
+    n = int(_lib.load().ultr_opt_state_floats(ctypes.byref(u)))
+    if n < 0:
+        raise ValueError("ultr_opt_state_floats refused algo=%r optimizer=%r list_size=%r n_params=%r" % (algo, optimizer, list_size, n_params))
+    return n
+
+
 def _f32(n, device, zero=False):
     n = max(int(n), 1)
     return (torch.zeros if zero else torch.empty)(n, dtype=torch.float32, device=device)
@@ -89,13 +106,16 @@ class StepEngine:
         self._host_report = os.environ.get("ULTR_HOST_REPORT", "1") != "0"
         u = _lib.UpdateDesc()
         u.algo = ALGOS[algo]
-        u.optimizer = _lib.OPT_SGD if optimizer == "sgd" else _lib.OPT_ADAGRAD
+        u.optimizer = optimizer_id(optimizer)
         u.list_size = self.L
         u.logits_to_prob = self.l2p
         u.n_params = P
         u.learning_rate = float(learning_rate)
         u.max_gradient_norm = float(max_gradient_norm)
-        u.adagrad_eps = 1e-10
+        u.adagrad_eps = _lib.ADAM_EPS if u.optimizer == _lib.OPT_ADAM else 1e-10
+        # Adam's step count t is NOT this engine's: engines are cached per (batch, list size) and evicted, the count belongs beside the
+        # state tensor.  The owner of the state hands it in before every step (set_opt_step); 0 makes the update launch refuse.
+        u.adam_t = 0
         u.ranker_loss_weight = float(ranker_loss_weight)
         plr = propensity_learning_rate
         u.propensity_learning_rate = float(learning_rate if plr is None or plr < 0 else plr)
@@ -186,6 +206,11 @@ class StepEngine:
     def _next_seq(self):
         self._seq = (self._seq % 0xFFFFFFFF) + 1  # 1 .. 2^32-1: never 0, the buffer's initial content
         self.udesc.seq = self._seq
+
+    def set_opt_step(self, t):
+        """The step count t >= 1 the NEXT train_step / update applies to `state` (ultr_update_desc::adam_t; read by Adam only).  The
+        caller counts it beside the state tensor, one count per state, whichever engine a step runs in."""
+        self.udesc.adam_t = min(int(t), 0xFFFFFFFF)  # (beyond 2^32 - 1 steps both bias corrections are 1 anyway)
 
     def read_scalars(self, timeout_s=60.0, scheduled=False):
         """The step scalars of the LAST queued step as a numpy array ([0] loss, [1] gradient norm, [2] clip coefficient, [3] D,

@@ -46,7 +46,13 @@ class BaseAlgorithm(object):
         self.global_step = 0
         self.model = self.create_model(self.feature_size).to(self.cuda)
         self.learning_rate = float(self.hparams.learning_rate)
-        self.state_sum = torch.zeros_like(self.model.flat_params)  # Adagrad accumulator (initial value 0)
+        # optimizer state, initial value 0: the Adagrad accumulator [P], or Adam's m | v [2 P] (+ DLA's propensity moments) with the
+        # step count beside it - both are this object's, not an engine's (engines are per batch shape and get evicted).  SGD keeps
+        # the [P] tensor it always had, unused.
+        P = self.model.flat_params.numel()
+        n_state = engine.opt_state_floats(self.ENGINE_ALGO, self._optimizer(), getattr(self, "rank_list_size", self.max_candidate_num), P)
+        self.state_sum = torch.zeros(n_state if n_state > 0 else P, dtype=torch.float32, device=self.model.flat_params.device)
+        self.opt_steps = 0
         # per-(batch, list size) workspaces, least recently used first: DirectLabelFeed may return short batches (SURVEY Appendix
         # A.13), each distinct size is a workspace set - at most MAX_ENGINES of them are kept
         self._train_engines, self._eval_engines = collections.OrderedDict(), collections.OrderedDict()
@@ -127,6 +133,11 @@ class BaseAlgorithm(object):
     def _engine_kwargs(self):
         return {}
 
+    def _optimizer(self):
+        """The engines' optimizer name for hparams.grad_strategy: 'sgd', 'adam', and Adagrad for any other string, as the reference."""
+        gs = self.hparams.grad_strategy
+        return gs if gs in ("sgd", "adam") else "ada"
+
     MAX_ENGINES = 8
 
     def _dp_batch_total(self, B):
@@ -160,7 +171,7 @@ class BaseAlgorithm(object):
         eng = self._train_engines.get(key)
         if eng is None:
             kw = dict(learning_rate=self.learning_rate, max_gradient_norm=float(self.hparams.max_gradient_norm),
-                      optimizer="sgd" if self.hparams.grad_strategy == "sgd" else "ada",
+                      optimizer=self._optimizer(),
                       l2_loss=float(getattr(self.hparams, "l2_loss", 0.0)), process_group=self.process_group)
             if self.process_group is not None:
                 kw.update(batch_total=bt, comm=self._dp_comm)
@@ -175,6 +186,9 @@ class BaseAlgorithm(object):
         else:
             self._train_engines.move_to_end(key)
         eng.batch_total = bt
+        # one _train_engine() per train(): the step about to run is number opt_steps of state_sum, whichever engine runs it (Adam's t)
+        self.opt_steps += 1
+        eng.set_opt_step(self.opt_steps)
         # a DeviceClickFeed batch: the engine draws the feed's NEXT batch behind this step in the same host call
         eng.next_click_source = getattr(self, "_feed_obj", None)
         return eng

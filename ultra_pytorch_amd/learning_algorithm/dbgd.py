@@ -53,6 +53,9 @@ class DBGD(BaseAlgorithm):
         _, self.click_model, self.click_model_id = click_models.load_for_device(self.hparams.click_model_json, type(self).__name__)
         self.exam, self.n_exam, self.cprob = click_models.device_tables(self.click_model, self.click_model_id, self.cuda)
 
+    def _optimizer(self):
+        return "sgd" if self.hparams.grad_strategy == "sgd" else "ada"  # (engine.DbgdEngine knows these two)
+
     def _dbgd_engine(self, B, M):
         key = (B, M)
         eng = self._train_engines.get(key)
@@ -62,7 +65,7 @@ class DBGD(BaseAlgorithm):
                 need_interleave=bool(self.hparams.need_interleave), stochastic=self.interleaving_strategy == "Stochastic",
                 tau=float(self.hparams.tau), noise_rate=float(self.hparams.learning_rate), learning_rate=self.learning_rate,
                 max_gradient_norm=float(self.hparams.max_gradient_norm),
-                optimizer="sgd" if self.hparams.grad_strategy == "sgd" else "ada", click_model=self.click_model_id,
+                optimizer=self._optimizer(), click_model=self.click_model_id,
                 exam=self.exam, n_exam=self.n_exam, cprob=self.cprob, seed=self.rng_seed, max_redraws=self.MAX_SAMPLE_ROUND_NUM)
             while len(self._train_engines) > self.MAX_ENGINES:
                 self._train_engines.popitem(last=False)

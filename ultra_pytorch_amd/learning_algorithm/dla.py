@@ -56,14 +56,17 @@ class DLA(BaseAlgorithm):
 
     def train(self, input_feed):
         """dla.py:179-266.  Both models get a FRESH optimizer each step in the reference (dla.py:153-154), so the
-        Adagrad accumulator never persists: state=None selects the stateless update.  max_propensity_weight is
+        Adagrad accumulator never persists: state=None selects the stateless update.  grad_strategy=adam is this project's own and
+        keeps its moments across steps (a fresh Adam every step would be a sign update): state_sum holds the ranker's m | v and, behind
+        them, the propensity model's.  max_propensity_weight is
         inert in the reference (clamps .grad of a grad-less tensor, dla.py:303-305) and is ignored here too."""
         self.rank_list_size = self.exp_settings["selection_bias_cutoff"]
         if not self.model.training:  # (nn.Module.train() walks every submodule: ~10 us a 47 us step does not have)
             self.model.train()
         self.create_input_feed(input_feed, self.rank_list_size)
         eng = self._train_engine(self.batch_size, self.rank_list_size)
-        sc = eng.train_step(self.model.flat_params, None, self.letor_features, self.n_docs, self.docid_inputs,
+        state = self.state_sum if self._optimizer() == "adam" else None
+        sc = eng.train_step(self.model.flat_params, state, self.letor_features, self.n_docs, self.docid_inputs,
                             self.labels_LB, aux=self.propensity_model.flat_params)
         vals = eng.read_scalars()
         self.loss, self.rank_loss, self.exam_loss = float(vals[0]), float(vals[4]), float(vals[5])
