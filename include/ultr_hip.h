@@ -101,10 +101,10 @@ int64_t ultr_loss_workspace_bytes(int64_t batch, int32_t list_size);
 /* step-tail partials the stand-alone ultr_*_loss kernels leave in `loss_ws` (one per workgroup) = the n_loss_parts of
  * ultr_setrank_backward */
 int64_t ultr_loss_part_count(int64_t batch);
-/* Dynamic LDS in bytes that the stand-alone loss kernel of `algo` (ULTR_ALGO_SOFTMAX .. ULTR_ALGO_PDGD) requests at list_size
+/* Dynamic LDS in bytes that the stand-alone loss kernel of `algo` (ULTR_ALGO_SOFTMAX .. ULTR_ALGO_PDGD, ULTR_ALGO_TWOTOWER) requests at list_size
  * (additive within ABI 8; host-only, launches nothing) - read from the layout the kernel itself carves its LDS with
  * (csrc/ultr_listloss.h).  ULTR_E_UNSUPPORTED where the entry would refuse the list size: beyond 64 KiB for ultr_softmax_ce,
- * ultr_dla_loss and ultr_regem_loss, beyond 160 KiB for ultr_pairdebias_loss, ultr_lambdarank_loss and ultr_prs_loss, beyond 256
+ * ultr_dla_loss, ultr_regem_loss and ultr_twotower_loss, beyond 160 KiB for ultr_pairdebias_loss, ultr_lambdarank_loss and ultr_prs_loss, beyond 256
  * documents for ultr_pdgd_loss - the longest accepted lists are stated with each entry below.  ULTR_E_BADARG: an algorithm without a
  * stand-alone loss kernel, list_size <= 0. */
 int64_t ultr_loss_lds_bytes(int32_t algo, int32_t list_size);
@@ -258,6 +258,27 @@ int ultr_lambdarank_loss(const float* scores, const float* labels, const float* 
 int ultr_regem_loss(const float* scores, const float* labels, const float* propensity, const float* uniforms,
                     uint64_t seed, uint64_t step, int32_t batch, int32_t list_size, float* dscores,
                     float* pseudo_labels_out, void* loss_ws, void* stream);
+
+/* ---- TwoTower: joint click likelihood of a relevance and an observation tower (additive within ABI 8) ----
+ * The project's own pointwise learner (PAL's "shallow tower"); the click model of RegressionEM fitted by gradient steps.
+ * scores [B, L] = the relevance tower s; bias_logits [L] = the observation tower theta (one logit per position); click
+ * c = min(labels[l, b], 1) (graded labels clamp, fractional ones in [0, 1] are taken as they are).
+ * combination 0 (product): p = sigmoid(s) sigmoid(theta_l); ULTR_TWOTOWER_SUM: p = sigmoid(s + theta_l).
+ * Element loss -c log p - (1 - c) log(1 - p), summed over the positions of a list; D = the number of lists (the update divides).
+ * Evaluated without cancellation: log sigmoid(x) = min(x, 0) - log1p(exp(-|x|)); product: q = 1 - p = sigmoid(-s) +
+ * sigmoid(s) sigmoid(-theta), log(1 - p) = log1p(-p) where p < 0.5 and log q otherwise, r = (1 - c) p / q - c,
+ * dl/ds = sigmoid(-s) r, dl/dtheta = sigmoid(-theta) r; sum: BCE-with-logits of z = s + theta, dl/ds = dl/dtheta = sigmoid(z) - c.
+ * docids [L, B] != NULL: a PAD position (id < 0 or >= n_docs) adds nothing to the loss, gets dscores exactly 0 and adds nothing to
+ * theta's gradient; docids == NULL: every position counts (a PAD as an unclicked document, RegressionEM's convention).
+ * Writes dscores = dl/ds (x D) and the step tail [sum l, lists, 0, 0, sum_b dl/dtheta_l at 4 + l ...]; no atomics, the same inputs
+ * give the same bits.  ultr_apply_update (ULTR_ALGO_TWOTOWER, aux = theta) clips the two towers separately and steps theta with the
+ * descriptor's optimizer at propensity_learning_rate.
+ * list_size up to 8190 (64 KiB of LDS, ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched.
+ * ULTR_E_BADARG: a missing pointer, batch <= 0, list_size <= 0, a combination other than 0 / ULTR_TWOTOWER_SUM, docids with n_docs < 0. */
+#define ULTR_TWOTOWER_SUM 1  /* also bit 0 of ultr_update_desc::logits_to_prob */
+#define ULTR_TWOTOWER_MASK 2 /* bit 1 of ultr_update_desc::logits_to_prob: ultr_train_step passes its docids to the loss */
+int ultr_twotower_loss(const float* scores, const float* labels, const float* bias_logits, int32_t combination, const int32_t* docids,
+                       int64_t n_docs, int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
 
 /* ---- PRSrank: propensity-ratio-scored LambdaRank -------------------------------------
  * Replaces PRSrank.train's propensity + loss section (prs_rank.py:94-176) + dcg/compute_delta_ndcg
@@ -519,7 +540,10 @@ int ultr_gsf_backward(const ultr_gsf_desc* c, const float* params, const float* 
 enum ultr_algo { ULTR_ALGO_SOFTMAX = 0, ULTR_ALGO_DLA = 1, ULTR_ALGO_PAIRDEBIAS = 2, ULTR_ALGO_LAMBDARANK = 3, ULTR_ALGO_REGEM = 4,
                  ULTR_ALGO_PRS = 5, ULTR_ALGO_PDGD = 6,
                  /* DBGD / MGD: grads from ultr_dbgd_grad_args, loss in the step tail, D = 1 (no l2_loss) */
-                 ULTR_ALGO_DBGD = 7 };
+                 ULTR_ALGO_DBGD = 7,
+                 /* TwoTower (additive within ABI 8): ultr_twotower_loss, aux = the observation tower's logits [L].  The value 8 is
+                  * left out and stays ULTR_E_BADARG everywhere: tests/test_adam_cpu.py holds `algo = 8` to be a bad descriptor. */
+                 ULTR_ALGO_TWOTOWER = 9 };
 /* ULTR_OPT_ADAM: torch.optim.Adam with its defaults (no weight decay, no amsgrad), applied to the gradient Adagrad / SGD get - after
  * the 1 / D scaling, the l2_loss term and the clip.  For step t = 1, 2, ...:
  *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
@@ -534,13 +558,14 @@ typedef struct ultr_update_desc {
   int32_t algo;            /* ultr_algo */
   int32_t optimizer;       /* ultr_opt (grad_strategy 'ada' / 'sgd' / 'adam') */
   int32_t list_size;       /* L */
-  int32_t logits_to_prob;  /* DLA only */
+  int32_t logits_to_prob;  /* DLA: 0 softmax, 1 sigmoid.  TwoTower (same field, the struct's layout is unchanged): bit 0 = the towers
+                            * combine as a sum (ULTR_TWOTOWER_SUM), bit 1 = PAD positions are masked (ULTR_TWOTOWER_MASK) */
   int64_t n_params;        /* P */
   float learning_rate;
   float max_gradient_norm; /* <= 0 disables clipping */
   float adagrad_eps;       /* 1e-10; ULTR_OPT_ADAM: Adam's eps (ULTR_ADAM_EPS) */
   float ranker_loss_weight;     /* DLA */
-  float propensity_learning_rate; /* DLA */
+  float propensity_learning_rate; /* DLA, TwoTower (the observation tower's rate) */
   float em_step_size;      /* PairDebias / LambdaRank */
   float regulation_p;      /* PairDebias / LambdaRank */
   /* l2_loss hyper-parameter (ipw_rank.py:154-157, navie_algorithm.py:109-114, pairwise_debias.py:166-169,
@@ -573,8 +598,9 @@ typedef struct ultr_update_desc {
 } ultr_update_desc;
 
 /* floats of `state` for this descriptor (host-only; reads algo, optimizer, list_size, n_params): SGD 0; Adagrad P; Adam 2 P as
- * m[P] | v[P], and for DLA 2 (L + 1) more behind them, m_aux[L + 1] | v_aux[L + 1] (the propensity parameters' moments).  -1 on a
- * bad descriptor.  A fresh state is all zeros. */
+ * m[P] | v[P], and for DLA 2 (L + 1) more behind them, m_aux[L + 1] | v_aux[L + 1] (the propensity parameters' moments).
+ * TwoTower's observation tower keeps state of its own behind the ranker's: Adagrad P + L (its L accumulators), Adam 2 P + 2 L
+ * (m[L] | v[L]).  -1 on a bad descriptor.  A fresh state is all zeros. */
 int64_t ultr_opt_state_floats(const ultr_update_desc* u);
 
 /* params/state [P] (ultr_opt_state_floats) updated in place; grads = the buffer ultr_dnn_backward filled (possibly
@@ -584,7 +610,8 @@ int64_t ultr_opt_state_floats(const ultr_update_desc* u);
  * in sync with the updated parameters.  bwd_ws = the workspace ultr_dnn_backward (or
  * ultr_grad_sumsq) left the sum-of-squares partials in.
  * scalars_out[16]: [0] loss [1] ranker grad norm (pre-clip) [2] clip coef [3] D
- *                  [4] rank_loss (DLA) [5] exam_loss (DLA) [6] propensity grad norm (DLA) [7] sum g^2
+ *                  [4] rank_loss (DLA) [5] exam_loss (DLA) [6] propensity grad norm (DLA; TwoTower: the observation tower's,
+ *                  pre-clip) [7] sum g^2
  *                  [8] sum p^2  [9] sum g.p  (written by a pre-pass only when l2_loss > 0)  [10..16) reserved */
 int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state,
                       const float* grads, float* aux, const void* bwd_ws, float* scalars_out, void* stream);
@@ -593,7 +620,8 @@ int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* 
  * ultr_dnn_forward -> ultr_<loss by upd->algo> -> ultr_dnn_backward -> ultr_apply_update, enqueued by ONE host
  * call (what `model.train(input_feed)` does between marshalling the feed and `loss.item()`).  A data-parallel
  * caller sets skip_update, all-reduces `grads`, then calls ultr_grad_sumsq + ultr_apply_update itself.
- * aux: prop_params (DLA) or [t_plus | t_minus] (PairDebias / LambdaRank) or propensity [L] (RegressionEM) or NULL.
+ * aux: prop_params (DLA) or [t_plus | t_minus] (PairDebias / LambdaRank) or propensity [L] (RegressionEM) or the observation
+ * tower's logits [L] (TwoTower) or NULL.
  * ipw_table / n_ipw: the IPW_list of IPW (SOFTMAX) and PRS; pw: explicit [B, L] weights instead (SOFTMAX: ultr_softmax_ce's pw;
  * PRS: ultr_prs_loss_pw's ipw_bl).  sigma: LambdaRank and PRS.
  * PDGD (no IPW table, no sigma): sigma carries tau and n_ipw the cutoff (selection_bias_cutoff); docids / n_docs mark

@@ -14,6 +14,8 @@ COMM_HANDLE_BYTES, COMM_MAX_WORLD = 64, 8
 ACT = {"elu": 0, "relu": 1, "tanh": 2, "sigmoid": 3}  # base_ranking_model.py:63-69 ("selu" raises in the reference)
 ATTN_DTYPE = {"fp32": 0, "fp16": 1}
 ALGO_SOFTMAX, ALGO_DLA, ALGO_PAIRDEBIAS, ALGO_LAMBDARANK, ALGO_REGEM, ALGO_PRS, ALGO_PDGD, ALGO_DBGD = 0, 1, 2, 3, 4, 5, 6, 7
+ALGO_TWOTOWER = 9  # (8 is no algorithm: include/ultr_hip.h)
+TWOTOWER_SUM, TWOTOWER_MASK = 1, 2  # ultr_twotower_loss's combination; bits of ultr_update_desc::logits_to_prob
 OPT_ADAGRAD, OPT_SGD, OPT_ADAM = 0, 1, 2
 ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-8  # include/ultr_hip.h: ULTR_ADAM_*
 
@@ -182,6 +184,7 @@ SIGNATURES = {
     "ultr_prs_loss_long": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_prs_loss_pw_long": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_regem_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "ultr_twotower_loss": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_setrank_param_count": (c_i64, [ctypes.POINTER(SetRankDesc)]),
     "ultr_setrank_saved_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
     "ultr_setrank_workspace_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),

@@ -1,4 +1,4 @@
-// ultr_listloss.h — what the seven list-loss kernels share (ultr_loss.hip, ultr_prs.hip, ultr_pdgd.hip):
+// ultr_listloss.h — what the eight list-loss kernels share (ultr_loss.hip, ultr_prs.hip, ultr_pdgd.hip, ultr_twotower.hip):
 //   * one LDS layout per kernel, a __host__ __device__ struct built from L: the kernel takes its pointers from the offsets, the
 //     launcher and ultr_loss_lds_bytes take `bytes` - the two sides cannot drift apart;
 //   * launch_list_loss, the one launcher behind the extern "C" entries;
@@ -60,6 +60,9 @@ struct RegemLds : LdsCarve {  // list_size <= 8190
   int64_t bytes = end();
   __host__ __device__ explicit RegemLds(int L_) : LdsCarve(L_) {}
 };
+
+// ultr_twotower.hip keeps nothing but the tail in LDS either: RegressionEM's layout under the kernel's own name (list_size <= 8190)
+using TwoTowerLds = RegemLds;
 
 struct DlaLds : LdsCarve {  // list_size <= 3276
   static constexpr int64_t limit = LOSS_LDS_DEFAULT;
@@ -207,6 +210,8 @@ static inline bool loss_short_refuses(int algo, int L) {
 
 // LOSS_ROUTE_SHORT, LOSS_ROUTE_LONG, or ULTR_E_UNSUPPORTED for a list neither kernel takes
 static inline int loss_route(int algo, int L) {
+  // TwoTower has the one kernel: a list beyond its layout is refused here, before the forward is launched
+  if (algo == ULTR_ALGO_TWOTOWER && L > 0 && TwoTowerLds(L).bytes > TwoTowerLds::limit) return ULTR_E_UNSUPPORTED;
   if (!loss_short_refuses(algo, L)) return LOSS_ROUTE_SHORT;
   return loss_long_bytes(algo, L) >= 0 ? LOSS_ROUTE_LONG : ULTR_E_UNSUPPORTED;
 }

@@ -114,6 +114,11 @@ int ultr_train_step_ctx(const ultr_step_args* a, StepCtx* ctx, void* stream) {
       rc = ultr_regem_loss(a->scores, a->labels, a->aux, a->uniforms, a->rng_seed, a->rng_step, a->batch, a->list_size,
                            a->dscores, nullptr, a->loss_ws, stream);
       break;
+    case ULTR_ALGO_TWOTOWER:  // the combination and the mask flag travel in logits_to_prob (include/ultr_hip.h)
+      rc = ultr_twotower_loss(a->scores, a->labels, a->aux, a->upd->logits_to_prob & ULTR_TWOTOWER_SUM,
+                              (a->upd->logits_to_prob & ULTR_TWOTOWER_MASK) ? a->docids : nullptr, a->n_docs, a->batch, a->list_size,
+                              a->dscores, a->loss_ws, stream);
+      break;
     default:
       return ULTR_E_BADARG;
   }

@@ -57,7 +57,7 @@ __device__ __forceinline__ float opt_step(float p, float g, float* st, int opt, 
 
 // ULTR_OPT_ADAM.  The bias corrections depend on the step count alone, so the HOST forms them, in double (adam_corr): a float32
 // pow(b2, t) in every thread would cost more than the rest of the step and lose digits as t grows.
-//   step  = lr / (1 - b1^t)   (step_aux: the same with propensity_learning_rate, for DLA's aux)
+//   step  = lr / (1 - b1^t)   (step_aux: the same with propensity_learning_rate, for DLA's aux and TwoTower's)
 //   rsq2  = 1 / sqrt(1 - b2^t)
 // The kernels are instantiated per optimizer class; the Adagrad / SGD instantiation carries an empty OptArgs.
 template <bool ADAM>
@@ -162,8 +162,8 @@ __global__ __launch_bounds__(1024) void l2_sums_kernel(const float* __restrict__
 // Everything after the gradient and the sum of squares are known: step scalars, clip, optimizer, k-major copy /
 // image, and (block 0) the per-position state.  EPT elements per thread, indices e_a (-1 = none); the new parameter
 // values come back in p_new_a for the caller's k-major / image writes.
-// ADAM: s_old_a holds the first moments m = state[e] and v_old_a the second moments v = state[P + e]; DLA's aux moments follow at
-// state[2 P] (ultr_opt_state_floats).  Otherwise v_old_a is not read.
+// ADAM: s_old_a holds the first moments m = state[e] and v_old_a the second moments v = state[P + e]; DLA's aux moments and TwoTower's
+// follow at state[2 P] (ultr_opt_state_floats).  Otherwise v_old_a is not read.
 template <int EPT, bool ADAM>
 __device__ __forceinline__ void update_body(const ultr_update_desc& u, const DnnPlan& dp, float* __restrict__ params,
                                             float* __restrict__ state, const float* __restrict__ tail,
@@ -204,6 +204,10 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
       gs = 1.0f / D;
       loss = loss_sum / D;
       break;
+    case ULTR_ALGO_TWOTOWER:  // the click log-likelihood: positions summed, mean over the D lists (ultr_twotower.hip)
+      gs = 1.0f / D;
+      loss = loss_sum / D;
+      break;
     case ULTR_ALGO_PDGD:  // the weighted pair terms are summed (pdgd.py:197-205)
     case ULTR_ALGO_DBGD:  // grads already hold the step's direction; the loss is 1 - NDCG of the current model (dbgd.py:140)
       gs = 1.0f;
@@ -214,7 +218,8 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
   // l2_loss > 0 (ipw_rank.py:154-157 and siblings): g += lam * p, loss += l2_loss * sum p^2 / 2.  Every algorithm but DLA
   // and PDGD hands clip_grad_norm_ a parameter generator the L2 loop has already exhausted, so NOTHING is clipped (Appendix
   // A.8); DLA adds the term to rank_loss (scaled by ranker_loss_weight with it) and clips the full gradient (dla.py:146-162);
-  // PDGD passes a FRESH model.parameters() to opt_step (pdgd.py:206-212) and clips the full gradient too.
+  // PDGD passes a FRESH model.parameters() to opt_step (pdgd.py:206-212) and clips the full gradient too.  TwoTower is the project's
+  // own algorithm and does not inherit the quirk: its clip covers the full gradient.
   float lam = 0.f;
   bool clip = u.max_gradient_norm > 0.f;
   if (u.l2_loss > 0.f && l2_sums != nullptr) {
@@ -226,7 +231,7 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
     } else {
       lam = u.l2_loss;
       loss += u.l2_loss * (0.5f * sp2);
-      clip = clip && u.algo == ULTR_ALGO_PDGD;
+      clip = clip && (u.algo == ULTR_ALGO_PDGD || u.algo == ULTR_ALGO_TWOTOWER);
     }
     norm = sqrtf(fmaxf(gs * gs * ss + 2.0f * gs * lam * sgp + lam * lam * sp2, 0.f));
   }
@@ -320,6 +325,32 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
     const float a = u.em_step_size, oma = (float)(1.0 - (double)u.em_step_size);
     const float nb = D / (float)L;  // lists in the (global) batch
     for (int l = threadIdx.x; l < L; l += 256) aux[l] = oma * aux[l] + a * (tail[ULTR_TAIL_FIXED + l] / nb);
+  } else if (u.algo == ULTR_ALGO_TWOTOWER && aux != nullptr) {
+    // the observation tower theta = aux[0 .. L): gradient tail / D, a clip of its own (as DLA's two models), the descriptor's
+    // optimizer at propensity_learning_rate with PERSISTENT state behind the ranker's (ultr_opt_state_floats): Adagrad's L
+    // accumulators at state[P], Adam's m[L] | v[L] at state[2 P]; the step count is the ranker's
+    float gsq = 0.f;
+    for (int l = threadIdx.x; l < L; l += 256) {
+      const float g = tail[ULTR_TAIL_FIXED + l] / D;
+      gsq += g * g;
+    }
+    gsq = block_sum256(gsq, sm);
+    pnorm = sqrtf(gsq);
+    const float pc = (u.max_gradient_norm > 0.f) ? fminf(1.0f, u.max_gradient_norm / (pnorm + 1e-6f)) : 1.0f;
+    for (int l = threadIdx.x; l < L; l += 256) {
+      const float g = (tail[ULTR_TAIL_FIXED + l] / D) * pc;
+      if constexpr (ADAM) {
+        float* ma = state + 2 * P;
+        float* va = ma + L;
+        float m = ma[l], v = va[l];
+        aux[l] = adam_step(aux[l], g, &m, &v, oa.step_aux, oa.rsq2, u.adagrad_eps);
+        ma[l] = m;
+        va[l] = v;
+      } else {
+        float* acc = (state != nullptr && u.optimizer != ULTR_OPT_SGD) ? state + P + l : nullptr;
+        aux[l] = opt_step(aux[l], g, acc, u.optimizer, acc == nullptr, u.propensity_learning_rate, u.adagrad_eps);
+      }
+    }
   }
   if (threadIdx.x == 0 && scalars_out != nullptr) {
     scalars_out[0] = loss;
@@ -603,12 +634,17 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
   UPD_STAMP(4);
 }
 
+// an ultr_algo value: 0 .. ULTR_ALGO_DBGD and ULTR_ALGO_TWOTOWER - the 8 between them is none (include/ultr_hip.h)
+static bool algo_known(int32_t algo) { return (algo >= 0 && algo <= ULTR_ALGO_DBGD) || algo == ULTR_ALGO_TWOTOWER; }
+
 extern "C" int64_t ultr_opt_state_floats(const ultr_update_desc* u) {
-  if (!u || u->n_params <= 0 || u->list_size <= 0 || u->algo < 0 || u->algo > ULTR_ALGO_DBGD) return -1;
+  if (!u || u->n_params <= 0 || u->list_size <= 0 || !algo_known(u->algo)) return -1;
+  const int64_t L = u->list_size;
+  const bool tower = u->algo == ULTR_ALGO_TWOTOWER;  // its observation tower keeps optimizer state of its own behind the ranker's
   switch (u->optimizer) {
     case ULTR_OPT_SGD: return 0;
-    case ULTR_OPT_ADAGRAD: return u->n_params;
-    case ULTR_OPT_ADAM: return 2 * u->n_params + (u->algo == ULTR_ALGO_DLA ? 2 * ((int64_t)u->list_size + 1) : 0);
+    case ULTR_OPT_ADAGRAD: return u->n_params + (tower ? L : 0);
+    case ULTR_OPT_ADAM: return 2 * u->n_params + (u->algo == ULTR_ALGO_DLA ? 2 * (L + 1) : tower ? 2 * L : 0);
   }
   return -1;
 }
@@ -657,7 +693,7 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
   if (wt != nullptr) {
     if (!ultr_make_dnn_plan(d, 0, &dp) || dp.P != u->n_params) return ULTR_E_BADARG;
   }
-  if (u->algo < 0 || u->algo > ULTR_ALGO_DBGD || ultr_update_check_opt(u, state)) return ULTR_E_BADARG;
+  if (!algo_known(u->algo) || ultr_update_check_opt(u, state)) return ULTR_E_BADARG;
   if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && u->algo != ULTR_ALGO_PDGD && u->algo != ULTR_ALGO_DBGD && !aux)
     return ULTR_E_BADARG;
   if (u->optimizer == ULTR_OPT_ADAGRAD && u->algo != ULTR_ALGO_DLA && !state) return ULTR_E_BADARG;

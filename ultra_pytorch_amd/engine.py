@@ -23,7 +23,7 @@ from .utils import metrics as metrics_mod
 
 ALGOS = {"softmax": _lib.ALGO_SOFTMAX, "dla": _lib.ALGO_DLA, "pairdebias": _lib.ALGO_PAIRDEBIAS,
          "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM, "prs": _lib.ALGO_PRS,
-         "pdgd": _lib.ALGO_PDGD, "dbgd": _lib.ALGO_DBGD}
+         "pdgd": _lib.ALGO_PDGD, "dbgd": _lib.ALGO_DBGD, "twotower": _lib.ALGO_TWOTOWER}
 
 
 def optimizer_id(name):
@@ -34,7 +34,8 @@ def optimizer_id(name):
 
 def opt_state_floats(algo, optimizer, list_size, n_params):
     """Floats of optimizer state (ultr_opt_state_floats; host-only) for an engine algorithm name, a grad_strategy, the list size and
-    the parameter count: SGD 0, Adagrad P, Adam 2 P (m | v) and 2 (L + 1) more for DLA's propensity parameters."""
+    the parameter count: SGD 0, Adagrad P, Adam 2 P (m | v) and 2 (L + 1) more for DLA's propensity parameters; TwoTower's observation
+    tower adds L (Adagrad) / 2 L (Adam) behind the ranker's."""
     u = _lib.UpdateDesc()
     u.algo, u.optimizer, u.list_size, u.n_params = ALGOS[algo], optimizer_id(optimizer), int(list_size), int(n_params)
     n = int(_lib.load().ultr_opt_state_floats(ctypes.byref(u)))
@@ -52,7 +53,7 @@ class StepEngine:
     def __init__(self, shape, batch, list_size, device, algo="softmax", optimizer="ada", learning_rate=0.05,
                  max_gradient_norm=5.0, ranker_loss_weight=1.0, propensity_learning_rate=None, em_step_size=0.05,
                  regulation_p=1.0, sigma=1.0, logits_to_prob="softmax", process_group=None, rng_seed=0, l2_loss=0.0,
-                 batch_total=None, comm=None, no_peer_comm=False, cutoff=None):
+                 batch_total=None, comm=None, no_peer_comm=False, cutoff=None, tower_combination="product", mask_padding=True):
         if not torch.cuda.is_available():
             raise RuntimeError("ultra_pytorch_amd needs an MI355X/ROCm GPU: there is no CPU fallback")
         self.shape, self.B, self.L, self.device = shape, int(batch), int(list_size), device
@@ -63,6 +64,12 @@ class StepEngine:
         self.algo = algo
         self.sigma = float(sigma)
         self.l2p = 1 if logits_to_prob == "sigmoid" else 0
+        if algo == "twotower":
+            # the same descriptor field carries TwoTower's combination (bit 0: sum) and mask flag (bit 1): include/ultr_hip.h
+            if tower_combination not in ("product", "sum"):
+                raise ValueError("tower_combination must be 'product' or 'sum', got %r" % (tower_combination,))
+            self.tower_combination, self.mask_padding = tower_combination, bool(mask_padding)
+            self.l2p = (_lib.TWOTOWER_SUM if tower_combination == "sum" else 0) | (_lib.TWOTOWER_MASK if mask_padding else 0)
         self.pg = process_group
         self.world = 1 if process_group is None else torch.distributed.get_world_size(process_group)
         self.rank = 0 if process_group is None else torch.distributed.get_rank(process_group)
@@ -175,6 +182,11 @@ class StepEngine:
             hip_ops.regem_loss(self.scores, labels, aux, B, L, self.dscores, self.loss_ws, uniforms=uniforms,
                                seed=self.rng_seed, step=self.rng_step)
             self.rng_step += 1
+        elif self.algo == "twotower":
+            if self.mask_padding and (docids is None or n_docs is None):
+                raise ValueError("TwoTower's loss with mask_padding needs the docids and n_docs (its PADs)")
+            hip_ops.twotower_loss(self.scores, labels, aux, B, L, self.dscores, self.loss_ws, combination=self.tower_combination,
+                                  docids=docids if self.mask_padding else None, n_docs=n_docs if self.mask_padding else 0)
         else:
             raise ValueError(self.algo)
 

@@ -618,6 +618,16 @@ def regem_loss(scores, labels, propensity, B, L, dscores, loss_ws, uniforms=None
                                       int(L), _p(dscores), _p(pseudo_out), _p(loss_ws), _stream()), "ultr_regem_loss")
 
 
+def twotower_loss(scores, labels, bias_logits, B, L, dscores, loss_ws, combination="product", docids=None, n_docs=0):
+    """TwoTower: the click log-likelihood of sigmoid(s) sigmoid(theta_l) ("product") or sigmoid(s + theta_l) ("sum"), bias_logits [L]
+    = theta.  docids [L, B] int32 with n_docs masks the PAD positions (id < 0 or >= n_docs); None: every position counts."""
+    if combination not in ("product", "sum"):
+        raise ValueError("tower_combination must be 'product' or 'sum', got %r" % (combination,))
+    check(_lib.load().ultr_twotower_loss(_p(scores), _p(labels), _p(bias_logits), _lib.TWOTOWER_SUM if combination == "sum" else 0,
+                                         _p(docids), int(n_docs), int(B), int(L), _p(dscores), _p(loss_ws), _stream()),
+          "ultr_twotower_loss")
+
+
 def apply_update(shape, udesc, params, state, grads, aux, bwd_ws, scalars):
     wt = weight_copy(shape).get(params)  # the update kernel writes the new weights into both layouts
     check(shape.lib.ultr_apply_update(ctypes.byref(udesc), ctypes.byref(shape.desc), _p(params), _p(wt), _p(state), _p(grads),

@@ -12,3 +12,4 @@ from .prs_rank import PRSrank  # noqa: F401
 from .pdgd import PDGD  # noqa: F401
 from .dbgd import DBGD, MGD  # noqa: F401
 from .nsgd import NSGD  # noqa: F401
+from .two_tower import TwoTower  # noqa: F401
