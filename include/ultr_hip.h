@@ -101,10 +101,12 @@ int64_t ultr_loss_workspace_bytes(int64_t batch, int32_t list_size);
 /* step-tail partials the stand-alone ultr_*_loss kernels leave in `loss_ws` (one per workgroup) = the n_loss_parts of
  * ultr_setrank_backward */
 int64_t ultr_loss_part_count(int64_t batch);
-/* Dynamic LDS in bytes that the stand-alone loss kernel of `algo` (ULTR_ALGO_SOFTMAX .. ULTR_ALGO_PDGD, ULTR_ALGO_TWOTOWER) requests at list_size
+/* Dynamic LDS in bytes that the stand-alone loss kernel of `algo` (ULTR_ALGO_SOFTMAX .. ULTR_ALGO_PDGD, ULTR_ALGO_TWOTOWER,
+ * ULTR_ALGO_PLRANK) requests at list_size
  * (additive within ABI 8; host-only, launches nothing) - read from the layout the kernel itself carves its LDS with
  * (csrc/ultr_listloss.h).  ULTR_E_UNSUPPORTED where the entry would refuse the list size: beyond 64 KiB for ultr_softmax_ce,
- * ultr_dla_loss, ultr_regem_loss and ultr_twotower_loss, beyond 160 KiB for ultr_pairdebias_loss, ultr_lambdarank_loss and ultr_prs_loss, beyond 256
+ * ultr_dla_loss, ultr_regem_loss and ultr_twotower_loss, beyond 160 KiB for ultr_pairdebias_loss, ultr_lambdarank_loss, ultr_prs_loss
+ * and ultr_plrank_loss, beyond 256
  * documents for ultr_pdgd_loss - the longest accepted lists are stated with each entry below.  ULTR_E_BADARG: an algorithm without a
  * stand-alone loss kernel, list_size <= 0. */
 int64_t ultr_loss_lds_bytes(int32_t algo, int32_t list_size);
@@ -279,6 +281,35 @@ int ultr_regem_loss(const float* scores, const float* labels, const float* prope
 #define ULTR_TWOTOWER_MASK 2 /* bit 1 of ultr_update_desc::logits_to_prob: ultr_train_step passes its docids to the loss */
 int ultr_twotower_loss(const float* scores, const float* labels, const float* bias_logits, int32_t combination, const int32_t* docids,
                        int64_t n_docs, int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
+
+/* ---- PLRank: Plackett-Luce policy gradient of the expected DCG@K (PL-Rank, Oosterhuis 2021; additive within ABI 8) ----
+ * The project's own counterfactual learner of a ranking metric; the law is DESIGN.md section 4d.  Per list of L positions:
+ *   valid document: docids[l, b] in [0, n_docs); a PAD is never drawn, has rho = 0 and gets dscores exactly 0;
+ *   rho_l = w_l gain(labels[l, b]),  w_l = pw[b, l] (pw != NULL), else ipw_table[min(l, n_ipw - 1)] (ipw_table != NULL), else 1;
+ *   gain 0 (ULTR_PLRANK_GAIN_LINEAR): y;  ULTR_PLRANK_GAIN_EXP2: 2^y - 1;
+ *   policy e_d = exp(s_d - max over valid s); n_samples rankings per list, each the exponential race of the online feeds at
+ *   tau = 1 (PADs staged as -inf): descending keys, the documents of fp32 probability 0 and the PADs behind the n_pos drawn ones in
+ *   index order; the race uniform of position l in sample n is word l % 4 of Philox(key(rng_seed, rng_step); b, n, l / 4,
+ *   0x504C524B);  K = cutoff (0: L),  K_eff = min(K, n_pos);
+ *   per sample, ranks from 0:  theta_k = 1 / log2(k + 2);  Z_k = sum of e over the valid documents at ranks >= k;
+ *   FR_k = sum_{x = k}^{K_eff - 1} theta_x rho_{y_x};  RI_i = sum_{k <= i} FR_k / Z_k;  DR_i = sum_{k <= i} theta_k / Z_k;
+ *   a valid document d at rank r, i = min(r, K_eff - 1):  g_d = [r < K_eff] FR_{r + 1} + e_d (rho_d DR_i - RI_i);
+ *   dscores[b, d] = -(1 / N) sum_n g_d;  step tail [-(1 / N) sum_n FR_0, 1, 0, 0, zeros]: D counts lists (the update divides).
+ * The estimator is unbiased for d E[sum_{k < K} theta_k rho_{y_k}] / d s.  No atomics: the same inputs, seed and step give the same
+ * bits.  perm_out: NULL or [B, n_samples, L] int32, the order every sample was drawn in.
+ * list_size up to 465 (160 KiB of LDS, ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched.
+ * ULTR_E_BADARG: a missing scores / labels / docids / dscores / loss_ws, batch <= 0, list_size <= 0, n_docs < 0, cutoff < 0,
+ * n_samples outside 1 .. 4095, a gain other than the two, ipw_table with n_ipw <= 0.
+ * Out of scope: data parallelism, an NDCG-normalised reward, sampling at tau != 1. */
+#define ULTR_PLRANK_GAIN_LINEAR 0
+#define ULTR_PLRANK_GAIN_EXP2 1
+#define ULTR_PLRANK_MAX_SAMPLES 4095
+/* ultr_update_desc::logits_to_prob of a ULTR_ALGO_PLRANK step: bits 0-11 min(cutoff, 4095), bits 12-23 n_samples, bit 24 the exp2 gain */
+#define ULTR_PLRANK_PACK(cutoff, n_samples, gain) \
+  ((int32_t)(((cutoff) > 4095 ? 4095 : (cutoff)) | ((n_samples) << 12) | (((gain) & 1) << 24)))
+int ultr_plrank_loss(const float* scores, const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw,
+                     const int32_t* docids, int64_t n_docs, int32_t cutoff, int32_t n_samples, int32_t gain, uint64_t rng_seed,
+                     uint64_t rng_step, int32_t batch, int32_t list_size, float* dscores, int32_t* perm_out, void* loss_ws, void* stream);
 
 /* ---- PRSrank: propensity-ratio-scored LambdaRank -------------------------------------
  * Replaces PRSrank.train's propensity + loss section (prs_rank.py:94-176) + dcg/compute_delta_ndcg
@@ -543,7 +574,11 @@ enum ultr_algo { ULTR_ALGO_SOFTMAX = 0, ULTR_ALGO_DLA = 1, ULTR_ALGO_PAIRDEBIAS 
                  ULTR_ALGO_DBGD = 7,
                  /* TwoTower (additive within ABI 8): ultr_twotower_loss, aux = the observation tower's logits [L].  The value 8 is
                   * left out and stays ULTR_E_BADARG everywhere: tests/test_adam_cpu.py holds `algo = 8` to be a bad descriptor. */
-                 ULTR_ALGO_TWOTOWER = 9 };
+                 ULTR_ALGO_TWOTOWER = 9,
+                 /* PLRank (additive within ABI 8): ultr_plrank_loss, no aux; cutoff, sample count and gain in logits_to_prob.  The
+                  * value 10 is left out as 8 is and stays ULTR_E_BADARG everywhere: tests/test_twotower_cpu.py holds `algo = 10` to
+                  * be a bad descriptor. */
+                 ULTR_ALGO_PLRANK = 11 };
 /* ULTR_OPT_ADAM: torch.optim.Adam with its defaults (no weight decay, no amsgrad), applied to the gradient Adagrad / SGD get - after
  * the 1 / D scaling, the l2_loss term and the clip.  For step t = 1, 2, ...:
  *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
@@ -559,7 +594,7 @@ typedef struct ultr_update_desc {
   int32_t optimizer;       /* ultr_opt (grad_strategy 'ada' / 'sgd' / 'adam') */
   int32_t list_size;       /* L */
   int32_t logits_to_prob;  /* DLA: 0 softmax, 1 sigmoid.  TwoTower (same field, the struct's layout is unchanged): bit 0 = the towers
-                            * combine as a sum (ULTR_TWOTOWER_SUM), bit 1 = PAD positions are masked (ULTR_TWOTOWER_MASK) */
+                            * combine as a sum (ULTR_TWOTOWER_SUM), bit 1 = PAD positions are masked (ULTR_TWOTOWER_MASK).  PLRank: ULTR_PLRANK_PACK(cutoff, n_samples, gain) */
   int64_t n_params;        /* P */
   float learning_rate;
   float max_gradient_norm; /* <= 0 disables clipping */
@@ -606,7 +641,7 @@ int64_t ultr_opt_state_floats(const ultr_update_desc* u);
 /* params/state [P] (ultr_opt_state_floats) updated in place; grads = the buffer ultr_dnn_backward filled (possibly
  * all-reduced).  ULTR_OPT_ADAM: state == NULL or adam_t == 0 is ULTR_E_BADARG (here and in ultr_train_step, before anything is
  * launched), as is an optimizer outside ultr_opt.  aux = prop_params[L+1] (DLA) or [t_plus(L) | t_minus(L)] (PairDebias /
- * LambdaRank), updated in place; NULL for SOFTMAX and PRS.  d + wt (both may be NULL): keep the k-major weight copy
+ * LambdaRank), updated in place; NULL for SOFTMAX, PRS and PLRANK.  d + wt (both may be NULL): keep the k-major weight copy
  * in sync with the updated parameters.  bwd_ws = the workspace ultr_dnn_backward (or
  * ultr_grad_sumsq) left the sum-of-squares partials in.
  * scalars_out[16]: [0] loss [1] ranker grad norm (pre-clip) [2] clip coef [3] D
@@ -653,6 +688,7 @@ typedef struct ultr_step_args {
   int32_t skip_update;
   float sigma;         /* LambdaRank / PRS; PDGD: tau */
   const float* uniforms; /* RegressionEM: [B, L] uniforms of the Bernoulli draw, or NULL = Philox(rng_seed, rng_step) */
+  /* (rng_seed / rng_step: also the key of PLRank's sampled rankings; its weights come from pw / ipw_table / n_ipw as SOFTMAX's) */
   uint64_t rng_seed;
   uint64_t rng_step;
   /* data parallel (ABI 3): with a communicator the call runs the WHOLE sharded step - backward, then ultr_comm_allreduce of

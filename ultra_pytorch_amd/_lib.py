@@ -16,6 +16,14 @@ ATTN_DTYPE = {"fp32": 0, "fp16": 1}
 ALGO_SOFTMAX, ALGO_DLA, ALGO_PAIRDEBIAS, ALGO_LAMBDARANK, ALGO_REGEM, ALGO_PRS, ALGO_PDGD, ALGO_DBGD = 0, 1, 2, 3, 4, 5, 6, 7
 ALGO_TWOTOWER = 9  # (8 is no algorithm: include/ultr_hip.h)
 TWOTOWER_SUM, TWOTOWER_MASK = 1, 2  # ultr_twotower_loss's combination; bits of ultr_update_desc::logits_to_prob
+ALGO_PLRANK = 11  # (10 is no algorithm either)
+PLRANK_GAIN = {"linear": 0, "exp2": 1}  # ULTR_PLRANK_GAIN_*
+PLRANK_MAX_SAMPLES = 4095
+
+
+def plrank_pack(cutoff, n_samples, gain):
+    """ULTR_PLRANK_PACK: what ultr_update_desc::logits_to_prob carries for a PLRank step (bits 0-11 cutoff, 12-23 samples, 24 exp2)."""
+    return min(int(cutoff), 4095) | (int(n_samples) << 12) | (PLRANK_GAIN[gain] << 24)
 OPT_ADAGRAD, OPT_SGD, OPT_ADAM = 0, 1, 2
 ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-8  # include/ultr_hip.h: ULTR_ADAM_*
 
@@ -185,6 +193,8 @@ SIGNATURES = {
     "ultr_prs_loss_pw_long": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_regem_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "ultr_twotower_loss": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "ultr_plrank_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint64,
+                                 c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "ultr_setrank_param_count": (c_i64, [ctypes.POINTER(SetRankDesc)]),
     "ultr_setrank_saved_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
     "ultr_setrank_workspace_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),

@@ -1,4 +1,5 @@
-// ultr_listloss.h — what the eight list-loss kernels share (ultr_loss.hip, ultr_prs.hip, ultr_pdgd.hip, ultr_twotower.hip):
+// ultr_listloss.h — what the nine list-loss kernels share (ultr_loss.hip, ultr_prs.hip, ultr_pdgd.hip, ultr_twotower.hip,
+// ultr_plrank.hip):
 //   * one LDS layout per kernel, a __host__ __device__ struct built from L: the kernel takes its pointers from the offsets, the
 //     launcher and ultr_loss_lds_bytes take `bytes` - the two sides cannot drift apart;
 //   * launch_list_loss, the one launcher behind the extern "C" entries;
@@ -134,6 +135,28 @@ struct PdgdLds : LdsCarve {  // list_size <= PDGD_MAX_L (the entry refuses beyon
   __host__ __device__ explicit PdgdLds(int L_) : LdsCarve(L_) {}
 };
 
+// ultr_plrank.hip: what a list stages once, and per wave (LOSS_JW waves share a list, each draws its own samples) the race keys, the
+// drawn order, the two backward scans and the private partial gradient.  88 L + 37 words: list_size <= 465
+struct PlRankLds : LdsCarve {  // list_size <= 465
+  static constexpr int64_t limit = LOSS_LDS_MAX;
+  int tail = per_list(ultr_tail_len(L));          // [LPW][tail]
+  int s = per_list(L);                            // [LPW][L] scores, -inf at a PAD
+  int rho = per_list(L);                          // [LPW][L] relevance estimates w gain(y), 0 at a PAD
+  int ea = per_list(L);                           // [LPW][L] exp(s - max) scaled, in two factors (ultr_plrank.hip): 0 at a PAD
+  int eb = per_list(L);                           // [LPW][L]
+  int v = per_list(L);                            // [LPW][L] int: 1 = a valid document
+  int hdr = per_list(1);                          // [LPW] int: the list's valid documents
+  int d = take(L);                                // [L] discount 1 / log2(rank + 2)
+  int red = per_list(LOSS_JW);                    // [LPW][LOSS_JW] each wave's sum of FR_0 over its samples
+  int key = per_list((int64_t)LOSS_JW * L);       // [LPW][LOSS_JW][L] unsigned: race keys
+  int perm = per_list((int64_t)LOSS_JW * L);      // [LPW][LOSS_JW][L] int: document at each rank
+  int z = per_list((int64_t)LOSS_JW * L);         // [LPW][LOSS_JW][L] Z_k
+  int fr = per_list((int64_t)LOSS_JW * (L + 1));  // [LPW][LOSS_JW][L + 1] FR_k, FR_L = 0
+  int acc = per_list((int64_t)LOSS_JW * L);       // [LPW][LOSS_JW][L] the wave's partial gradient by document
+  int64_t bytes = end();
+  __host__ __device__ explicit PlRankLds(int L_) : LdsCarve(L_) {}
+};
+
 // The long-list kernels (ultr_loss_long.hip): the workgroup's LOSS_LONG_WAVES waves split the OWNED positions, each lane walks every
 // partner, so the sums per position stay in registers and no [LOSS_JW][L][NV] array exists: O(L) floats of LDS.  One list per workgroup.
 #define LOSS_LONG_WAVES 16
@@ -212,6 +235,7 @@ static inline bool loss_short_refuses(int algo, int L) {
 static inline int loss_route(int algo, int L) {
   // TwoTower has the one kernel: a list beyond its layout is refused here, before the forward is launched
   if (algo == ULTR_ALGO_TWOTOWER && L > 0 && TwoTowerLds(L).bytes > TwoTowerLds::limit) return ULTR_E_UNSUPPORTED;
+  if (algo == ULTR_ALGO_PLRANK && L > 0 && PlRankLds(L).bytes > PlRankLds::limit) return ULTR_E_UNSUPPORTED;  // PLRank likewise
   if (!loss_short_refuses(algo, L)) return LOSS_ROUTE_SHORT;
   return loss_long_bytes(algo, L) >= 0 ? LOSS_ROUTE_LONG : ULTR_E_UNSUPPORTED;
 }

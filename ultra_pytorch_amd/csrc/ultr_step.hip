@@ -119,6 +119,12 @@ int ultr_train_step_ctx(const ultr_step_args* a, StepCtx* ctx, void* stream) {
                               (a->upd->logits_to_prob & ULTR_TWOTOWER_MASK) ? a->docids : nullptr, a->n_docs, a->batch, a->list_size,
                               a->dscores, a->loss_ws, stream);
       break;
+    case ULTR_ALGO_PLRANK: {  // cutoff, sample count and gain travel in logits_to_prob (ULTR_PLRANK_PACK, include/ultr_hip.h)
+      const int32_t pk = a->upd->logits_to_prob;
+      rc = ultr_plrank_loss(a->scores, a->labels, a->pw, a->ipw_table, a->n_ipw, a->docids, a->n_docs, pk & 0xFFF, (pk >> 12) & 0xFFF,
+                            (pk >> 24) & 1, a->rng_seed, a->rng_step, a->batch, a->list_size, a->dscores, nullptr, a->loss_ws, stream);
+      break;
+    }
     default:
       return ULTR_E_BADARG;
   }

@@ -208,6 +208,10 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
       gs = 1.0f / D;
       loss = loss_sum / D;
       break;
+    case ULTR_ALGO_PLRANK:  // minus the sampled expected DCG@K, mean over the D lists (ultr_plrank.hip)
+      gs = 1.0f / D;
+      loss = loss_sum / D;
+      break;
     case ULTR_ALGO_PDGD:  // the weighted pair terms are summed (pdgd.py:197-205)
     case ULTR_ALGO_DBGD:  // grads already hold the step's direction; the loss is 1 - NDCG of the current model (dbgd.py:140)
       gs = 1.0f;
@@ -218,8 +222,8 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
   // l2_loss > 0 (ipw_rank.py:154-157 and siblings): g += lam * p, loss += l2_loss * sum p^2 / 2.  Every algorithm but DLA
   // and PDGD hands clip_grad_norm_ a parameter generator the L2 loop has already exhausted, so NOTHING is clipped (Appendix
   // A.8); DLA adds the term to rank_loss (scaled by ranker_loss_weight with it) and clips the full gradient (dla.py:146-162);
-  // PDGD passes a FRESH model.parameters() to opt_step (pdgd.py:206-212) and clips the full gradient too.  TwoTower is the project's
-  // own algorithm and does not inherit the quirk: its clip covers the full gradient.
+  // PDGD passes a FRESH model.parameters() to opt_step (pdgd.py:206-212) and clips the full gradient too.  TwoTower and PLRank are the
+  // project's own algorithms and do not inherit the quirk: their clip covers the full gradient.
   float lam = 0.f;
   bool clip = u.max_gradient_norm > 0.f;
   if (u.l2_loss > 0.f && l2_sums != nullptr) {
@@ -231,7 +235,7 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
     } else {
       lam = u.l2_loss;
       loss += u.l2_loss * (0.5f * sp2);
-      clip = clip && (u.algo == ULTR_ALGO_PDGD || u.algo == ULTR_ALGO_TWOTOWER);
+      clip = clip && (u.algo == ULTR_ALGO_PDGD || u.algo == ULTR_ALGO_TWOTOWER || u.algo == ULTR_ALGO_PLRANK);
     }
     norm = sqrtf(fmaxf(gs * gs * ss + 2.0f * gs * lam * sgp + lam * lam * sp2, 0.f));
   }
@@ -634,8 +638,11 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
   UPD_STAMP(4);
 }
 
-// an ultr_algo value: 0 .. ULTR_ALGO_DBGD and ULTR_ALGO_TWOTOWER - the 8 between them is none (include/ultr_hip.h)
-static bool algo_known(int32_t algo) { return (algo >= 0 && algo <= ULTR_ALGO_DBGD) || algo == ULTR_ALGO_TWOTOWER; }
+// an ultr_algo value: 0 .. ULTR_ALGO_DBGD, ULTR_ALGO_TWOTOWER and ULTR_ALGO_PLRANK - the 8 and the 10 between them are none
+// (include/ultr_hip.h)
+static bool algo_known(int32_t algo) {
+  return (algo >= 0 && algo <= ULTR_ALGO_DBGD) || algo == ULTR_ALGO_TWOTOWER || algo == ULTR_ALGO_PLRANK;
+}
 
 extern "C" int64_t ultr_opt_state_floats(const ultr_update_desc* u) {
   if (!u || u->n_params <= 0 || u->list_size <= 0 || !algo_known(u->algo)) return -1;
@@ -694,7 +701,8 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
     if (!ultr_make_dnn_plan(d, 0, &dp) || dp.P != u->n_params) return ULTR_E_BADARG;
   }
   if (!algo_known(u->algo) || ultr_update_check_opt(u, state)) return ULTR_E_BADARG;
-  if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && u->algo != ULTR_ALGO_PDGD && u->algo != ULTR_ALGO_DBGD && !aux)
+  if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && u->algo != ULTR_ALGO_PDGD && u->algo != ULTR_ALGO_DBGD &&
+      u->algo != ULTR_ALGO_PLRANK && !aux)
     return ULTR_E_BADARG;
   if (u->optimizer == ULTR_OPT_ADAGRAD && u->algo != ULTR_ALGO_DLA && !state) return ULTR_E_BADARG;
   if (u->l2_loss < 0.f || (u->l2_loss > 0.f && !scalars_out) ||

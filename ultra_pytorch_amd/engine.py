@@ -23,7 +23,7 @@ from .utils import metrics as metrics_mod
 
 ALGOS = {"softmax": _lib.ALGO_SOFTMAX, "dla": _lib.ALGO_DLA, "pairdebias": _lib.ALGO_PAIRDEBIAS,
          "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM, "prs": _lib.ALGO_PRS,
-         "pdgd": _lib.ALGO_PDGD, "dbgd": _lib.ALGO_DBGD, "twotower": _lib.ALGO_TWOTOWER}
+         "pdgd": _lib.ALGO_PDGD, "dbgd": _lib.ALGO_DBGD, "twotower": _lib.ALGO_TWOTOWER, "plrank": _lib.ALGO_PLRANK}
 
 
 def optimizer_id(name):
@@ -53,7 +53,8 @@ class StepEngine:
     def __init__(self, shape, batch, list_size, device, algo="softmax", optimizer="ada", learning_rate=0.05,
                  max_gradient_norm=5.0, ranker_loss_weight=1.0, propensity_learning_rate=None, em_step_size=0.05,
                  regulation_p=1.0, sigma=1.0, logits_to_prob="softmax", process_group=None, rng_seed=0, l2_loss=0.0,
-                 batch_total=None, comm=None, no_peer_comm=False, cutoff=None, tower_combination="product", mask_padding=True):
+                 batch_total=None, comm=None, no_peer_comm=False, cutoff=None, tower_combination="product", mask_padding=True,
+                 num_samples=64, gain="linear"):
         if not torch.cuda.is_available():
             raise RuntimeError("ultra_pytorch_amd needs an MI355X/ROCm GPU: there is no CPU fallback")
         self.shape, self.B, self.L, self.device = shape, int(batch), int(list_size), device
@@ -70,6 +71,18 @@ class StepEngine:
                 raise ValueError("tower_combination must be 'product' or 'sum', got %r" % (tower_combination,))
             self.tower_combination, self.mask_padding = tower_combination, bool(mask_padding)
             self.l2p = (_lib.TWOTOWER_SUM if tower_combination == "sum" else 0) | (_lib.TWOTOWER_MASK if mask_padding else 0)
+        if algo == "plrank":
+            # the sampled Plackett-Luce policy gradient: cutoff (None / 0: the whole list), samples per list and gain ride in the same
+            # descriptor field (ULTR_PLRANK_PACK, include/ultr_hip.h); the draw's key is (rng_seed, the step set_draw_step hands in)
+            if process_group is not None:
+                raise NotImplementedError("PLRank does not train data parallel")
+            if gain not in _lib.PLRANK_GAIN:
+                raise ValueError("gain must be one of %s, got %r" % (sorted(_lib.PLRANK_GAIN), gain))
+            if not 1 <= int(num_samples) <= _lib.PLRANK_MAX_SAMPLES:
+                raise ValueError("num_samples must be in 1 .. %d, got %r" % (_lib.PLRANK_MAX_SAMPLES, num_samples))
+            self.cutoff = 0 if cutoff is None else max(int(cutoff), 0)
+            self.num_samples, self.gain = int(num_samples), gain
+            self.l2p = _lib.plrank_pack(self.cutoff, self.num_samples, gain)
         self.pg = process_group
         self.world = 1 if process_group is None else torch.distributed.get_world_size(process_group)
         self.rank = 0 if process_group is None else torch.distributed.get_rank(process_group)
@@ -187,8 +200,20 @@ class StepEngine:
                 raise ValueError("TwoTower's loss with mask_padding needs the docids and n_docs (its PADs)")
             hip_ops.twotower_loss(self.scores, labels, aux, B, L, self.dscores, self.loss_ws, combination=self.tower_combination,
                                   docids=docids if self.mask_padding else None, n_docs=n_docs if self.mask_padding else 0)
+        elif self.algo == "plrank":
+            if docids is None or n_docs is None:
+                raise ValueError("PLRank's loss needs the docids and n_docs (its PADs)")
+            self._loss_is_long()  # (raises for a list beyond the kernel's layout, before anything is launched)
+            hip_ops.plrank_loss(self.scores, labels, docids, n_docs, B, L, self.dscores, self.loss_ws, n_samples=self.num_samples,
+                                cutoff=self.cutoff, gain=self.gain, seed=self.rng_seed, step=self.rng_step, pw=pw, ipw_table=ipw_table)
         else:
             raise ValueError(self.algo)
+
+    def set_draw_step(self, step):
+        """PLRank: the step of the key (rng_seed, step) the NEXT train_step / loss draws its rankings under.  As Adam's t it is counted
+        by the owner of the model, not here: engines are cached per (batch, list size) and evicted, a count of theirs would replay
+        samples."""
+        self.rng_step = int(step)
 
     def _loss_is_long(self):
         """hip_ops.loss_route of this engine's algorithm and list size, asked once (raises for a list neither kernel takes)."""
@@ -357,6 +382,8 @@ class StepEngine:
             a.uniforms = uniforms.data_ptr() if uniforms is not None else None
             a.rng_seed, a.rng_step = self.rng_seed, self.rng_step
             self.rng_step += 1
+        elif self.algo == "plrank":
+            a.rng_seed, a.rng_step = self.rng_seed, self.rng_step  # (set_draw_step: the owner counts)
         if self.comm is not None:
             a.comm_step = self.comm.step
             self.comm.step += 1

@@ -628,6 +628,23 @@ def twotower_loss(scores, labels, bias_logits, B, L, dscores, loss_ws, combinati
           "ultr_twotower_loss")
 
 
+def plrank_loss(scores, labels, docids, n_docs, B, L, dscores, loss_ws, n_samples=64, cutoff=0, gain="linear", seed=0, step=0, pw=None,
+                ipw_table=None, perm_out=None):
+    """PLRank: the sampled Plackett-Luce policy gradient of the expected DCG@cutoff (0: the whole list) from n_samples rankings per
+    list, drawn under Philox(seed, step).  Relevance estimates rho = w * gain(labels): w from pw [B, L], else ipw_table (the IPW_list),
+    else 1; gain "linear" or "exp2".  docids [L, B] int32 with n_docs mark the PADs.  perm_out [B, n_samples, L] int32 (optional)
+    receives the sampled orders."""
+    if gain not in _lib.PLRANK_GAIN:
+        raise ValueError("gain must be one of %s, got %r" % (sorted(_lib.PLRANK_GAIN), gain))
+    if perm_out is not None:
+        _req(perm_out, torch.int32, "perm_out")
+    n_ipw = 0 if ipw_table is None else int(ipw_table.numel())
+    check(_lib.load().ultr_plrank_loss(_p(scores), _p(labels), _p(pw), _p(ipw_table), n_ipw, _p(docids), int(n_docs), int(cutoff),
+                                       int(n_samples), _lib.PLRANK_GAIN[gain], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                       int(step) & 0xFFFFFFFFFFFFFFFF, int(B), int(L), _p(dscores), _p(perm_out), _p(loss_ws),
+                                       _stream()), "ultr_plrank_loss")
+
+
 def apply_update(shape, udesc, params, state, grads, aux, bwd_ws, scalars):
     wt = weight_copy(shape).get(params)  # the update kernel writes the new weights into both layouts
     check(shape.lib.ultr_apply_update(ctypes.byref(udesc), ctypes.byref(shape.desc), _p(params), _p(wt), _p(state), _p(grads),

@@ -13,3 +13,4 @@ from .pdgd import PDGD  # noqa: F401
 from .dbgd import DBGD, MGD  # noqa: F401
 from .nsgd import NSGD  # noqa: F401
 from .two_tower import TwoTower  # noqa: F401
+from .pl_rank import PLRank  # noqa: F401
