@@ -116,7 +116,15 @@ int64_t ultr_loss_lds_bytes(int32_t algo, int32_t list_size);
  * and DNN.build (DNN.py:58-88): np.take of feature rows (zero PAD row for id == n_docs),
  * then [LayerNorm -> Linear -> act] x k -> LayerNorm -> Linear(.,1), scores as [B, L].
  * saved == NULL: inference (validation) forward; otherwise activations and LayerNorm
- * statistics are kept for ultr_dnn_backward. */
+ * statistics are kept for ultr_dnn_backward.
+ * The operand contract (one rule for every DNN entry point; ultr_dnn_route_operands answers for it):
+ *   params, features: any 4-byte aligned address (a slice of a larger buffer, a candidate vector at any stride).  On a 16-byte
+ *     boundary the kernels take float4 loads, off it the scalar builds of the same kernels; the results agree to rounding.
+ *   wt: NULL, or the buffer ultr_dnn_build_wt filled.  Every kernel that reads it uses 16-byte loads, so a copy that is NOT on a
+ *     16-byte boundary counts as ABSENT wherever it is only read: here, in ultr_dnn_forward_ndcg / _metrics and in the backward
+ *     stages of ultr_train_step.  The calls that must WRITE it - ultr_apply_update, ultr_train_step - refuse it with
+ *     ULTR_E_BADARG before anything is launched.  wt == NULL is accepted everywhere: the generic kernels read W directly.
+ *   the other buffers (scores, saved, dscores, workspaces, grads) are the library's own sizes at allocator alignment (16 bytes). */
 int ultr_dnn_forward(const ultr_dnn_desc* d, const float* params, const float* wt, const float* features,
                      int64_t n_docs, const int32_t* docids, int32_t batch, int32_t list_size, float* scores,
                      void* saved, void* stream);
@@ -137,7 +145,8 @@ int ultr_dnn_wt_range(const ultr_dnn_desc* d, const float* wt, void* stream);
 /* Which kernels a call takes (additive within ABI 8; host-only, launches nothing): the route ultr_dnn_forward, ultr_dnn_backward,
  * ultr_dnn_backward_softmax and the fused step decide once per call - the queries below read the same function - at batch x list_size
  * rows gathered from n_docs documents, under the knobs as last read (ultr_config_reload), for what ultr_train_step and the evaluation
- * always pass: 16-byte aligned pointers and the weight copies present; with the CU count the planners read (256 where no device
+ * always pass: 16-byte aligned pointers, the weight copies present and a dscores buffer (ultr_dnn_route_operands takes these
+ * facts as an argument); with the CU count the planners read (256 where no device
  * answers).  ULTR_E_UNSUPPORTED where the call itself would refuse (`out` is filled, the family that refuses is ULTR_DNN_UNSUPPORTED);
  * ULTR_E_BADARG: a bad desc, a NULL out, batch <= 0, list_size <= 0, n_docs < 0 or an unknown `call`. */
 enum ultr_dnn_route_call {
@@ -170,6 +179,21 @@ typedef struct ultr_dnn_route_info {
   int32_t reserved[5];        /* 0 */
 } ultr_dnn_route_info;
 int ultr_dnn_route(const ultr_dnn_desc* d, int32_t batch, int32_t list_size, int64_t n_docs, int32_t call, ultr_dnn_route_info* out);
+/* The same for any operands (additive within ABI 8): `operands` = the ULTR_DNN_OP_ bits of what the call passes; ultr_dnn_route is
+ * ULTR_DNN_OP_ALL.  PARAMS16 / FEATURES16: that pointer is on a 16-byte boundary.  WT: the weight copies are passed; WT16: they are
+ * on a 16-byte boundary - by the operand contract (ultr_dnn_forward) a copy off it counts as absent, so clearing either bit gives
+ * the same route.  DSCORES: a [B, L] dscores buffer exists (ultr_dnn_backward_softmax's dscores_out, ultr_step_args::dscores);
+ * without one the softmax loss runs in the backward kernel's prologue, which the wide-tile and per-layer backward do not have.
+ * The public ultr_dnn_backward / ultr_dnn_backward_softmax never see the copies: their route is the step's with WT clear.
+ * ULTR_E_BADARG also for a bit outside ULTR_DNN_OP_ALL. */
+#define ULTR_DNN_OP_PARAMS16 1u
+#define ULTR_DNN_OP_FEATURES16 2u
+#define ULTR_DNN_OP_WT 4u
+#define ULTR_DNN_OP_WT16 8u
+#define ULTR_DNN_OP_DSCORES 16u
+#define ULTR_DNN_OP_ALL 31u
+int ultr_dnn_route_operands(const ultr_dnn_desc* d, int32_t batch, int32_t list_size, int64_t n_docs, int32_t call, uint32_t operands,
+                            ultr_dnn_route_info* out);
 /* The older queries, views of the same route (for tests, tools and the bench line).  Which forward kernel ultr_dnn_forward launches
  * for n_rows = batch x list_size rows: 16 / 32 = dnn_fwd_kernel with that many rows per workgroup, 1000 + R = the wide-tile kernel
  * dnn_fwdw_kernel with R = 17 .. 64 rows per workgroup, 0 = the per-layer path (training forward only), < 0 = bad descriptor.
@@ -647,7 +671,9 @@ int64_t ultr_opt_state_floats(const ultr_update_desc* u);
  * scalars_out[16]: [0] loss [1] ranker grad norm (pre-clip) [2] clip coef [3] D
  *                  [4] rank_loss (DLA) [5] exam_loss (DLA) [6] propensity grad norm (DLA; TwoTower: the observation tower's,
  *                  pre-clip) [7] sum g^2
- *                  [8] sum p^2  [9] sum g.p  (written by a pre-pass only when l2_loss > 0)  [10..16) reserved */
+ *                  [8] sum p^2  [9] sum g.p  (written by a pre-pass only when l2_loss > 0)  [10..16) reserved
+ * wt: NULL (only params are written), or the copies on a 16-byte boundary; one off it is refused with ULTR_E_BADARG and nothing
+ * is launched (the operand contract, ultr_dnn_forward).  params needs 4-byte alignment only. */
 int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state,
                       const float* grads, float* aux, const void* bwd_ws, float* scalars_out, void* stream);
 
@@ -660,7 +686,11 @@ int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc* d, float* 
  * ipw_table / n_ipw: the IPW_list of IPW (SOFTMAX) and PRS; pw: explicit [B, L] weights instead (SOFTMAX: ultr_softmax_ce's pw;
  * PRS: ultr_prs_loss_pw's ipw_bl).  sigma: LambdaRank and PRS.
  * PDGD (no IPW table, no sigma): sigma carries tau and n_ipw the cutoff (selection_bias_cutoff); docids / n_docs mark
- * the PADs. */
+ * the PADs.
+ * wt: the weight copies on a 16-byte boundary, or NULL - every algorithm then runs the separate forward / backward calls on the
+ * generic kernels (SOFTMAX included: the fused launch needs the copies) and the update writes params only.  A wt off a 16-byte
+ * boundary: ULTR_E_BADARG before anything is launched, skip_update or not (the operand contract, ultr_dnn_forward).  params and
+ * features need 4-byte alignment only. */
 typedef struct ultr_step_args {
   const ultr_dnn_desc* desc;
   const ultr_update_desc* upd;

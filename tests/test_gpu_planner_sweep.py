@@ -6,7 +6,8 @@ RandomState(0) around every boundary - rows per workgroup 16 / 17, 48 / 49, 64 /
 255 / 256 / 257 and 511 / 512 / 513, feature sizes that are not multiples of 4, zero to four hidden layers, list sizes 1, 9, 10, 17,
 100, 101, PAD documents (rank_list_size < max_candidate_num), training and evaluation - each runs ONE product step
 (engine.StepEngine.train_step = ultr_train_step) against oracle.ultr_oracle at the golden tolerances (loss 1e-5, scores 1e-5,
-gradients 1e-5 (|g| + sum |terms|) per entry), or one evaluation forward (scores 1e-5).  Three tiny shapes behind the drawn ones reach
+gradients 1e-5 (|g| + sum |terms|) per entry, ReLU included: its cases draw their feature rows away from the kinks, tests/dnn_ref.py),
+or one evaluation forward (scores 1e-5).  Three tiny shapes behind the drawn ones reach
 the fused launch on 8 and on 16 waves and its neighbour one document past the 16-row tile.  The sweep asserts that it reached every
 kernel family (ultr_dnn_route, the route the entry points themselves decide, says what a case launches).
 Reference: DNN.py:18-56 (any widths, any depth), base_algorithm.py:118-154, ipw_rank.py:102-182."""
@@ -86,6 +87,14 @@ def test_one_step_against_the_oracle(c):
     for n, s, o in O.param_layout(F, hidden):  # LayerNorm affine parameters away from (1, 0)
         if "layer_norm" in n:
             params[o:o + int(np.prod(s))] += rng.normal(scale=0.2, size=int(np.prod(s))).astype(np.float32)
+    if act == "relu" and hidden:
+        # ReLU's derivative is a step: a pre-activation within fp32 rounding of zero lands on either side of it under another
+        # summation order, and each flip moves gradient entries by a whole term.  That is a property of the inputs, not of a kernel:
+        # the feature rows with such a unit are redrawn (tests/dnn_ref.py: |z| <= (K_j + 16) 2^-23 S, the derivation is there), and
+        # the case is held to the per-entry bar of every other activation
+        from tests import dnn_ref
+        feats, params, share = dnn_ref.condition_relu(rng, params, F, hidden, feats, ids)
+        print("relu case %02d: %.1f%% of the feature rows redrawn" % (c["k"], 100 * share))
     for fam in families(c):
         SEEN[fam] = SEEN.get(fam, 0) + 1
     shape = hip_ops.DnnShape(F, hidden, act)
@@ -114,13 +123,10 @@ def test_one_step_against_the_oracle(c):
         (dsc,) = torch.autograd.grad(O.softmax_loss(s_t, lab, torch.from_numpy(ref["pw"]) if ref["pw"] is not None else None), s_t)
         terms = O.dnn_backward_manual(params, F, hidden, x, dsc.numpy().reshape(-1), act, abs_terms=True)
         d = np.abs(g - gref)
+        ratio = float((d / (1e-5 * (np.abs(gref) + terms) + 1e-12)).max())
         if act == "relu":
-            # ReLU's derivative is a step: among ~10^6 pre-activations a few sit within an ulp of zero and land on the other side of
-            # it under another summation order (the reference's own 1-thread and 8-thread runs do the same), each flip moves a few
-            # gradient entries by a whole term (layers below a flipped unit: every entry a little).  Held to 2e-3 of the largest entry.
-            assert d.max() <= 2e-3 * np.abs(gref).max(), (float(d.max()), float(np.abs(gref).max()))
-        else:
-            assert (d <= 1e-5 * (np.abs(gref) + terms) + 1e-12).all(), float((d / np.maximum(np.abs(gref) + terms, 1e-30)).max())
+            print("relu case %02d: largest gradient error / bar = %.3f" % (c["k"], ratio))
+        assert ratio <= 1.0, ratio
         eng.close()
     else:
         prop = (0.1 * rng.randn(L + 1)).astype(np.float32)

@@ -43,6 +43,9 @@ class DnnRouteInfo(ctypes.Structure):  # ultr_dnn_route_info (ultr_dnn_route)
 DNN_CALLS = ("eval", "step_softmax", "step_dscores")  # include/ultr_hip.h: ultr_dnn_route_call
 DNN_FAMILIES = ("none", "tile", "tile2", "wide", "per_layer", "fused", "unsupported")  # ultr_dnn_family
 DNN_LOSS_PLACES = ("none", "launch", "prologue", "fused")  # ultr_dnn_loss_place
+# ULTR_DNN_OP_*: what a call passes (ultr_dnn_route_operands); a weight copy off a 16-byte boundary counts as absent
+DNN_OPERANDS = {"params16": 1, "features16": 2, "wt": 4, "wt16": 8, "dscores": 16}
+DNN_OP_ALL = 31
 
 MODEL_FP32_PRODUCTS = 1  # ultr_dnn_desc / ultr_setrank_desc ::flags (include/ultr_hip.h, ABI 6)
 MODEL_SR_STREAM_BWD = 2  # ultr_setrank_desc::flags: the streaming attention backward beyond the one-pass kernels' list bounds
@@ -173,6 +176,8 @@ SIGNATURES = {
     "ultr_dnn_backward_tile_rows": (c_i32, [ctypes.POINTER(DnnDesc), c_i64]),
     "ultr_fused_fb_waves": (c_i32, [ctypes.POINTER(DnnDesc), c_i32, c_i32]),
     "ultr_dnn_route": (c_i32, [ctypes.POINTER(DnnDesc), c_i32, c_i32, c_i64, c_i32, ctypes.POINTER(DnnRouteInfo)]),
+    "ultr_dnn_route_operands": (c_i32, [ctypes.POINTER(DnnDesc), c_i32, c_i32, c_i64, c_i32, ctypes.c_uint32,
+                                        ctypes.POINTER(DnnRouteInfo)]),
     "ultr_dnn_backward": (c_i32, [ctypes.POINTER(DnnDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp]),
     "ultr_dnn_backward_softmax": (c_i32, [ctypes.POINTER(DnnDesc), c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,

@@ -421,10 +421,11 @@ static int vecmask_for(const DnnPlan& p, const DnnOperands& o) {
   if (o.features16 && p.K[0] % 4 == 0) mask |= (1u << 31);
   return mask;
 }
-static bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-// what a call knows of its operands (dscores: the buffer a separate loss launch writes, or the caller's own)
+// what a call knows of its operands (wt: what ultr_readable_wt left of the caller's; dscores: the buffer a separate loss launch
+// writes, or the caller's own)
 static DnnOperands operands_of(const float* params, const float* features, const float* wt, const float* dscores) {
-  return DnnOperands{aligned16(params), features != nullptr && aligned16(features), wt != nullptr, aligned16(wt), dscores != nullptr};
+  return DnnOperands{ultr_aligned16(params), features != nullptr && ultr_aligned16(features), ultr_readable_wt(wt) != nullptr,
+                     dscores != nullptr};
 }
 
 extern "C" int64_t ultr_dnn_param_count(const ultr_dnn_desc* d) {
@@ -707,7 +708,7 @@ static DnnRoute dnn_route(const DnnPlan& p, int64_t batch, int L, int64_t n_docs
   r.av = all_vec(p, r.vm, N, n_docs) && k.no_vec == 0;
   if (call == DNN_EVAL_FWD || call == DNN_TRAIN_FWD) {
     // the fast paths need the k-major weight copy (ultr_dnn_build_wt / kept current by ultr_apply_update)
-    r.av = r.av && (o.wt || p.nl == 1) && o.wt16;
+    r.av = r.av && (o.wt || p.nl == 1);
     r.fwd_rows = fwd_rows_per_wg(); r.fwd_nw = k.fwd_nw; r.fwd_lds = fwd_lds_bytes(p, r.fwd_rows);
     if (call == DNN_TRAIN_FWD && o.wt && r.av && ultr_dnn_big_ok(p, N, n_docs) && k.big_fwd != 0 &&
         (big_fwd_wanted(p, N, r.fwd_lds) || r.fwd_lds > cap)) {
@@ -727,7 +728,7 @@ static DnnRoute dnn_route(const DnnPlan& p, int64_t batch, int L, int64_t n_docs
   }
   r.g = bwd_geom(p, N, r.av); r.bwd_nw = k.bwd_nw;
   if (call == DNN_STEP_SOFTMAX) {
-    r.fb_waves = fused_fb_waves(p, r.av && o.wt && o.wt16, batch, L, &r.fb_lds);
+    r.fb_waves = fused_fb_waves(p, r.av && o.wt, batch, L, &r.fb_lds);
     if (r.fb_waves == 0) return r;  // the separate calls
     r.fb_lpb = 16 / L; r.fb_blocks = (batch + r.fb_lpb - 1) / r.fb_lpb;
     r.fwd = r.bwd = ULTR_DNN_FUSED; r.fwd_rows = r.fb_lpb * L; r.loss = ULTR_DNN_LOSS_FUSED;
@@ -742,7 +743,7 @@ static DnnRoute dnn_route(const DnnPlan& p, int64_t batch, int L, int64_t n_docs
   const bool big = by_dscores && ultr_dnn_big_ok(p, N, n_docs) && k.big_bwd != 0 && (big_bwd_wanted(N, v2) || lds > cap);
   if (ultr_tail_len(L) > 4096 || (lds > cap && !big)) {
     r.bwd = ULTR_DNN_UNSUPPORTED;
-  } else if (by_dscores && o.wt && o.wt16 && bwd_wide_plan(p, N, &r.wb, &wlds)) {
+  } else if (by_dscores && o.wt && bwd_wide_plan(p, N, &r.wb, &wlds)) {
     r.bwd = ULTR_DNN_WIDE; r.g.rblk = r.wb.R;
     r.g.nrb = (int)((N + r.wb.R - 1) / r.wb.R);  // one vector slab per workgroup
   } else if (big) {
@@ -761,6 +762,7 @@ extern "C" int ultr_dnn_forward(const ultr_dnn_desc* d, const float* params, con
                                 void* saved, void* stream) {
   if (!params || !docids || !scores || batch <= 0 || list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features))
     return ULTR_E_BADARG;
+  wt = ultr_readable_wt(wt);
   DnnPlan p;
   if (!ultr_make_dnn_plan(d, (int64_t)batch * list_size, &p)) return ULTR_E_BADARG;
   const DnnRoute r = dnn_route(p, batch, list_size, n_docs, operands_of(params, features, wt, nullptr), saved ? DNN_TRAIN_FWD : DNN_EVAL_FWD);
@@ -805,39 +807,48 @@ extern "C" int ultr_dnn_forward_metrics(const ultr_dnn_desc* d, const float* par
                              masked_out, ws, counter, host_report, seq, stream);
 }
 
-// ---- the queries: the route of a call with 16-byte aligned operands and the weight copies present (include/ultr_hip.h) ----
-static bool route_query(const ultr_dnn_desc* d, int64_t batch, int L, int64_t n_docs, DnnCall call, DnnRoute* r) {
+// ---- the queries: the route of a call (include/ultr_hip.h); the older ones answer for 16-byte aligned operands, the weight copies
+// present and a dscores buffer ----
+static const DnnOperands ALL_OPERANDS = {true, true, true, true};
+static bool route_query(const ultr_dnn_desc* d, int64_t batch, int L, int64_t n_docs, DnnCall call, const DnnOperands& o, DnnRoute* r) {
   DnnPlan p;
   if (batch <= 0 || L <= 0 || n_docs < 0 || !ultr_make_dnn_plan(d, batch * L, &p)) return false;
-  *r = dnn_route(p, batch, L, n_docs, DnnOperands{true, true, true, true, true}, call);
+  *r = dnn_route(p, batch, L, n_docs, o, call);
   return true;
 }
-extern "C" int ultr_dnn_route(const ultr_dnn_desc* d, int32_t batch, int32_t list_size, int64_t n_docs, int32_t call, ultr_dnn_route_info* out) {
+extern "C" int ultr_dnn_route_operands(const ultr_dnn_desc* d, int32_t batch, int32_t list_size, int64_t n_docs, int32_t call,
+                                       uint32_t operands, ultr_dnn_route_info* out) {
   DnnRoute f, b;
-  if (!out || call < ULTR_DNN_CALL_EVAL || call > ULTR_DNN_CALL_STEP_DSCORES) return ULTR_E_BADARG;
-  if (!route_query(d, batch, list_size, n_docs, call == ULTR_DNN_CALL_EVAL ? DNN_EVAL_FWD : DNN_TRAIN_FWD, &f)) return ULTR_E_BADARG;
+  if (!out || call < ULTR_DNN_CALL_EVAL || call > ULTR_DNN_CALL_STEP_DSCORES || (operands & ~(uint32_t)ULTR_DNN_OP_ALL) != 0) return ULTR_E_BADARG;
+  // as operands_of: a copy off a 16-byte boundary counts as absent.  The forward of a step has no dscores to look at (it ignores the bit)
+  const DnnOperands o = {(operands & ULTR_DNN_OP_PARAMS16) != 0, (operands & ULTR_DNN_OP_FEATURES16) != 0,
+                         (operands & ULTR_DNN_OP_WT) != 0 && (operands & ULTR_DNN_OP_WT16) != 0, (operands & ULTR_DNN_OP_DSCORES) != 0};
+  if (!route_query(d, batch, list_size, n_docs, call == ULTR_DNN_CALL_EVAL ? DNN_EVAL_FWD : DNN_TRAIN_FWD, o, &f)) return ULTR_E_BADARG;
   b = f;  // (evaluation: no backward part; a step, as ultr_train_step: the fused launch where the shape qualifies, else the separate calls)
-  if (call == ULTR_DNN_CALL_STEP_SOFTMAX) route_query(d, batch, list_size, n_docs, DNN_STEP_SOFTMAX, &b);
+  if (call == ULTR_DNN_CALL_STEP_SOFTMAX) route_query(d, batch, list_size, n_docs, DNN_STEP_SOFTMAX, o, &b);
   if (b.fb_waves != 0) f = b;
   else if (call != ULTR_DNN_CALL_EVAL)
-    route_query(d, batch, list_size, n_docs, call == ULTR_DNN_CALL_STEP_SOFTMAX ? DNN_BWD_SOFTMAX : DNN_BWD_DSCORES, &b);
+    route_query(d, batch, list_size, n_docs, call == ULTR_DNN_CALL_STEP_SOFTMAX ? DNN_BWD_SOFTMAX : DNN_BWD_DSCORES, o, &b);
   const int bwd_rows = b.bwd == ULTR_DNN_FUSED ? b.fwd_rows : (b.bwd == ULTR_DNN_NONE || b.bwd == ULTR_DNN_PER_LAYER) ? 0 : b.g.rblk;
   *out = ultr_dnn_route_info{b.fb_waves, f.fwd, f.fwd_rows, b.bwd, bwd_rows, b.loss, b.g.wg_h3, {0}};
   return (f.fwd == ULTR_DNN_UNSUPPORTED || b.bwd == ULTR_DNN_UNSUPPORTED) ? ULTR_E_UNSUPPORTED : 0;
+}
+extern "C" int ultr_dnn_route(const ultr_dnn_desc* d, int32_t batch, int32_t list_size, int64_t n_docs, int32_t call, ultr_dnn_route_info* out) {
+  return ultr_dnn_route_operands(d, batch, list_size, n_docs, call, ULTR_DNN_OP_ALL, out);
 }
 // the older encodings (n_rows: as many lists of one document, gathered from as many)
 static int32_t tile_rows_code(int family, int rows) { return family == ULTR_DNN_PER_LAYER ? 0 : family == ULTR_DNN_WIDE ? 1000 + rows : rows; }
 extern "C" int32_t ultr_dnn_forward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows, int32_t training) {
   DnnRoute r;
-  return route_query(d, n_rows, 1, n_rows, training ? DNN_TRAIN_FWD : DNN_EVAL_FWD, &r) ? tile_rows_code(r.fwd, r.fwd_rows) : -1;
+  return route_query(d, n_rows, 1, n_rows, training ? DNN_TRAIN_FWD : DNN_EVAL_FWD, ALL_OPERANDS, &r) ? tile_rows_code(r.fwd, r.fwd_rows) : -1;
 }
 extern "C" int32_t ultr_dnn_backward_tile_rows(const ultr_dnn_desc* d, int64_t n_rows) {
   DnnRoute r;
-  return route_query(d, n_rows, 1, n_rows, DNN_BWD_DSCORES, &r) ? tile_rows_code(r.bwd, r.g.rblk) : -1;
+  return route_query(d, n_rows, 1, n_rows, DNN_BWD_DSCORES, ALL_OPERANDS, &r) ? tile_rows_code(r.bwd, r.g.rblk) : -1;
 }
 extern "C" int32_t ultr_fused_fb_waves(const ultr_dnn_desc* d, int32_t batch, int32_t list_size) {
   DnnRoute r;
-  return route_query(d, batch, list_size, 0, DNN_STEP_SOFTMAX, &r) ? r.fb_waves : -1;
+  return route_query(d, batch, list_size, 0, DNN_STEP_SOFTMAX, ALL_OPERANDS, &r) ? r.fb_waves : -1;
 }
 
 bool ultr_wgrad_h3_geometry(int64_t T, int M, int K, int* nsplit, int* rows_per_split) {
@@ -863,7 +874,7 @@ struct BwdArgs {
 // but for the chunking of the loss-partial fold, which depends on the partial count of this launch
 static int backward_impl(const DnnPlan& p, const DnnRoute& r, BwdPlan bp, const BwdArgs& a, const float* dscores, const FusedSoftmax& fl) {
   StepCtx* ctx = a.ctx;
-  const float *params = a.params, *features = a.features, *saved = (const float*)a.saved, *wt = ctx ? ctx->wt : nullptr;  // (the step's weight copies)
+  const float *params = a.params, *features = a.features, *saved = (const float*)a.saved, *wt = ctx ? ultr_readable_wt(ctx->wt) : nullptr;  // (the step's weight copies)
   const int batch = a.batch, list_size = a.list_size, tail = (int)ultr_tail_len(list_size);
   float *ws = (float*)a.bwd_ws, *grads = a.grads;
   hipStream_t st = (hipStream_t)a.stream;
@@ -1001,9 +1012,10 @@ int ultr_fused_step_softmax(const ultr_dnn_desc* d, const float* params, const f
                             const int32_t* docids, int32_t batch, int32_t list_size, float* scores, void* saved,
                             const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw, float* dscores_out,
                             void* loss_ws, void* bwd_ws, float* grads, void* stream, StepCtx* ctx) {
-  if (!params || !wt || !docids || !scores || !saved || !labels || !loss_ws || !bwd_ws || !grads || batch <= 0 ||
+  if (!params || !docids || !scores || !saved || !labels || !loss_ws || !bwd_ws || !grads || batch <= 0 ||
       list_size <= 0 || n_docs < 0 || (n_docs > 0 && !features) || (ipw_table && n_ipw <= 0))
     return ULTR_E_BADARG;
+  wt = ultr_readable_wt(wt);  // (absent, or off a 16-byte boundary: the route answers "the separate calls")
   const int64_t N = (int64_t)batch * list_size;
   DnnPlan p;
   BwdPlan bp;

@@ -809,7 +809,7 @@ struct WideBwd {
 enum DnnCall { DNN_EVAL_FWD, DNN_TRAIN_FWD, DNN_BWD_DSCORES, DNN_BWD_SOFTMAX, DNN_STEP_SOFTMAX };
 struct DnnOperands {
   bool params16, features16;  // on a 16-byte boundary (features: and present)
-  bool wt, wt16;              // the weight copies are present / on a 16-byte boundary (absent counts as aligned)
+  bool wt;                    // the weight copies are present AND on a 16-byte boundary (a misaligned copy counts as absent: ultr_plan.h)
   bool dscores;               // there is a [B, L] buffer a separate loss launch can leave d(loss)/d(scores) in
 };
 struct DnnRoute {

@@ -278,8 +278,14 @@ int ultr_comm_allreduce_ex(ultr_comm* c, uint64_t step, const float* src, int64_
 // The step in flight: on the stack of ultr_train_step / ultr_feed_train_step, handed to the stages the step calls.  nullptr =
 // a stand-alone stage call (the public entry points): the row-major parameters are streamed, nothing reports early, nothing is
 // exchanged and no draw rides on the update launch.
+// The operand contract of the weight copies (include/ultr_hip.h, ultr_dnn_forward): every kernel that reads `wt` reads it with
+// 16-byte loads, so a copy off a 16-byte boundary counts as ABSENT wherever it is only read (the forward, both backward calls
+// through StepCtx, the route queries), and the calls that must WRITE it (ultr_apply_update, ultr_train_step) refuse it.
+static inline bool ultr_aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+static inline const float* ultr_readable_wt(const float* wt) { return ultr_aligned16(wt) ? wt : nullptr; }
+
 struct StepCtx {
-  const float* wt = nullptr;                      // ultr_step_args::wt, the weight copies for the backward kernels
+  const float* wt = nullptr;                      // ultr_step_args::wt, the weight copies for the backward kernels (ultr_readable_wt)
   EarlyReport early = {nullptr, 0u, 0, 1.0f};     // single-GPU report of the weight-gradient launch
   ultr_comm* comm = nullptr;                      // data-parallel step: where the backward ends in the slab reduction, that launch
   uint64_t comm_step = 0;                         //   runs the exchange on its own output (grad_reduce_xchg_kernel)

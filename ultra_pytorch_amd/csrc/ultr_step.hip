@@ -45,6 +45,9 @@ int ultr_train_step_ctx(const ultr_step_args* a, StepCtx* ctx, void* stream) {
   if (!a || !a->desc || !a->upd) return ULTR_E_BADARG;
   // the update launch would refuse these behind the backward: refuse them here, with nothing launched
   if (!a->skip_update && ultr_update_check_opt(a->upd, a->state)) return ULTR_E_BADARG;
+  // the step keeps the weight copies current (its update launch writes them with 16-byte stores): one off a 16-byte boundary is
+  // refused; an absent one is fine - every stage then streams the row-major parameters (the operand contract, ultr_plan.h)
+  if (!ultr_aligned16(a->wt)) return ULTR_E_BADARG;
   ultr_prof_tick();
   // early loss report of this step's backward (EarlyReport, ultr_plan.h): only where the reported loss has no L2 term (that one is
   // formed by the update launch) - from the local loss sums where they ARE the batch's, behind the peer exchange in a data-parallel step

@@ -695,6 +695,7 @@ extern "C" int ultr_apply_update(const ultr_update_desc* u, const ultr_dnn_desc*
 int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, float* params, float* wt, float* state, const float* grads,
                          float* aux, const void* bwd_ws, float* scalars_out, int nsq2, const ultr_click_args** rider_io, void* stream) {
   if (!u || !params || !grads || !bwd_ws || u->n_params <= 0 || u->list_size <= 0) return ULTR_E_BADARG;
+  if (!ultr_aligned16(wt)) return ULTR_E_BADARG;  // update_tiled_kernel writes the copies with 16-byte stores (the operand contract, ultr_plan.h)
   DnnPlan dp;
   memset(&dp, 0, sizeof(dp));
   if (wt != nullptr) {

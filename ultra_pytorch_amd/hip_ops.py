@@ -71,14 +71,24 @@ class DnnShape:
     def bwd_workspace_bytes(self, n_rows):
         return int(self.lib.ultr_dnn_bwd_workspace_bytes(ctypes.byref(self.desc), n_rows))
 
-    def route(self, B, L, n_docs=None, call="step_softmax"):
+    def route(self, B, L, n_docs=None, call="step_softmax", operands=None):
         """The kernels one call takes at B lists of L documents gathered from n_docs (default B x L) documents (ultr_dnn_route: the
         route the entry points themselves decide, under the knobs as the library last read them; host-only, launches nothing) as a
-        dict of the fields of ultr_dnn_route_info.  `call`: one of _lib.DNN_CALLS.  A call the library would refuse raises
-        UltrHipError ("unsupported shape")."""
+        dict of the fields of ultr_dnn_route_info.  `call`: one of _lib.DNN_CALLS.  `operands`: None = what the engines pass (16-byte
+        aligned pointers, the weight copies, a dscores buffer), else the names of _lib.DNN_OPERANDS that hold for the call (an
+        iterable, or the ULTR_DNN_OP_ bits as an int: ultr_dnn_route_operands).  A call the library would refuse raises UltrHipError
+        ("unsupported shape")."""
         info = _lib.DnnRouteInfo()
-        check(self.lib.ultr_dnn_route(ctypes.byref(self.desc), int(B), int(L), int(B) * int(L) if n_docs is None else int(n_docs),
-                                      _lib.DNN_CALLS.index(call), ctypes.byref(info)), "ultr_dnn_route")
+        if operands is None:
+            bits = _lib.DNN_OP_ALL
+        elif isinstance(operands, int):
+            bits = operands
+        else:
+            bits = 0
+            for name in operands:
+                bits |= _lib.DNN_OPERANDS[name]
+        check(self.lib.ultr_dnn_route_operands(ctypes.byref(self.desc), int(B), int(L), int(B) * int(L) if n_docs is None else int(n_docs),
+                                               _lib.DNN_CALLS.index(call), bits, ctypes.byref(info)), "ultr_dnn_route_operands")
         return {name: int(getattr(info, name)) for name, _ in _lib.DnnRouteInfo._fields_ if name != "reserved"}
 
 
