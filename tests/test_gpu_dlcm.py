@@ -89,6 +89,30 @@ def test_scoring_form_and_rerun_give_the_same_bits(k):
     assert torch.equal(s1.view(torch.int32), s3.view(torch.int32))
 
 
+def test_a_single_token_has_no_previous_state():
+    """B = L = 1 with one real document (make_inputs would make the only list all PADs): dW_hh sums over T - 1 = 0 tokens, so the
+    weight-gradient launch is not reached and the gradient is zeroed - exactly zero, everything else to the bar."""
+    from ultra_pytorch_amd.ranking_model import DLCM
+    dims = B, L, F, H, heads = (1, 1, 12, 20, 3)
+    torch.manual_seed(77)
+    model = DLCM("hidden_size=%d,num_heads=%d" % (H, heads), F)
+    with torch.no_grad():
+        model.layer_norm.weight.add_(0.3 * torch.randn(F))
+        model.layer_norm.bias.add_(0.3 * torch.randn(F))
+    feats, dsc = 3.0 * torch.randn(1, F), torch.randn(B, L)
+    ids = torch.zeros(L, B, dtype=torch.int32)
+    ref_scores, ref_grads = R.reference(model.state_dict(), F, H, heads, feats, ids, dsc)
+    scores, grads = run_on(model, feats, ids, dsc, dims)
+    assert R.rel_err(scores, ref_scores) <= R.BAR
+    for name, shp, off in model.shape.layout():
+        g = grads[off:off + ref_grads[name].numel()].view(*shp)
+        if name == "gru.weight_hh_l0":
+            assert bool((g == 0).all())
+        e = R.rel_err(g, ref_grads[name])
+        print("DLCM %s %s: %.3g" % (dims, name, e))
+        assert e <= R.BAR, (name, e)
+
+
 def test_pad_rows_come_out_as_beta_and_pad_lists_share_one_score_row():
     """A PAD is the zero row: LayerNorm gives beta whatever the position, so every all-PAD list scores like every other."""
     from ultra_pytorch_amd import hip_ops

@@ -1,5 +1,5 @@
 """The edge cases of tests/test_gpu_dlcm_edges.py and tests/test_gpu_gsf_edges.py (dlcm_ref.EDGES / FWD_ONLY, gsf_ref.EDGES), without a
-GPU: the boundary arithmetic of csrc/ultr_dlcm_plan.h, csrc/ultr_gsf_plan.h, csrc/ultr_gemm.h and csrc/ultr_sr_rows.hip restated in
+GPU: the boundary arithmetic of csrc/ultr_dlcm_plan.h, csrc/ultr_gsf_plan.h, csrc/ultr_rowgrad_plan.h, csrc/ultr_gemm.h and csrc/ultr_sr_rows.hip restated in
 Python, checked against the library's own size queries, and for every case the proof that it sits on the boundary it is named for - a
 later change of a constant makes these tests say that a case has left its boundary.  Also the room the parity bar leaves: e32, the
 float64 twin evaluated in float32 on the CPU, per case."""
@@ -12,8 +12,8 @@ from tests import gsf_ref as G
 LDS_MAX = 160 * 1024      # DL_LDS_MAX; also the LDS of a compute unit
 CUS = 256                 # compute units of an MI355X
 LISTS = 16                # DL_LISTS
-CS_ROWS = 256             # DL_CS_ROWS = GSF_CS_ROWS
-WG_SPLITS = 64            # DL_WG_SPLITS = GSF_WG_SPLITS
+CS_ROWS = 256             # RG_CS_ROWS
+WG_SPLITS = 64            # RG_WG_SPLITS
 WG_FLOOR = 128            # rows per weight-gradient split at least
 WIDE_FOLD = 256           # SrFoldQueue::add: nparts >= 256 takes the 16-column fold ...
 WIDE2_LEN = 1024          # ... and partials this long its float4 form (out of scope here: SetRank's tests own it)

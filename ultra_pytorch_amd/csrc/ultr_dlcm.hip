@@ -5,7 +5,7 @@
 //             dl_gru_fwd_kernel (ONE launch walks the positions) -> W_phi s + b_phi (ugemm) -> dl_head_fwd_kernel (tanh, m, scores)
 //   backward  dl_head_bwd_kernel (dm, dM, dv partials) -> ds = dM . W_phi (ugemm) -> dl_gru_bwd_kernel (ONE launch, the other way,
 //             carrying dh; writes the gate gradients) -> d xh = dGi . W_ih (ugemm) -> column sums per row chunk (biases, gamma / beta) ->
-//             dW_phi (ugemm, a transposing A producer) -> dW_ih, dW_hh (dl_wgrad_kernel: the tokens split over the grid) -> ONE fold
+//             dW_phi (ugemm, a transposing A producer) -> dW_ih, dW_hh (rg_wgrad: the tokens split over the grid) -> ONE fold
 //             launch (the splits and chunks, dv, the loss partials of the step tail)
 //
 // The recurrent kernels: lists are independent, so a workgroup owns 16 lists (the rows of a v_mfma_f32_16x16x4_f32 tile), keeps their
@@ -22,7 +22,7 @@
 #include "ultr_dlcm_plan.h"
 #include "ultr_gemm.h"
 #include "ultr_plan.h"
-#include "ultr_sr_rows.h"
+#include "ultr_rowgrad.h"
 
 namespace {
 
@@ -265,117 +265,6 @@ __global__ __launch_bounds__(256) void dl_head_bwd_kernel(const float* __restric
   }
 }
 
-// ---- column sums (bias gradients, d beta, d gamma = sum d xh o xhat): every job of a backward in one launch ------------------------------
-// A workgroup owns 16 columns of DL_CS_ROWS rows: 16 groups of threads each add every 16th row in order (in double), fixed-order combine,
-// one partial per row chunk; the chunks are folded by the backward's one fold launch.
-#define DL_MAX_CS 6
-struct DlCsJob {
-  const float* a;
-  const float* mul;  // NULL, or the same shape as a: sums of a o mul
-  float* part;       // [chunks][W]
-  int64_t T;
-  int W, ncb, blk_begin;
-};
-struct DlCsTable {
-  int n, nblocks;
-  DlCsJob job[DL_MAX_CS];
-};
-__global__ __launch_bounds__(256) void dl_colsum_kernel(DlCsTable tb) {
-  __shared__ double sm[16][16];
-  int j = 0;
-  while (j + 1 < tb.n && (int)blockIdx.x >= tb.job[j + 1].blk_begin) ++j;
-  const DlCsJob jb = tb.job[j];
-  const int blk = (int)blockIdx.x - jb.blk_begin, chunk = blk / jb.ncb;
-  const int cl = threadIdx.x & 15, grp = threadIdx.x >> 4;
-  const int c = (blk - chunk * jb.ncb) * 16 + cl;
-  const int64_t t0 = (int64_t)chunk * DL_CS_ROWS, t1 = t0 + DL_CS_ROWS < jb.T ? t0 + DL_CS_ROWS : jb.T;
-  double acc = 0.0;
-  if (c < jb.W) {
-    for (int64_t t = t0 + grp; t < t1; t += 16) {
-      float x = jb.a[t * jb.W + c];
-      if (jb.mul != nullptr) x *= jb.mul[t * jb.W + c];
-      acc += (double)x;
-    }
-  }
-  sm[grp][cl] = acc;
-  __syncthreads();
-  if (grp == 0 && c < jb.W) {
-    double t = sm[0][cl];
-#pragma unroll
-    for (int g = 1; g < 16; ++g) t += sm[g][cl];
-    jb.part[(int64_t)chunk * jb.W + c] = (float)t;
-  }
-}
-// queues the job and the fold of its partials; returns the floats of `part` it took
-int64_t cs_add(DlCsTable& tb, SrFoldQueue& folds, const float* a, const float* mul, int64_t T, int W, float* part, float* dst, hipStream_t st) {
-  const int chunks = (int)dl_cs_chunks(T);
-  DlCsJob& j = tb.job[tb.n++];
-  j.a = a; j.mul = mul; j.part = part; j.T = T; j.W = W; j.ncb = (W + 15) / 16; j.blk_begin = tb.nblocks;
-  tb.nblocks += j.ncb * chunks;
-  folds.add(part, (int64_t)W, chunks, W, dst, st, /*own_buffer=*/true);
-  return (int64_t)chunks * W;
-}
-
-// ---- weight gradients over the tokens: part[s][n][f] = sum over the tokens t of split s of G[t][n] X'[t][f] ------------------------------
-// G [K][ldg] are gate gradients (n < Rn), X [K][ldx] the other operand (f < N); X' = X gamma + beta when gamma is given (the product against
-// xh from the stored xhat).  mask_L != 0: tokens with t % mask_L == mask_L - 1 do not count (the last position of a list has no previous
-// state).  A wave owns 16 rows x 64 columns and walks its split four tokens per matrix-core step: lane (i, q) supplies G[t + q][n0 + i] and
-// X'[t + q][f0 + 16 c + i], 64-byte runs of both.  The splits are folded by the backward's one fold launch (fixed order).
-__global__ __launch_bounds__(256) void dl_wgrad_kernel(const float* __restrict__ G, int ldg, int Rn, const float* __restrict__ X, int ldx, int N,
-                                                       int64_t K, int mask_L, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       int64_t chunk, float* __restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int i = lane & 15, q = lane >> 4;
-  const int n0 = ((int)blockIdx.x * 4 + wave) * 16, f0 = (int)blockIdx.y * 64;
-  if (n0 >= Rn) return;
-  const int64_t t_begin = (int64_t)blockIdx.z * chunk, t_end = t_begin + chunk < K ? t_begin + chunk : K;
-  const Src gs = make_src(G, K * ldg), xs = make_src(X, K * ldx);
-  const bool nok = n0 + i < Rn;
-  bool fok[4];
-  float ga[4], be[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int f = f0 + 16 * c + i;
-    fok[c] = f < N;
-    ga[c] = (gamma != nullptr && fok[c]) ? gamma[f] : 1.0f;
-    be[c] = (beta != nullptr && fok[c]) ? beta[f] : 0.0f;
-  }
-  f32x4 acc[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int64_t t0 = t_begin; t0 < t_end; t0 += 4) {
-    const int64_t t = t0 + q;
-    const bool tok = t < t_end;
-    const bool aok = tok && nok && (mask_L == 0 || (int)(t % mask_L) != mask_L - 1);
-    const float a = buf_ld1(gs, aok ? (unsigned)((t * ldg + n0 + i) * 4) : ULTR_OOB);
-    float x[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) x[c] = buf_ld1(xs, (tok && fok[c]) ? (unsigned)((t * ldx + f0 + 16 * c + i) * 4) : ULTR_OOB);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = mfma16(a, (tok && fok[c]) ? fmaf(x[c], ga[c], be[c]) : 0.0f, acc[c]);
-  }
-  float* ps = part + (int64_t)blockIdx.z * Rn * N;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = n0 + 4 * q + r, col = f0 + 16 * c + i;
-      if (row < Rn && col < N) ps[(int64_t)row * N + col] = acc[c][r];
-    }
-}
-void wgrad_launch(SrFoldQueue& folds, const float* G, int Rn, const float* X, int N, int64_t K, int mask_L, const float* gamma,
-                  const float* beta, float* part, float* dst, hipStream_t st) {
-  if (K <= 0) {  // a single token has no previous state at all
-    (void)hipMemsetAsync(dst, 0, (size_t)Rn * N * sizeof(float), st);
-    return;
-  }
-  const int64_t chunk = dl_wg_chunk(K);
-  const int splits = (int)((K + chunk - 1) / chunk);
-  hipLaunchKernelGGL(dl_wgrad_kernel, dim3((unsigned)((Rn + 63) / 64), (unsigned)((N + 63) / 64), (unsigned)splits), dim3(256), 0, st, G, Rn, Rn,
-                     X, N, N, K, mask_L, gamma, beta, chunk, part);
-  folds.add(part, (int64_t)Rn * N, splits, Rn * N, dst, st, /*own_buffer=*/true);
-}
-
 // ---- pieces for ugemm::run ---------------------------------------------------------------------------------------------------------------
 // A[r][k] = src[k][r]: the transpose of a row-major [K][ld] matrix (weight gradients: the contraction runs over the tokens).  mask_L != 0:
 // source rows k with k % mask_L == mask_L - 1 read as zeros (the last position of every list has no previous state).
@@ -408,8 +297,6 @@ hipError_t dl_set_lds(const void* kern, std::atomic<int64_t>* set, int64_t bytes
   if (e == hipSuccess) set[dev].store(bytes, std::memory_order_release);
   return e;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -462,7 +349,7 @@ int ultr_dlcm_forward(const ultr_dlcm_desc* c, const float* params, const float*
   dl_make_plan(c, batch, list_size, (int64_t)batch * list_size, p);
   if (!dl_sizes_fit(p, n_docs) || p.lds_fwd > DL_LDS_MAX) return ULTR_E_UNSUPPORTED;
   float* sv = (float*)(saved ? saved : work);
-  if (!aligned16(params) || !aligned16(sv) || !aligned16(features)) return ULTR_E_BADARG;
+  if (!ultr_aligned16(params) || !ultr_aligned16(sv) || !ultr_aligned16(features)) return ULTR_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   const bool train = saved != nullptr;
   const int F = p.F, H = p.H, hH = p.heads * p.H, B = p.B, L = p.L;
@@ -510,7 +397,7 @@ int ultr_dlcm_backward(const ultr_dlcm_desc* c, const float* params, const float
   DlPlan p;
   dl_make_plan(c, batch, list_size, (int64_t)batch * list_size, p);
   if (!dl_sizes_fit(p, n_docs) || p.lds_bwd > DL_LDS_MAX) return ULTR_E_UNSUPPORTED;
-  if (!aligned16(params) || !aligned16(saved) || !aligned16(workspace) || !aligned16(grads)) return ULTR_E_BADARG;
+  if (!ultr_aligned16(params) || !ultr_aligned16(saved) || !ultr_aligned16(workspace) || !ultr_aligned16(grads)) return ULTR_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   const float* sv = (const float*)saved;
   float* ws = (float*)workspace;
@@ -548,15 +435,14 @@ int ultr_dlcm_backward(const ultr_dlcm_desc* c, const float* params, const float
   }
   SrFoldQueue folds(nullptr, 0);  // every partial sum of this backward is folded by ONE launch at its end (fixed order)
   {
-    DlCsTable tb;
-    tb.n = 0; tb.nblocks = 0;
+    RgCsTable tb;  // every column sum of this backward in one launch
     float* part = ws + p.w_cspart;
-    part += cs_add(tb, folds, ws + p.w_dgi, nullptr, T, 3 * H, part, grads + p.p_bih, st);
-    part += cs_add(tb, folds, ws + p.w_dgh, nullptr, T, 3 * H, part, grads + p.p_bhh, st);
-    part += cs_add(tb, folds, ws + p.w_dM, nullptr, B, hH, part, grads + p.p_bphi, st);
-    part += cs_add(tb, folds, ws + p.w_dxh, nullptr, T, F, part, grads + p.p_beta, st);
-    part += cs_add(tb, folds, ws + p.w_dxh, sv + p.s_xhat, T, F, part, grads + p.p_gamma, st);
-    hipLaunchKernelGGL(dl_colsum_kernel, dim3((unsigned)tb.nblocks), dim3(256), 0, st, tb);
+    part += tb.add(folds, ws + p.w_dgi, nullptr, nullptr, nullptr, T, 3 * H, part, grads + p.p_bih, st);
+    part += tb.add(folds, ws + p.w_dgh, nullptr, nullptr, nullptr, T, 3 * H, part, grads + p.p_bhh, st);
+    part += tb.add(folds, ws + p.w_dM, nullptr, nullptr, nullptr, B, hH, part, grads + p.p_bphi, st);
+    part += tb.add(folds, ws + p.w_dxh, nullptr, nullptr, nullptr, T, F, part, grads + p.p_beta, st);
+    part += tb.add(folds, ws + p.w_dxh, sv + p.s_xhat, nullptr, nullptr, T, F, part, grads + p.p_gamma, st);
+    tb.launch(st);
   }
   {  // dW_phi = dM^T . s (the contraction is the batch: short)
     const ATrans a{ws + p.w_dM, (int64_t)B, hH, 0};
@@ -565,15 +451,13 @@ int ultr_dlcm_backward(const ultr_dlcm_desc* c, const float* params, const float
     if ((err = ugemm::run<false>(d, a, sv + p.s_o, e, st)) != hipSuccess) return (int)err;
   }
   // dW_ih = dGi^T . xh, xh = xhat gamma + beta formed as the operand is read
-  wgrad_launch(folds, ws + p.w_dgi, 3 * H, sv + p.s_xhat, F, T, 0, params + p.p_gamma, params + p.p_beta, ws + p.w_wpart_ih, grads + p.p_wih, st);
+  rg_wgrad(folds, ws + p.w_dgi, 3 * H, sv + p.s_xhat, F, T, 0, nullptr, nullptr, params + p.p_gamma, params + p.p_beta, ws + p.w_wpart_ih,
+           grads + p.p_wih, st);
   // dW_hh = dGh^T . h_prev: token t's previous state is o[t + 1], none at a list's last position (the very last token among them)
-  wgrad_launch(folds, ws + p.w_dgh, 3 * H, sv + p.s_o + H, H, T - 1, L, nullptr, nullptr, ws + p.w_wpart_hh, grads + p.p_whh, st);
+  rg_wgrad(folds, ws + p.w_dgh, 3 * H, sv + p.s_o + H, H, T - 1, L, nullptr, nullptr, nullptr, nullptr, ws + p.w_wpart_hh, grads + p.p_whh,
+           st);
   folds.add(ws + p.w_dv, (int64_t)p.heads, B, p.heads, grads + p.p_v, st, /*own_buffer=*/true);
-  if (loss_ws != nullptr && n_loss_parts > 0) {  // the step tail
-    const int tail = (int)ultr_tail_len(list_size);
-    folds.add((const float*)loss_ws, (int64_t)tail, (int)n_loss_parts, tail, grads + p.P, st, /*own_buffer=*/true);
-  }
-  folds.flush(st);
+  rg_fold_all(folds, loss_ws, n_loss_parts, list_size, grads + p.P, st);
   return (int)hipGetLastError();
 }
 

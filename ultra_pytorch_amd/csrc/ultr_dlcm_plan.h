@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/ultr_hip.h"
+#include "ultr_rowgrad_plan.h"
 
 #define DL_LISTS 16         // lists per workgroup of the recurrent kernels = the rows of one 16x16x4 matrix-core tile
 #define DL_WAVES 8          // waves per workgroup: column tiles of 16 hidden units are dealt round-robin to them
@@ -24,18 +25,6 @@ struct DlPlan {
   int64_t lds_fwd, lds_bwd;  // bytes
   bool dh_global;            // the backward's carried dh sits in `workspace`: dg and dh do not both fit the LDS
 };
-
-#define DL_CS_ROWS 256       // rows per partial of the column-sum launch
-#define DL_WG_SPLITS 64      // at most this many token splits of a weight-gradient launch
-
-static inline int64_t dl_up4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-static inline int64_t dl_cs_chunks(int64_t T) { return (T + DL_CS_ROWS - 1) / DL_CS_ROWS; }
-// tokens per split of dl_wgrad_kernel: at least 128 (32 matrix-core steps), a multiple of 4, at most DL_WG_SPLITS splits
-static inline int64_t dl_wg_chunk(int64_t K) {
-  const int64_t c = dl_up4((K + DL_WG_SPLITS - 1) / DL_WG_SPLITS);
-  return c < 128 ? 128 : c;
-}
-static inline int64_t dl_wg_splits(int64_t K) { return K <= 0 ? 0 : (K + dl_wg_chunk(K) - 1) / dl_wg_chunk(K); }
 
 // 0, ULTR_E_BADARG (not a model) or ULTR_E_UNSUPPORTED (a model these kernels do not take)
 static inline int dl_check_desc(const ultr_dlcm_desc* c) {
@@ -66,8 +55,8 @@ static inline void dl_make_plan(const ultr_dlcm_desc* c, int64_t B, int64_t L, i
   const int64_t F = p.F, H = p.H, hd = p.heads;
   p.B = (int)B; p.L = (int)L; p.T = T;
   p.s_mean = 0;
-  p.s_rstd = dl_up4(T);
-  p.s_gi = 2 * dl_up4(T);
+  p.s_rstd = rg_up4(T);
+  p.s_gi = 2 * rg_up4(T);
   p.s_o = p.s_gi + T * 3 * H;
   p.s_M = p.s_o + T * H;
   p.s_m = p.s_M + B * hd * H;
@@ -81,10 +70,10 @@ static inline void dl_make_plan(const ultr_dlcm_desc* c, int64_t B, int64_t L, i
   p.w_dM = p.w_dxh + T * F;
   p.w_ds = p.w_dM + B * hd * H;
   p.w_dv = p.w_ds + B * H;
-  p.w_cspart = p.w_dv + dl_up4(B * hd);
-  p.w_wpart_ih = p.w_cspart + dl_cs_chunks(T) * (6 * H + 2 * F) + dl_cs_chunks(B) * hd * H;
-  p.w_wpart_hh = p.w_wpart_ih + dl_wg_splits(T) * 3 * H * F;
-  p.w_dh = p.w_wpart_hh + dl_wg_splits(T - 1) * 3 * H * H;
+  p.w_cspart = p.w_dv + rg_up4(B * hd);
+  p.w_wpart_ih = p.w_cspart + rg_cs_chunks(T) * (6 * H + 2 * F) + rg_cs_chunks(B) * hd * H;
+  p.w_wpart_hh = p.w_wpart_ih + rg_wg_splits(T) * 3 * H * F;
+  p.w_dh = p.w_wpart_hh + rg_wg_splits(T - 1) * 3 * H * H;
   p.lds_fwd = (int64_t)2 * DL_LISTS * (p.Hp + 8) * 4;
   p.lds_bwd = (int64_t)DL_LISTS * ((3 * p.Hp + 8) + (p.Hp + 8)) * 4;
   p.dh_global = p.lds_bwd > DL_LDS_MAX;

@@ -5,12 +5,12 @@
 //   forward   gsf_stats0_kernel (the statistics of the m gathered rows side by side; the table of each row's m documents) -> layer 0 on
 //             ugemm::run with the gathering producer AGroupLN -> per hidden layer gsf_rowstats_kernel + ugemm::run (ALayerNorm) ->
 //             gsf_head_fwd_kernel (LayerNorm + m dot products per row; no hidden layer: a ugemm::run of m columns) -> gsf_fold_kernel
-//   backward  gsf_head_bwd_kernel (d o by the gather law, d u of the head) -> per layer, head first: gsf_colsum_kernel (bias, beta, gamma
-//             partials per row chunk), gsf_wgrad_kernel (the rows split over the grid), gsf_ln_bwd_kernel (LayerNorm backward x act'),
+//   backward  gsf_head_bwd_kernel (d o by the gather law, d u of the head) -> per layer, head first: RgCsTable (bias, beta, gamma
+//             partials per row chunk), rg_wgrad (the rows split over the grid; both in ultr_rowgrad.hip), gsf_ln_bwd_kernel (LayerNorm backward x act'),
 //             ugemm::run (data gradient) -> ONE fold launch (every partial, the loss partials of the step tail)
 //
 // LDS: ugemm's tiles (forward products 60 KiB / 40 KiB per workgroup at more than / up to 64 outputs, data gradients 52 / 36 KiB), the
-// 2 KiB combine of gsf_colsum_kernel, nothing else; no atomics anywhere.
+// 2 KiB combine of rg_colsum_kernel, nothing else; no atomics anywhere.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -19,7 +19,7 @@
 #include "ultr_gemm.h"
 #include "ultr_gsf_plan.h"
 #include "ultr_plan.h"
-#include "ultr_sr_rows.h"
+#include "ultr_rowgrad.h"
 
 namespace {
 
@@ -255,123 +255,6 @@ __global__ __launch_bounds__(256) void gsf_ln_bwd_kernel(const float* __restrict
   }
 }
 
-// ---- column sums (bias gradients, d beta, d gamma = sum d u o xhat): the three jobs of a layer in one launch -----------------------------
-// A workgroup owns 16 columns of GSF_CS_ROWS rows: 16 groups of threads each add every 16th row in order (in double), fixed-order combine,
-// one partial per row chunk; the chunks are folded by the backward's one fold launch.  LDS: 2 KiB.
-#define GSF_MAX_CS 3
-struct GsfCsJob {
-  const float* a;
-  const float* mul;   // NULL, or the same shape as a: sums of a o mul ...
-  const float* mean;  // ... NULL, or with mean / rstd [T]: sums of a o ((mul - mean) rstd)
-  const float* rstd;
-  float* part;        // [chunks][W]
-  int W, ncb, blk_begin;
-};
-struct GsfCsTable {
-  int n, nblocks;
-  int64_t T;
-  GsfCsJob job[GSF_MAX_CS];
-};
-__global__ __launch_bounds__(256) void gsf_colsum_kernel(GsfCsTable tb) {
-  __shared__ double sm[16][16];
-  int j = 0;
-  while (j + 1 < tb.n && (int)blockIdx.x >= tb.job[j + 1].blk_begin) ++j;
-  const GsfCsJob jb = tb.job[j];
-  const int blk = (int)blockIdx.x - jb.blk_begin, chunk = blk / jb.ncb;
-  const int cl = threadIdx.x & 15, grp = threadIdx.x >> 4;
-  const int c = (blk - chunk * jb.ncb) * 16 + cl;
-  const int64_t t0 = (int64_t)chunk * GSF_CS_ROWS, t1 = t0 + GSF_CS_ROWS < tb.T ? t0 + GSF_CS_ROWS : tb.T;
-  double acc = 0.0;
-  if (c < jb.W) {
-    for (int64_t t = t0 + grp; t < t1; t += 16) {
-      float v = jb.a[t * jb.W + c];
-      if (jb.mul != nullptr) {
-        float h = jb.mul[t * jb.W + c];
-        if (jb.mean != nullptr) h = (h - jb.mean[t]) * jb.rstd[t];
-        v *= h;
-      }
-      acc += (double)v;
-    }
-  }
-  sm[grp][cl] = acc;
-  __syncthreads();
-  if (grp == 0 && c < jb.W) {
-    double t = sm[0][cl];
-#pragma unroll
-    for (int g = 1; g < 16; ++g) t += sm[g][cl];
-    jb.part[(int64_t)chunk * jb.W + c] = (float)t;
-  }
-}
-// queues the job and the fold of its partials; returns the floats of `part` it took
-int64_t cs_add(GsfCsTable& tb, SrFoldQueue& folds, const float* a, const float* mul, const float* mean, const float* rstd, int W, float* part,
-               float* dst, hipStream_t st) {
-  const int chunks = (int)gsf_cs_chunks(tb.T);
-  GsfCsJob& j = tb.job[tb.n++];
-  j.a = a; j.mul = mul; j.mean = mean; j.rstd = rstd; j.part = part; j.W = W; j.ncb = (W + 15) / 16; j.blk_begin = tb.nblocks;
-  tb.nblocks += j.ncb * chunks;
-  folds.add(part, (int64_t)W, chunks, W, dst, st, /*own_buffer=*/true);
-  return (int64_t)chunks * W;
-}
-
-// ---- weight gradients over the rows: part[s][n][f] = sum over the rows t of split s of G[t][n] U[t][f] -----------------------------------
-// G [T][Rn] = the gradient of the Linear's output, U = the Linear's input formed as it is read: (X - mean[t]) rstd[t] gamma + beta from the
-// layer's raw input X (mean NULL: X is already normalised).  A wave owns 16 rows x 64 columns of the weight and walks its split four
-// rows of T per matrix-core step: lane (i, q) supplies G[t + q][n0 + i] and U[t + q][f0 + 16 c + i], 64-byte runs of both.  The splits
-// are folded by the backward's one fold launch (fixed order).
-__global__ __launch_bounds__(256) void gsf_wgrad_kernel(const float* __restrict__ G, int Rn, const float* __restrict__ X, int N, int64_t T,
-                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta, int64_t chunk,
-                                                        float* __restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int i = lane & 15, q = lane >> 4;
-  const int n0 = ((int)blockIdx.x * 4 + wave) * 16, f0 = (int)blockIdx.y * 64;
-  if (n0 >= Rn) return;
-  const int64_t t_begin = (int64_t)blockIdx.z * chunk, t_end = t_begin + chunk < T ? t_begin + chunk : T;
-  const Src gs = make_src(G, T * Rn), xs = make_src(X, T * N), ms = make_src(mean, mean != nullptr ? T : 0),
-            rs = make_src(rstd, mean != nullptr ? T : 0);
-  const bool nok = n0 + i < Rn, normed = mean == nullptr;
-  bool fok[4];
-  float ga[4], be[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int f = f0 + 16 * c + i;
-    fok[c] = f < N;
-    ga[c] = fok[c] ? gamma[f] : 0.0f;
-    be[c] = fok[c] ? beta[f] : 0.0f;
-  }
-  f32x4 acc[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int64_t t0 = t_begin; t0 < t_end; t0 += 4) {
-    const int64_t t = t0 + q;
-    const bool tok = t < t_end;
-    const float a = buf_ld1(gs, (tok && nok) ? (unsigned)((t * Rn + n0 + i) * 4) : ULTR_OOB);
-    const float mu = buf_ld1(ms, tok ? (unsigned)(t * 4) : ULTR_OOB);
-    const float rr = normed ? 1.0f : buf_ld1(rs, tok ? (unsigned)(t * 4) : ULTR_OOB);
-    float x[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) x[c] = buf_ld1(xs, (tok && fok[c]) ? (unsigned)((t * N + f0 + 16 * c + i) * 4) : ULTR_OOB);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = mfma16(a, (tok && fok[c]) ? fmaf((x[c] - mu) * rr, ga[c], be[c]) : 0.0f, acc[c]);
-  }
-  float* ps = part + (int64_t)blockIdx.z * Rn * N;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = n0 + 4 * q + r, col = f0 + 16 * c + i;
-      if (row < Rn && col < N) ps[(int64_t)row * N + col] = acc[c][r];
-    }
-}
-void wgrad_launch(SrFoldQueue& folds, const float* G, int Rn, const float* X, int N, int64_t T, const float* mean, const float* rstd,
-                  const float* gamma, const float* beta, float* part, float* dst, hipStream_t st) {
-  const int64_t chunk = gsf_wg_chunk(T);
-  const int splits = (int)gsf_wg_splits(T);
-  hipLaunchKernelGGL(gsf_wgrad_kernel, dim3((unsigned)((Rn + 63) / 64), (unsigned)((N + 63) / 64), (unsigned)splits), dim3(256), 0, st, G, Rn, X,
-                     N, T, mean, rstd, gamma, beta, chunk, part);
-  folds.add(part, (int64_t)Rn * N, splits, Rn * N, dst, st, /*own_buffer=*/true);
-}
-
 // ---- the A operand of the first product ----------------------------------------------------------------------------------------------------
 // Row r = b L + g, contraction index k in slot k / F: the feature row of the document at place (g + k / F) mod L (a PAD is the zero row),
 // LayerNorm applied from the row's statistics: (x - mean[r]) rstd[r] gamma[k] + beta[k].  F is a multiple of 4, so a 16-byte piece never
@@ -425,7 +308,6 @@ struct AGroupLN {
   }
 };
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 unsigned rows4(int64_t T) { return (unsigned)((T + 3) / 4); }
 
 int size_query(const ultr_gsf_desc* c, int64_t B, int64_t L, int64_t T, bool train, GsfPlan& p) {
@@ -497,7 +379,7 @@ int ultr_gsf_forward(const ultr_gsf_desc* c, const float* params, const float* f
   gsf_make_plan(c, batch, list_size, (int64_t)batch * list_size, train, p);
   if (!gsf_sizes_fit(p, n_docs)) return ULTR_E_UNSUPPORTED;
   float* sv = (float*)(train ? saved : work);
-  if (!aligned16(params) || !aligned16(sv) || !aligned16(features)) return ULTR_E_BADARG;
+  if (!ultr_aligned16(params) || !ultr_aligned16(sv) || !ultr_aligned16(features)) return ULTR_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   const int B = p.B, L = p.L, top = p.nl - 1;
   const int64_t T = p.T;
@@ -546,7 +428,7 @@ int ultr_gsf_backward(const ultr_gsf_desc* c, const float* params, const float* 
   GsfPlan p;
   gsf_make_plan(c, batch, list_size, (int64_t)batch * list_size, true, p);
   if (!gsf_sizes_fit(p, n_docs)) return ULTR_E_UNSUPPORTED;
-  if (!aligned16(params) || !aligned16(saved) || !aligned16(workspace) || !aligned16(grads)) return ULTR_E_BADARG;
+  if (!ultr_aligned16(params) || !ultr_aligned16(saved) || !ultr_aligned16(workspace) || !ultr_aligned16(grads)) return ULTR_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   const float* sv = (const float*)saved;
   float* ws = (float*)workspace;
@@ -565,15 +447,14 @@ int ultr_gsf_backward(const ultr_gsf_desc* c, const float* params, const float* 
     const float* mean = j == 0 ? nullptr : sv + p.s_mean[j];
     const float* rstd = j == 0 ? nullptr : sv + p.s_rstd[j];
     {
-      GsfCsTable tb;
-      tb.n = 0; tb.nblocks = 0; tb.T = T;
+      RgCsTable tb;  // the three column sums of the layer in one launch
       float* part = ws + p.w_cs[j];
-      part += cs_add(tb, folds, dz, nullptr, nullptr, nullptr, p.M[j], part, grads + p.off_c[j], st);
-      part += cs_add(tb, folds, du, nullptr, nullptr, nullptr, p.K[j], part, grads + p.off_b[j], st);
-      part += cs_add(tb, folds, du, X, mean, rstd, p.K[j], part, grads + p.off_g[j], st);
-      hipLaunchKernelGGL(gsf_colsum_kernel, dim3((unsigned)tb.nblocks), dim3(256), 0, st, tb);
+      part += tb.add(folds, dz, nullptr, nullptr, nullptr, T, p.M[j], part, grads + p.off_c[j], st);
+      part += tb.add(folds, du, nullptr, nullptr, nullptr, T, p.K[j], part, grads + p.off_b[j], st);
+      part += tb.add(folds, du, X, mean, rstd, T, p.K[j], part, grads + p.off_g[j], st);
+      tb.launch(st);
     }
-    wgrad_launch(folds, dz, p.M[j], X, p.K[j], T, mean, rstd, params + p.off_g[j], params + p.off_b[j], ws + p.w_wp[j], grads + p.off_w[j], st);
+    rg_wgrad(folds, dz, p.M[j], X, p.K[j], T, 0, mean, rstd, params + p.off_g[j], params + p.off_b[j], ws + p.w_wp[j], grads + p.off_w[j], st);
     if (j > 0) {  // through LayerNorm_j and the activation below it, then the data gradient of Linear_{j-1} (layer 0: for gamma / beta only)
       float* dzb = ws + p.w_dz[j - 1];
       hipLaunchKernelGGL(gsf_ln_bwd_kernel, dim3(rows4(T)), dim3(256), 0, st, du, X, mean, rstd, params + p.off_g[j], T, p.K[j], p.act, dzb);
@@ -583,11 +464,7 @@ int ultr_gsf_backward(const ultr_gsf_desc* c, const float* params, const float* 
       if ((err = ugemm::run<false>(d, a, params + p.off_w[j - 1], e, st)) != hipSuccess) return (int)err;
     }
   }
-  if (loss_ws != nullptr && n_loss_parts > 0) {  // the step tail
-    const int tail = (int)ultr_tail_len(list_size);
-    folds.add((const float*)loss_ws, (int64_t)tail, (int)n_loss_parts, tail, grads + p.P, st, /*own_buffer=*/true);
-  }
-  folds.flush(st);
+  rg_fold_all(folds, loss_ws, n_loss_parts, list_size, grads + p.P, st);
   return (int)hipGetLastError();
 }
 

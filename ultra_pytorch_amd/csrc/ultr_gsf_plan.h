@@ -4,11 +4,10 @@
 #include <stdint.h>
 
 #include "../../include/ultr_hip.h"
+#include "ultr_rowgrad_plan.h"
 
 #define GSF_MAX_GROUP 8                   // documents per group (the slots a row of the first product gathers)
 #define GSF_MAXL (ULTR_MAX_HIDDEN + 1)    // Linear layers: the hidden ones and the head
-#define GSF_CS_ROWS 256                   // rows per partial of the column-sum launch
-#define GSF_WG_SPLITS 64                  // at most this many row splits of a weight-gradient launch
 
 struct GsfPlan {
   int F, m, nl, act;        // nl = n_hidden + 1 Linear layers; layer nl - 1 is the head (m outputs)
@@ -35,15 +34,6 @@ struct GsfPlan {
   int64_t w_wp[GSF_MAXL];   // weight-gradient partials of layer j: [splits][M[j] K[j]]
   int64_t ws_floats;
 };
-
-static inline int64_t gsf_up4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-static inline int64_t gsf_cs_chunks(int64_t T) { return (T + GSF_CS_ROWS - 1) / GSF_CS_ROWS; }
-// rows per split of gsf_wgrad_kernel: at least 128 (32 matrix-core steps), a multiple of 4, at most GSF_WG_SPLITS splits
-static inline int64_t gsf_wg_chunk(int64_t T) {
-  const int64_t c = gsf_up4((T + GSF_WG_SPLITS - 1) / GSF_WG_SPLITS);
-  return c < 128 ? 128 : c;
-}
-static inline int64_t gsf_wg_splits(int64_t T) { return (T + gsf_wg_chunk(T) - 1) / gsf_wg_chunk(T); }
 
 // is it a model at all?  (the parameter layout is defined for every such descriptor, supported by the kernels or not)
 static inline bool gsf_is_model(const ultr_gsf_desc* c) {
@@ -90,8 +80,8 @@ static inline void gsf_make_plan(const ultr_gsf_desc* c, int64_t B, int64_t L, i
   int64_t off = 0;
   p.s_slots = off; off += T * GSF_MAX_GROUP;
   for (int j = 0; j < p.nl; ++j) {
-    p.s_mean[j] = off; off += gsf_up4(T);
-    p.s_rstd[j] = off; off += gsf_up4(T);
+    p.s_mean[j] = off; off += rg_up4(T);
+    p.s_rstd[j] = off; off += rg_up4(T);
   }
   if (train) {
     for (int j = 0; j < top; ++j) { p.s_a[j] = off; off += T * p.M[j]; }
@@ -102,17 +92,17 @@ static inline void gsf_make_plan(const ultr_gsf_desc* c, int64_t B, int64_t L, i
     for (int j = 0; j < top; ++j) p.s_a[j] = off + (j & 1 ? w[0] : 0);
     off += w[0] + w[1];
   }
-  p.s_o = off; off += gsf_up4(T * p.m);
+  p.s_o = off; off += rg_up4(T * p.m);
   p.score_floats = off;
   p.s_xhat = off; off += T * p.K[0];
   p.saved_floats = off;
   off = 0;
-  p.w_do = off; off += gsf_up4(T * p.m);
+  p.w_do = off; off += rg_up4(T * p.m);
   for (int j = 0; j < top; ++j) { p.w_dz[j] = off; off += T * p.M[j]; }
   p.w_du = off; off += T * p.maxK;
   for (int j = 0; j < p.nl; ++j) {
-    p.w_cs[j] = off; off += gsf_up4(gsf_cs_chunks(T) * (p.M[j] + 2 * (int64_t)p.K[j]));
-    p.w_wp[j] = off; off += gsf_up4(gsf_wg_splits(T) * (int64_t)p.M[j] * p.K[j]);
+    p.w_cs[j] = off; off += rg_up4(rg_cs_chunks(T) * (p.M[j] + 2 * (int64_t)p.K[j]));
+    p.w_wp[j] = off; off += rg_up4(rg_wg_splits(T) * (int64_t)p.M[j] * p.K[j]);
   }
   p.ws_floats = off;
 }

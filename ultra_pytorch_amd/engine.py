@@ -661,6 +661,10 @@ class StagedStepEngine(StepEngine):
     their size (hundreds of microseconds to milliseconds per step) the host is not on the critical path.  A subclass supplies _alloc,
     forward and backward (which leaves the sum-of-squares partials in self.bwd_ws)."""
 
+    def _sumsq_floats(self):
+        """Floats of self.bwd_ws: the sum-of-squares partials of ultr_grad_sumsq / ultr_apply_update."""
+        return (self.P + self.tail + 63) // 64 + self.P // 4096 + 16
+
     def _range_flag(self):
         """Device address of the model's split-half range word (ultr_update_desc::range_flag), None: it builds no such planes."""
         return None
@@ -707,8 +711,7 @@ class SetRankStepEngine(StagedStepEngine):
     def _alloc(self, shape, device):
         self.saved = _f32(shape.saved_bytes(self.N) // 4, device)
         self.sr_ws = _f32(shape.workspace_bytes(self.N) // 4, device)
-        # sum-of-squares partials of ultr_grad_sumsq / ultr_apply_update
-        self.bwd_ws = _f32((self.P + self.tail + 63) // 64 + self.P // 4096 + 16, device)
+        self.bwd_ws = _f32(self._sumsq_floats(), device)
         self._flag_off = shape.range_flag_offset(self.N)
         self.saved[self._flag_off].zero_()  # (every forward zeroes it again: this is for a report before the first forward)
         self.dropout_stream = self.rank
@@ -783,8 +786,7 @@ class DlcmStepEngine(StagedStepEngine):
     def _alloc(self, shape, device):
         self.saved = _f32(shape.saved_bytes(self.N) // 4, device)
         self.dl_ws = _f32(shape.workspace_bytes(self.B, self.L) // 4, device)
-        # sum-of-squares partials of ultr_grad_sumsq / ultr_apply_update
-        self.bwd_ws = _f32((self.P + self.tail + 63) // 64 + self.P // 4096 + 16, device)
+        self.bwd_ws = _f32(self._sumsq_floats(), device)
 
     def forward(self, params, features, n_docs, docids, scores=None, train=False):
         scores = self.scores if scores is None else scores
@@ -797,8 +799,9 @@ class DlcmStepEngine(StagedStepEngine):
         hip_ops.grad_sumsq(self.grads, self.P, self.L, self.bwd_ws)
 
 
-class DlcmEvalEngine(EvalEngine):
-    """validation() for DLCM: the scoring form of ultr_dlcm_forward (no record for a backward), then the metric launch."""
+class StagedEvalEngine(EvalEngine):
+    """validation() for a staged model: the scoring form of its forward on `work` (no record for a backward), then the metric launch.
+    A subclass supplies forward."""
 
     def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10), metrics=("ndcg",)):
         super().__init__(shape, batch, list_size, device, topn=topn, metrics=metrics)
@@ -808,6 +811,10 @@ class DlcmEvalEngine(EvalEngine):
         self.forward(params, features, n_docs, docids)
         self._ndcg(labels, docids, n_docs)
         return self.scores, self.ndcg
+
+
+class DlcmEvalEngine(StagedEvalEngine):
+    """validation() for DLCM: ultr_dlcm_forward's scoring form."""
 
     def forward(self, params, features, n_docs, docids):
         hip_ops.dlcm_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, work=self.work)
@@ -828,8 +835,7 @@ class GsfStepEngine(StagedStepEngine):
     def _alloc(self, shape, device):
         self.saved = _f32(shape.saved_bytes(self.N) // 4, device)
         self.gsf_ws = _f32(shape.workspace_bytes(self.B, self.L) // 4, device)
-        # sum-of-squares partials of ultr_grad_sumsq / ultr_apply_update
-        self.bwd_ws = _f32((self.P + self.tail + 63) // 64 + self.P // 4096 + 16, device)
+        self.bwd_ws = _f32(self._sumsq_floats(), device)
         self.perm = torch.zeros(self.B, self.L, dtype=torch.int32, device=device)
         self._perm = None  # the draw of the forward in flight (None: presented order)
 
@@ -848,17 +854,8 @@ class GsfStepEngine(StagedStepEngine):
         hip_ops.grad_sumsq(self.grads, self.P, self.L, self.bwd_ws)
 
 
-class GsfEvalEngine(EvalEngine):
-    """validation() for GSF: the scoring form of ultr_gsf_forward in presented order (no record for a backward), then the metric launch."""
-
-    def __init__(self, shape, batch, list_size, device, topn=(1, 3, 5, 10), metrics=("ndcg",)):
-        super().__init__(shape, batch, list_size, device, topn=topn, metrics=metrics)
-        self.work = _f32(shape.score_bytes(self.B * self.L) // 4, device)
-
-    def run(self, params, features, n_docs, docids, labels):
-        self.forward(params, features, n_docs, docids)
-        self._ndcg(labels, docids, n_docs)
-        return self.scores, self.ndcg
+class GsfEvalEngine(StagedEvalEngine):
+    """validation() for GSF: ultr_gsf_forward's scoring form, in presented order."""
 
     def forward(self, params, features, n_docs, docids):
         hip_ops.gsf_forward(self.shape, params, features, n_docs, docids, self.B, self.L, self.scores, work=self.work)

@@ -246,13 +246,37 @@ def setrank_attn_path(shape, L, backward=False):
     return _lib.SR_ATTN_PATHS[rc]
 
 
-class DlcmShape:
+class _StagedSizes:
+    """The size queries of a staged model's shape (DLCM, GSF): ultr_<PREFIX>_saved_bytes / _score_bytes / _workspace_bytes on self.desc.
+    A model the kernels do not take raises UltrHipError, as the calls do."""
+
+    PREFIX = None
+
+    def _bytes(self, query, *args):
+        fn = "ultr_%s_%s_bytes" % (self.PREFIX, query)
+        n = int(getattr(self.lib, fn)(ctypes.byref(self.desc), *args))
+        check(min(n, 0), fn)
+        return n
+
+    def saved_bytes(self, n_rows):
+        return self._bytes("saved", int(n_rows))
+
+    def score_bytes(self, n_rows):
+        """Bytes of the scoring form's buffer: what one launch hands to the next, nothing is kept for a backward."""
+        return self._bytes("score", int(n_rows))
+
+    def workspace_bytes(self, B, L):
+        return self._bytes("workspace", int(B), int(L))
+
+
+class DlcmShape(_StagedSizes):
     """Host-side geometry of one DLCM model (include/ultr_hip.h: ultr_dlcm_*): descriptor + flat parameter layout in state_dict order.
     `hidden_size` 0 means feature_size (the paper's choice).  feature_size and hidden_size must be multiples of 4: the size queries of
     any other model raise UltrHipError ("unsupported shape"), as the calls do; the layout is defined for every model."""
 
     NAMES = ("layer_norm.weight", "layer_norm.bias", "gru.weight_ih_l0", "gru.weight_hh_l0", "gru.bias_ih_l0", "gru.bias_hh_l0",
              "att_linear.weight", "att_linear.bias", "att_v.weight")
+    PREFIX = "dlcm"
 
     def __init__(self, feature_size, hidden_size=0, num_heads=3):
         self.lib = _lib.load()
@@ -271,21 +295,6 @@ class DlcmShape:
         shapes = ((F,), (F,), (3 * H, F), (3 * H, H), (3 * H,), (3 * H,), (hd * H, H), (hd * H,), (1, hd))
         return [(n, s, o) for n, s, o in zip(self.NAMES, shapes, self.offsets)]
 
-    def _bytes(self, fn, *args):
-        n = int(getattr(self.lib, fn)(ctypes.byref(self.desc), *args))
-        check(min(n, 0), fn)
-        return n
-
-    def saved_bytes(self, n_rows):
-        return self._bytes("ultr_dlcm_saved_bytes", int(n_rows))
-
-    def score_bytes(self, n_rows):
-        """Bytes of the scoring form's buffer: what one launch hands to the next, nothing for a backward."""
-        return self._bytes("ultr_dlcm_score_bytes", int(n_rows))
-
-    def workspace_bytes(self, B, L):
-        return self._bytes("ultr_dlcm_workspace_bytes", int(B), int(L))
-
 
 def dlcm_forward(shape, params, features, n_docs, docids, B, L, scores, saved=None, work=None):
     """saved: the training form; saved None: the scoring form on `work` (shape.score_bytes) - the same scores bit for bit."""
@@ -299,7 +308,7 @@ def dlcm_backward(shape, params, features, n_docs, docids, B, L, saved, dscores,
                                        _stream()), "ultr_dlcm_backward")
 
 
-class GsfShape:
+class GsfShape(_StagedSizes):
     """Host-side geometry of one GSF model (include/ultr_hip.h: ultr_gsf_*): descriptor + flat parameter layout, the DNN's keys in the
     DNN's order with layer 0 reading group_size * feature_size inputs and the last layer writing group_size outputs.  feature_size and
     every hidden width must be multiples of 4 and group_size at most 8: the size queries of any other model raise UltrHipError
@@ -308,6 +317,8 @@ class GsfShape:
     The training shuffle's key rides along, as SetRankShape's dropout key does: `train_shuffle`, `shuffle_seed` (the owner of the shape
     sets it; ranking_model.GSF captures torch.initial_seed()) and `shuffle_step`, the count of shuffled training forwards so far -
     engines are per batch shape, cached and evicted, so the counter is the model's, shared through this object."""
+
+    PREFIX = "gsf"
 
     def __init__(self, feature_size, hidden, activation="elu", group_size=2, train_shuffle=True):
         self.lib = _lib.load()
@@ -337,21 +348,6 @@ class GsfShape:
         self.train_shuffle, self.shuffle_seed, self.shuffle_step = bool(train_shuffle), 0, 0
 
     layout = DnnShape.layout
-
-    def _bytes(self, fn, *args):
-        n = int(getattr(self.lib, fn)(ctypes.byref(self.desc), *args))
-        check(min(n, 0), fn)
-        return n
-
-    def saved_bytes(self, n_rows):
-        return self._bytes("ultr_gsf_saved_bytes", int(n_rows))
-
-    def score_bytes(self, n_rows):
-        """Bytes of the scoring form's buffer: the layer outputs alternate between two buffers, nothing is kept for a backward."""
-        return self._bytes("ultr_gsf_score_bytes", int(n_rows))
-
-    def workspace_bytes(self, B, L):
-        return self._bytes("ultr_gsf_workspace_bytes", int(B), int(L))
 
     def next_shuffle_step(self):
         """The step number of the shuffled training forward about to run; counts it."""
