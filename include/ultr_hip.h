@@ -102,10 +102,10 @@ int64_t ultr_loss_workspace_bytes(int64_t batch, int32_t list_size);
  * ultr_setrank_backward */
 int64_t ultr_loss_part_count(int64_t batch);
 /* Dynamic LDS in bytes that the stand-alone loss kernel of `algo` (ULTR_ALGO_SOFTMAX .. ULTR_ALGO_PDGD, ULTR_ALGO_TWOTOWER,
- * ULTR_ALGO_PLRANK) requests at list_size
+ * ULTR_ALGO_PLRANK, ULTR_ALGO_AFFINE) requests at list_size
  * (additive within ABI 8; host-only, launches nothing) - read from the layout the kernel itself carves its LDS with
  * (csrc/ultr_listloss.h).  ULTR_E_UNSUPPORTED where the entry would refuse the list size: beyond 64 KiB for ultr_softmax_ce,
- * ultr_dla_loss, ultr_regem_loss and ultr_twotower_loss, beyond 160 KiB for ultr_pairdebias_loss, ultr_lambdarank_loss, ultr_prs_loss
+ * ultr_affine_loss, ultr_dla_loss, ultr_regem_loss and ultr_twotower_loss, beyond 160 KiB for ultr_pairdebias_loss, ultr_lambdarank_loss, ultr_prs_loss
  * and ultr_plrank_loss, beyond 256
  * documents for ultr_pdgd_loss - the longest accepted lists are stated with each entry below.  ULTR_E_BADARG: an algorithm without a
  * stand-alone loss kernel, list_size <= 0. */
@@ -334,6 +334,24 @@ int ultr_twotower_loss(const float* scores, const float* labels, const float* bi
 int ultr_plrank_loss(const float* scores, const float* labels, const float* pw, const float* ipw_table, int32_t n_ipw,
                      const int32_t* docids, int64_t n_docs, int32_t cutoff, int32_t n_samples, int32_t gain, uint64_t rng_seed,
                      uint64_t rng_step, int32_t batch, int32_t list_size, float* dscores, int32_t* perm_out, void* loss_ws, void* stream);
+
+/* ---- AffineRank: listwise softmax loss under the affine correction of trust bias (additive within ABI 8) ----
+ * The project's own counterfactual learner for clicks that follow P(click | rank k, relevance gamma) = alpha_k gamma + beta_k; the law
+ * is DESIGN.md section 4e.  Per list of L positions, c = labels[l, b] as it is, k = min(l, n_aff - 1):
+ *   live position: docids == NULL, or docids[l, b] in [0, n_docs);
+ *   w_l = live ? (c - beta[k]) / alpha[k] : 0  (the division correctly rounded);  the softmax runs over all L positions (a PAD stays in
+ *   the denominator, as in ultr_softmax_ce);  loss_b = sum_l w_l (lse - s_l);
+ *   dscores[b, l] = softmax_l W_b - w_l,  W_b = sum_l w_l accumulated in double and rounded once.
+ * w_l, W_b and loss_b may be negative or zero.  Step tail [sum_b loss_b, 1 per list, 0, 0, zeros]: D counts lists (the update divides).
+ * No atomics: the same inputs give the same bits.  alpha [n_aff] must be > 0 (the caller's check; learning_algorithm.AffineRank makes it).
+ * list_size up to 4095 (64 KiB of LDS, ultr_loss_lds_bytes); beyond, ULTR_E_UNSUPPORTED and nothing is launched.
+ * ULTR_E_BADARG: a missing scores / labels / alpha / beta / dscores / loss_ws, batch <= 0, list_size <= 0, n_aff <= 0, docids with
+ * n_docs < 0.
+ * In ultr_train_step: ipw_table = [alpha(n) | beta(n)], n_ipw = n, ultr_update_desc::logits_to_prob bit 0 = PADs are masked
+ * (ULTR_AFFINE_MASK).  Out of scope: estimating (alpha, beta) from clicks, data parallelism. */
+#define ULTR_AFFINE_MASK 1
+int ultr_affine_loss(const float* scores, const float* labels, const float* alpha, const float* beta, int32_t n_aff,
+                     const int32_t* docids, int64_t n_docs, int32_t batch, int32_t list_size, float* dscores, void* loss_ws, void* stream);
 
 /* ---- PRSrank: propensity-ratio-scored LambdaRank -------------------------------------
  * Replaces PRSrank.train's propensity + loss section (prs_rank.py:94-176) + dcg/compute_delta_ndcg
@@ -602,7 +620,10 @@ enum ultr_algo { ULTR_ALGO_SOFTMAX = 0, ULTR_ALGO_DLA = 1, ULTR_ALGO_PAIRDEBIAS 
                  /* PLRank (additive within ABI 8): ultr_plrank_loss, no aux; cutoff, sample count and gain in logits_to_prob.  The
                   * value 10 is left out as 8 is and stays ULTR_E_BADARG everywhere: tests/test_twotower_cpu.py holds `algo = 10` to
                   * be a bad descriptor. */
-                 ULTR_ALGO_PLRANK = 11 };
+                 ULTR_ALGO_PLRANK = 11,
+                 /* AffineRank (additive within ABI 8): ultr_affine_loss, no aux; ipw_table carries [alpha | beta], the PAD-mask flag
+                  * rides in logits_to_prob. */
+                 ULTR_ALGO_AFFINE = 12 };
 /* ULTR_OPT_ADAM: torch.optim.Adam with its defaults (no weight decay, no amsgrad), applied to the gradient Adagrad / SGD get - after
  * the 1 / D scaling, the l2_loss term and the clip.  For step t = 1, 2, ...:
  *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
@@ -618,7 +639,8 @@ typedef struct ultr_update_desc {
   int32_t optimizer;       /* ultr_opt (grad_strategy 'ada' / 'sgd' / 'adam') */
   int32_t list_size;       /* L */
   int32_t logits_to_prob;  /* DLA: 0 softmax, 1 sigmoid.  TwoTower (same field, the struct's layout is unchanged): bit 0 = the towers
-                            * combine as a sum (ULTR_TWOTOWER_SUM), bit 1 = PAD positions are masked (ULTR_TWOTOWER_MASK).  PLRank: ULTR_PLRANK_PACK(cutoff, n_samples, gain) */
+                            * combine as a sum (ULTR_TWOTOWER_SUM), bit 1 = PAD positions are masked (ULTR_TWOTOWER_MASK).  PLRank: ULTR_PLRANK_PACK(cutoff, n_samples, gain).
+                            * AffineRank: bit 0 = PAD positions are masked (ULTR_AFFINE_MASK) */
   int64_t n_params;        /* P */
   float learning_rate;
   float max_gradient_norm; /* <= 0 disables clipping */
@@ -665,7 +687,7 @@ int64_t ultr_opt_state_floats(const ultr_update_desc* u);
 /* params/state [P] (ultr_opt_state_floats) updated in place; grads = the buffer ultr_dnn_backward filled (possibly
  * all-reduced).  ULTR_OPT_ADAM: state == NULL or adam_t == 0 is ULTR_E_BADARG (here and in ultr_train_step, before anything is
  * launched), as is an optimizer outside ultr_opt.  aux = prop_params[L+1] (DLA) or [t_plus(L) | t_minus(L)] (PairDebias /
- * LambdaRank), updated in place; NULL for SOFTMAX, PRS and PLRANK.  d + wt (both may be NULL): keep the k-major weight copy
+ * LambdaRank), updated in place; NULL for SOFTMAX, PRS, PLRANK and AFFINE.  d + wt (both may be NULL): keep the k-major weight copy
  * in sync with the updated parameters.  bwd_ws = the workspace ultr_dnn_backward (or
  * ultr_grad_sumsq) left the sum-of-squares partials in.
  * scalars_out[16]: [0] loss [1] ranker grad norm (pre-clip) [2] clip coef [3] D
@@ -817,6 +839,11 @@ int ultr_dnn_forward_metrics(const ultr_dnn_desc* d, const float* params, const 
 #define ULTR_CLICK_CASCADE 1
 #define ULTR_CLICK_UBM 2 /* user-browsing model (click_models.py:113-186): exam_prob = dense [n_exam][n_exam] image of the triangular
                           * table exam[rank][distance - 1] (distance to the last click; entries beyond the diagonal unused) */
+/* Trust bias (additive within ABI 8; the project's own model): exam_prob = dense [2][n_exam] image, row 0
+ * alpha_k, row 1 beta_k; position l, k = min(l, n_exam - 1), clicks iff u < fl(fl(alpha_k * click_prob[label]) + beta_k) - two fp32
+ * roundings, no carried state.  Taken wherever a click model is: ultr_click_batch / _args, the rider of ultr_feed_train_step,
+ * ultr_online_rerank_args, ultr_dbgd_interleave_args, ultr_propensity_count. */
+#define ULTR_CLICK_TRUST 3
 int ultr_click_batch(const int32_t* lists, const float* labels, int64_t n_queries, int32_t lmax, int64_t n_docs,
                      const float* exam_prob, int32_t n_exam, const float* click_prob, int32_t n_rel, int32_t click_model,
                      uint64_t seed, uint64_t step, int32_t batch, int32_t list_size, int32_t max_tries, int32_t* docids,

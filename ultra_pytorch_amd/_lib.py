@@ -24,6 +24,8 @@ PLRANK_MAX_SAMPLES = 4095
 def plrank_pack(cutoff, n_samples, gain):
     """ULTR_PLRANK_PACK: what ultr_update_desc::logits_to_prob carries for a PLRank step (bits 0-11 cutoff, 12-23 samples, 24 exp2)."""
     return min(int(cutoff), 4095) | (int(n_samples) << 12) | (PLRANK_GAIN[gain] << 24)
+ALGO_AFFINE = 12
+AFFINE_MASK = 1  # ULTR_AFFINE_MASK: bit 0 of ultr_update_desc::logits_to_prob of an AffineRank step
 OPT_ADAGRAD, OPT_SGD, OPT_ADAM = 0, 1, 2
 ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-8  # include/ultr_hip.h: ULTR_ADAM_*
 
@@ -200,6 +202,7 @@ SIGNATURES = {
     "ultr_twotower_loss": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_plrank_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint64,
                                  c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "ultr_affine_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "ultr_setrank_param_count": (c_i64, [ctypes.POINTER(SetRankDesc)]),
     "ultr_setrank_saved_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),
     "ultr_setrank_workspace_bytes": (c_i64, [ctypes.POINTER(SetRankDesc), c_i64]),

@@ -1,4 +1,4 @@
-// ultr_click.h - the simulated user: one view of a click model (ClickModel: the two tables, their sizes, PBM / cascade / UBM), the one
+// ultr_click.h - the simulated user: one view of a click model (ClickModel: the two tables, their sizes, PBM / cascade / UBM / trust), the one
 // statement of when it is valid (click_model_ok), the per-position decisions (click_decide) and the walk of one wavefront over one
 // list (wave_click_walk).  Every kernel that draws clicks goes through the walk: click_draw (ultr_feed.h), online_rerank_kernel
 // (ultr_online.hip), dbgd_interleave_kernel (ultr_dbgd.hip) and prop_wave (ultr_propensity.hip); prop_packed, several lists per
@@ -11,7 +11,8 @@
 #include "../../include/ultr_hip.h"
 #include "ultr_device.h"
 
-// exam: [n_exam] for PBM / cascade, the dense [n_exam][n_exam] image of the triangular rank x distance table for UBM; cprob: [n_rel]
+// exam: [n_exam] for PBM / cascade, the dense [n_exam][n_exam] image of the triangular rank x distance table for UBM, the dense
+// [2][n_exam] image alpha | beta of the trust-bias model; cprob: [n_rel]
 struct ClickModel {
   const float* exam;
   const float* cprob;
@@ -27,7 +28,7 @@ __host__ __device__ __forceinline__ ClickModel click_model_of(const A& a) {
 // what every entry refuses with ULTR_E_BADARG (UBM's walk reads column n_exam - 2 of the last row)
 inline bool click_model_ok(const ClickModel& m) {
   return m.exam && m.cprob && m.n_exam > 0 && m.n_rel > 0 &&
-         (m.model == ULTR_CLICK_PBM || m.model == ULTR_CLICK_CASCADE || m.model == ULTR_CLICK_UBM) &&
+         (m.model == ULTR_CLICK_PBM || m.model == ULTR_CLICK_CASCADE || m.model == ULTR_CLICK_UBM || m.model == ULTR_CLICK_TRUST) &&
          !(m.model == ULTR_CLICK_UBM && m.n_exam < 2);
 }
 
@@ -48,8 +49,16 @@ __device__ __forceinline__ float ubm_exam_prob(const ClickModel& cm, int rank, i
   return exam[(n_exam - 1) * n_exam + (dist < n_exam - 1 ? dist - 1 : (n_exam >= 2 ? n_exam - 2 : 0))];
 }
 
+// Trust bias: P(click) = alpha_k cp + beta_k, the product and the sum each rounded on its own (contraction is off in this body: a fused
+// multiply-add would round once, and numpy float32 could not restate the decision bit for bit)
+__device__ __forceinline__ float trust_click_prob(float alpha, float cp, float beta) {
+#pragma clang fp contract(off)
+  const float prod = alpha * cp;
+  return prod + beta;
+}
+
 // The click decision of position l = l0 + lane (in: l < L) of one chunk of 64 positions of an L-position list, from its label y and its
-// uniform u: PBM, cascade or UBM as ultr_click_batch draws them.  clicked_before (cascade: a click in an earlier chunk) and last_click
+// uniform u: PBM, cascade, UBM or trust bias (no carried state, as PBM) as ultr_click_batch draws them.  clicked_before (cascade: a click in an earlier chunk) and last_click
 // (UBM: the rank of the last click so far) are wave-uniform and carried from chunk to chunk; the caller starts them at false / -1.
 // (The body takes the tables as __restrict__ parameters, the one place where the compiler honours the qualifier: the table reads do
 // not alias the clicks the caller writes between two chunks.  Without it update_tiled_kernel, which carries click_draw as a rider,
@@ -66,6 +75,9 @@ __device__ __forceinline__ float click_decide_tables(const float* __restrict__ e
       // click iff u < exam x cp: the walk below compares u / cp with the examination probability; cp == 0 (a relevance level that
       // is never clicked) gives +inf or NaN, and both compare false against every probability - no click, as intended
       ck = u / cp;
+    } else if (cm.model == ULTR_CLICK_TRUST) {
+      const int k = l < cm.n_exam ? l : cm.n_exam - 1;
+      ck = (u < trust_click_prob(cm.exam[k], cp, cm.exam[cm.n_exam + k])) ? 1.f : 0.f;
     } else {
       ck = (u < cm.exam[l < cm.n_exam ? l : cm.n_exam - 1] * cp) ? 1.f : 0.f;
     }

@@ -1,5 +1,5 @@
-// ultr_listloss.h — what the nine list-loss kernels share (ultr_loss.hip, ultr_prs.hip, ultr_pdgd.hip, ultr_twotower.hip,
-// ultr_plrank.hip):
+// ultr_listloss.h — what the ten list-loss kernels share (ultr_loss.hip, ultr_prs.hip, ultr_pdgd.hip, ultr_twotower.hip,
+// ultr_plrank.hip, ultr_affine.hip):
 //   * one LDS layout per kernel, a __host__ __device__ struct built from L: the kernel takes its pointers from the offsets, the
 //     launcher and ultr_loss_lds_bytes take `bytes` - the two sides cannot drift apart;
 //   * launch_list_loss, the one launcher behind the extern "C" entries;
@@ -54,6 +54,9 @@ struct SoftmaxLds : LdsCarve {  // list_size <= 4095
   int64_t bytes = end();
   __host__ __device__ explicit SoftmaxLds(int L_) : LdsCarve(L_) {}
 };
+
+// ultr_affine.hip stages what softmax_ce_kernel stages, scores and weights: its layout under the kernel's own name (list_size <= 4095)
+using AffineLds = SoftmaxLds;
 
 struct RegemLds : LdsCarve {  // list_size <= 8190
   static constexpr int64_t limit = LOSS_LDS_DEFAULT;
@@ -236,6 +239,7 @@ static inline int loss_route(int algo, int L) {
   // TwoTower has the one kernel: a list beyond its layout is refused here, before the forward is launched
   if (algo == ULTR_ALGO_TWOTOWER && L > 0 && TwoTowerLds(L).bytes > TwoTowerLds::limit) return ULTR_E_UNSUPPORTED;
   if (algo == ULTR_ALGO_PLRANK && L > 0 && PlRankLds(L).bytes > PlRankLds::limit) return ULTR_E_UNSUPPORTED;  // PLRank likewise
+  if (algo == ULTR_ALGO_AFFINE && L > 0 && AffineLds(L).bytes > AffineLds::limit) return ULTR_E_UNSUPPORTED;  // ... and AffineRank
   if (!loss_short_refuses(algo, L)) return LOSS_ROUTE_SHORT;
   return loss_long_bytes(algo, L) >= 0 ? LOSS_ROUTE_LONG : ULTR_E_UNSUPPORTED;
 }

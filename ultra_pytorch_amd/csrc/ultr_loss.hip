@@ -41,6 +41,7 @@ extern "C" int64_t ultr_loss_lds_bytes(int32_t algo, int32_t list_size) {
     case ULTR_ALGO_PRS: return lds_bytes_or_refusal<PrsLds>(list_size);
     case ULTR_ALGO_TWOTOWER: return lds_bytes_or_refusal<TwoTowerLds>(list_size);
     case ULTR_ALGO_PLRANK: return lds_bytes_or_refusal<PlRankLds>(list_size);
+    case ULTR_ALGO_AFFINE: return lds_bytes_or_refusal<AffineLds>(list_size);
     case ULTR_ALGO_PDGD: return list_size > PDGD_MAX_L ? ULTR_E_UNSUPPORTED : lds_bytes_or_refusal<PdgdLds>(list_size);
     default: return ULTR_E_BADARG;
   }

@@ -51,7 +51,7 @@ __device__ __forceinline__ void prop_packed(const ultr_propensity_args& a, const
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, seg = lane / W, pos = lane % W, base = seg * W;
   const ClickModel cm = click_model_of(a);
   ClickModel each = cm;  // the decision of each position on its own: the cascade's cut and the user-browsing walk run per segment below
-  each.model = ULTR_CLICK_PBM;
+  each.model = cm.model == ULTR_CLICK_TRUST ? ULTR_CLICK_TRUST : ULTR_CLICK_PBM;  // (trust bias carries no state either)
   const uint64_t stride = (uint64_t)gridDim.x * PROP_WAVES * SPW;
   const uint64_t slot = ((uint64_t)blockIdx.x * PROP_WAVES + wave) * SPW + seg;
   const int64_t trips = (a.n_sessions + (int64_t)stride - 1) / (int64_t)stride;

@@ -64,6 +64,8 @@ int ultr_train_step_ctx(const ultr_step_args* a, StepCtx* ctx, void* stream) {
   // ultr_listloss.h) - decided here, so that a list neither takes is refused before the forward is launched
   const int route = loss_route(a->upd->algo, a->list_size);
   if (route < 0) return route;
+  // AffineRank's table [alpha(n) | beta(n)] rides in ipw_table: a missing one is refused here too, with nothing launched
+  if (a->upd->algo == ULTR_ALGO_AFFINE && (!a->ipw_table || a->n_ipw <= 0)) return ULTR_E_BADARG;
   const bool long_list = route == LOSS_ROUTE_LONG;
   int rc;
   if (a->upd->algo == ULTR_ALGO_SOFTMAX) {
@@ -128,6 +130,11 @@ int ultr_train_step_ctx(const ultr_step_args* a, StepCtx* ctx, void* stream) {
                             (pk >> 24) & 1, a->rng_seed, a->rng_step, a->batch, a->list_size, a->dscores, nullptr, a->loss_ws, stream);
       break;
     }
+    case ULTR_ALGO_AFFINE:  // ipw_table = [alpha(n) | beta(n)], n_ipw = n; the PAD-mask flag travels in logits_to_prob
+      rc = ultr_affine_loss(a->scores, a->labels, a->ipw_table, a->ipw_table + a->n_ipw, a->n_ipw,
+                            (a->upd->logits_to_prob & ULTR_AFFINE_MASK) ? a->docids : nullptr, a->n_docs, a->batch, a->list_size,
+                            a->dscores, a->loss_ws, stream);
+      break;
     default:
       return ULTR_E_BADARG;
   }

@@ -205,10 +205,8 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
       loss = loss_sum / D;
       break;
     case ULTR_ALGO_TWOTOWER:  // the click log-likelihood: positions summed, mean over the D lists (ultr_twotower.hip)
-      gs = 1.0f / D;
-      loss = loss_sum / D;
-      break;
-    case ULTR_ALGO_PLRANK:  // minus the sampled expected DCG@K, mean over the D lists (ultr_plrank.hip)
+    case ULTR_ALGO_PLRANK:    // minus the sampled expected DCG@K, mean over the D lists (ultr_plrank.hip)
+    case ULTR_ALGO_AFFINE:    // the affine-corrected softmax loss, mean over the D lists; it may be negative (ultr_affine.hip)
       gs = 1.0f / D;
       loss = loss_sum / D;
       break;
@@ -222,8 +220,8 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
   // l2_loss > 0 (ipw_rank.py:154-157 and siblings): g += lam * p, loss += l2_loss * sum p^2 / 2.  Every algorithm but DLA
   // and PDGD hands clip_grad_norm_ a parameter generator the L2 loop has already exhausted, so NOTHING is clipped (Appendix
   // A.8); DLA adds the term to rank_loss (scaled by ranker_loss_weight with it) and clips the full gradient (dla.py:146-162);
-  // PDGD passes a FRESH model.parameters() to opt_step (pdgd.py:206-212) and clips the full gradient too.  TwoTower and PLRank are the
-  // project's own algorithms and do not inherit the quirk: their clip covers the full gradient.
+  // PDGD passes a FRESH model.parameters() to opt_step (pdgd.py:206-212) and clips the full gradient too.  TwoTower, PLRank and
+  // AffineRank are the project's own algorithms and do not inherit the quirk: their clip covers the full gradient.
   float lam = 0.f;
   bool clip = u.max_gradient_norm > 0.f;
   if (u.l2_loss > 0.f && l2_sums != nullptr) {
@@ -235,7 +233,8 @@ __device__ __forceinline__ void update_body(const ultr_update_desc& u, const Dnn
     } else {
       lam = u.l2_loss;
       loss += u.l2_loss * (0.5f * sp2);
-      clip = clip && (u.algo == ULTR_ALGO_PDGD || u.algo == ULTR_ALGO_TWOTOWER || u.algo == ULTR_ALGO_PLRANK);
+      clip = clip && (u.algo == ULTR_ALGO_PDGD || u.algo == ULTR_ALGO_TWOTOWER || u.algo == ULTR_ALGO_PLRANK ||
+                      u.algo == ULTR_ALGO_AFFINE);
     }
     norm = sqrtf(fmaxf(gs * gs * ss + 2.0f * gs * lam * sgp + lam * lam * sp2, 0.f));
   }
@@ -638,10 +637,10 @@ __global__ __launch_bounds__(256) void update_tiled_kernel(ultr_update_desc u, D
   UPD_STAMP(4);
 }
 
-// an ultr_algo value: 0 .. ULTR_ALGO_DBGD, ULTR_ALGO_TWOTOWER and ULTR_ALGO_PLRANK - the 8 and the 10 between them are none
-// (include/ultr_hip.h)
+// an ultr_algo value: 0 .. ULTR_ALGO_DBGD, ULTR_ALGO_TWOTOWER, ULTR_ALGO_PLRANK and ULTR_ALGO_AFFINE - the 8 and the 10 between them
+// are none (include/ultr_hip.h)
 static bool algo_known(int32_t algo) {
-  return (algo >= 0 && algo <= ULTR_ALGO_DBGD) || algo == ULTR_ALGO_TWOTOWER || algo == ULTR_ALGO_PLRANK;
+  return (algo >= 0 && algo <= ULTR_ALGO_DBGD) || algo == ULTR_ALGO_TWOTOWER || algo == ULTR_ALGO_PLRANK || algo == ULTR_ALGO_AFFINE;
 }
 
 extern "C" int64_t ultr_opt_state_floats(const ultr_update_desc* u) {
@@ -703,7 +702,7 @@ int ultr_apply_update_ex(const ultr_update_desc* u, const ultr_dnn_desc* d, floa
   }
   if (!algo_known(u->algo) || ultr_update_check_opt(u, state)) return ULTR_E_BADARG;
   if (u->algo != ULTR_ALGO_SOFTMAX && u->algo != ULTR_ALGO_PRS && u->algo != ULTR_ALGO_PDGD && u->algo != ULTR_ALGO_DBGD &&
-      u->algo != ULTR_ALGO_PLRANK && !aux)
+      u->algo != ULTR_ALGO_PLRANK && u->algo != ULTR_ALGO_AFFINE && !aux)
     return ULTR_E_BADARG;
   if (u->optimizer == ULTR_OPT_ADAGRAD && u->algo != ULTR_ALGO_DLA && !state) return ULTR_E_BADARG;
   if (u->l2_loss < 0.f || (u->l2_loss > 0.f && !scalars_out) ||

@@ -23,7 +23,8 @@ from .utils import metrics as metrics_mod
 
 ALGOS = {"softmax": _lib.ALGO_SOFTMAX, "dla": _lib.ALGO_DLA, "pairdebias": _lib.ALGO_PAIRDEBIAS,
          "lambdarank": _lib.ALGO_LAMBDARANK, "regem": _lib.ALGO_REGEM, "prs": _lib.ALGO_PRS,
-         "pdgd": _lib.ALGO_PDGD, "dbgd": _lib.ALGO_DBGD, "twotower": _lib.ALGO_TWOTOWER, "plrank": _lib.ALGO_PLRANK}
+         "pdgd": _lib.ALGO_PDGD, "dbgd": _lib.ALGO_DBGD, "twotower": _lib.ALGO_TWOTOWER, "plrank": _lib.ALGO_PLRANK,
+         "affine": _lib.ALGO_AFFINE}
 
 
 def optimizer_id(name):
@@ -83,6 +84,13 @@ class StepEngine:
             self.cutoff = 0 if cutoff is None else max(int(cutoff), 0)
             self.num_samples, self.gain = int(num_samples), gain
             self.l2p = _lib.plrank_pack(self.cutoff, self.num_samples, gain)
+        if algo == "affine":
+            # the affine-corrected softmax loss: ipw_table carries [alpha(n) | beta(n)]; the PAD-mask flag rides in the descriptor's
+            # logits_to_prob (ULTR_AFFINE_MASK, include/ultr_hip.h)
+            if process_group is not None:
+                raise NotImplementedError("AffineRank does not train data parallel")
+            self.mask_padding = bool(mask_padding)
+            self.l2p = _lib.AFFINE_MASK if mask_padding else 0
         self.pg = process_group
         self.world = 1 if process_group is None else torch.distributed.get_world_size(process_group)
         self.rank = 0 if process_group is None else torch.distributed.get_rank(process_group)
@@ -206,6 +214,15 @@ class StepEngine:
             self._loss_is_long()  # (raises for a list beyond the kernel's layout, before anything is launched)
             hip_ops.plrank_loss(self.scores, labels, docids, n_docs, B, L, self.dscores, self.loss_ws, n_samples=self.num_samples,
                                 cutoff=self.cutoff, gain=self.gain, seed=self.rng_seed, step=self.rng_step, pw=pw, ipw_table=ipw_table)
+        elif self.algo == "affine":
+            if ipw_table is None or ipw_table.numel() < 2 or ipw_table.numel() % 2:
+                raise ValueError("AffineRank's loss needs its table [alpha(n) | beta(n)] (ipw_table=)")
+            if self.mask_padding and (docids is None or n_docs is None):
+                raise ValueError("AffineRank's loss with mask_padding needs the docids and n_docs (its PADs)")
+            self._loss_is_long()  # (raises for a list beyond the kernel's layout, before anything is launched)
+            n = ipw_table.numel() // 2
+            hip_ops.affine_loss(self.scores, labels, ipw_table[:n], ipw_table[n:], B, L, self.dscores, self.loss_ws,
+                                docids=docids if self.mask_padding else None, n_docs=n_docs if self.mask_padding else 0)
         else:
             raise ValueError(self.algo)
 
@@ -375,6 +392,8 @@ class StepEngine:
         if ipw_table is not c[7]:
             a.ipw_table = ipw_table.data_ptr() if ipw_table is not None else None
             a.n_ipw = int(ipw_table.numel()) if ipw_table is not None else 0
+            if self.algo == "affine":  # [alpha(n) | beta(n)]: the entry's n
+                a.n_ipw //= 2
         if self.algo == "pdgd":
             a.n_ipw = self.cutoff
         self._cached = (params, state, aux, features, docids, labels, pw, ipw_table)

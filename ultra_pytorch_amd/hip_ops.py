@@ -651,6 +651,18 @@ def plrank_loss(scores, labels, docids, n_docs, B, L, dscores, loss_ws, n_sample
                                        _stream()), "ultr_plrank_loss")
 
 
+def affine_loss(scores, labels, alpha, beta, B, L, dscores, loss_ws, docids=None, n_docs=0):
+    """AffineRank: the listwise softmax loss with the affine-corrected clicks w = (c - beta_k) / alpha_k, k = min(l, n - 1), at every
+    position (alpha, beta: float32 [n] each, alpha > 0).  docids [L, B] int32 with n_docs mark the PADs (w = 0 there); None: every
+    position counts.  Weights, their sum and the loss may be negative."""
+    _req(alpha, torch.float32, "alpha")
+    _req(beta, torch.float32, "beta")
+    if alpha.numel() != beta.numel():
+        raise ValueError("alpha and beta must have one length, got %d and %d" % (alpha.numel(), beta.numel()))
+    check(_lib.load().ultr_affine_loss(_p(scores), _p(labels), _p(alpha), _p(beta), int(alpha.numel()), _p(docids), int(n_docs), int(B),
+                                       int(L), _p(dscores), _p(loss_ws), _stream()), "ultr_affine_loss")
+
+
 def apply_update(shape, udesc, params, state, grads, aux, bwd_ws, scalars):
     wt = weight_copy(shape).get(params)  # the update kernel writes the new weights into both layouts
     check(shape.lib.ultr_apply_update(ctypes.byref(udesc), ctypes.byref(shape.desc), _p(params), _p(wt), _p(state), _p(grads),

@@ -14,3 +14,4 @@ from .dbgd import DBGD, MGD  # noqa: F401
 from .nsgd import NSGD  # noqa: F401
 from .two_tower import TwoTower  # noqa: F401
 from .pl_rank import PLRank  # noqa: F401
+from .affine_rank import AffineRank  # noqa: F401

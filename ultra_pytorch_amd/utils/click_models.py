@@ -1,6 +1,7 @@
 """Click simulators (host side): position-biased, user-browsing and cascade models driven by Python's `random` stream, so that
 a seeded run draws the same clicks as the reference's simulators (ultra/utils/click_models.py:7-16, 68-110, 113-186, 187-236):
-one `random.random()` per list position, click iff u < exam_prob * click_prob[label].  Below them: how a model reaches the GPU
+one `random.random()` per list position, click iff u < exam_prob * click_prob[label].  TrustBiasModel is the project's own: the
+one model here that leaves the examination hypothesis.  Below them: how a model reaches the GPU
 (CLICK_MODEL_IDS, load_for_device, device_tables) - the device feeds, DBGD / MGD / NSGD and the propensity estimator all go through it."""
 import json
 import os
@@ -48,6 +49,61 @@ class PositionBiasedModel(ClickModel):
     def estimatePropensityWeightsForOneList(self, click_list, use_non_clicked_data=False):
         return [(1.0 / self.getExamProb(r) * self.getExamProb(0)) if (use_non_clicked_data or c > 0) else 0.0
                 for r, c in enumerate(click_list)]
+
+
+class TrustBiasModel(PositionBiasedModel):
+    """Trust bias (Agarwal et al. 2019; Vardasbi et al. 2020): an examined document is clicked with a probability that depends on the
+    rank as well as on its perceived relevance - trust_pos[k] (epsilon+) if perceived relevant, trust_neg[k] (epsilon-) if not:
+
+        P(click | rank k, label y) = exam[k] * (trust_neg[k] + (trust_pos[k] - trust_neg[k]) * click_prob[y]) = alpha_k gamma + beta_k
+
+    with gamma = click_prob[y], alpha_k = exam[k] (trust_pos[k] - trust_neg[k]), beta_k = exam[k] trust_neg[k].  The rank saturates
+    at the tables' last entry and the label is clamped, as in the base class.  The default tables are this project's."""
+    model_name = "trust_bias_model"
+
+    def __init__(self, neg_click_prob=0.0, pos_click_prob=1.0, relevance_grading_num=1, eta=1.0, trust_pos=None, trust_neg=None):
+        PositionBiasedModel.__init__(self, neg_click_prob, pos_click_prob, relevance_grading_num, eta)
+        n = len(self.exam_prob)
+        self.trust_pos = [1.0 - (r + 1) / 100 for r in range(n)] if trust_pos is None else [float(x) for x in trust_pos]
+        self.trust_neg = [0.65 / (r + 1) for r in range(n)] if trust_neg is None else [float(x) for x in trust_neg]
+        self.check_tables()
+
+    def check_tables(self):
+        """ValueError unless exam_prob, trust_pos and trust_neg have one length and 0 <= trust_neg[k] < trust_pos[k] <= 1."""
+        if not (len(self.exam_prob) == len(self.trust_pos) == len(self.trust_neg)) or not self.exam_prob:
+            raise ValueError("trust_bias_model: exam_prob, trust_pos and trust_neg must have one length, got %d, %d and %d"
+                             % (len(self.exam_prob), len(self.trust_pos), len(self.trust_neg)))
+        for k, (tp, tn) in enumerate(zip(self.trust_pos, self.trust_neg)):
+            if not 0.0 <= tn < tp <= 1.0:
+                raise ValueError("trust_bias_model: 0 <= trust_neg[k] < trust_pos[k] <= 1 does not hold at k = %d (%r, %r)" % (k, tn, tp))
+
+    def getModelJson(self):
+        desc = PositionBiasedModel.getModelJson(self)
+        desc["trust_pos"], desc["trust_neg"] = self.trust_pos, self.trust_neg
+        return desc
+
+    def _rank(self, rank):
+        return rank if rank < len(self.exam_prob) else len(self.exam_prob) - 1
+
+    def sampleClick(self, rank, relevance_label):
+        """(click, examination probability, click probability given examination): one random.random(), as the base class draws."""
+        relevance_label = int(relevance_label) if relevance_label > 0 else 0
+        k = self._rank(rank)
+        exam_p = self.exam_prob[k]
+        gamma = self.click_prob[relevance_label if relevance_label < len(self.click_prob) else -1]
+        click_p = self.trust_neg[k] + (self.trust_pos[k] - self.trust_neg[k]) * gamma
+        return (1 if random.random() < exam_p * click_p else 0), exam_p, click_p
+
+    def affine_parameters(self, list_size):
+        """(alpha[list_size], beta[list_size]) in Python floats: P(click at rank k) = alpha_k click_prob[label] + beta_k."""
+        ks = [self._rank(r) for r in range(int(list_size))]
+        return ([self.exam_prob[k] * (self.trust_pos[k] - self.trust_neg[k]) for k in ks],
+                [self.exam_prob[k] * self.trust_neg[k] for k in ks])
+
+    def estimateAffineWeightsForOneList(self, click_list):
+        """The affine correction (c - beta_k) / alpha_k of every position, clicked or not: its expectation is click_prob[label]."""
+        alpha, beta = self.affine_parameters(len(click_list))
+        return [(c - b) / a for c, a, b in zip(click_list, alpha, beta)]
 
 
 class UserBrowsingModel(ClickModel):
@@ -130,15 +186,19 @@ class CascadeModel(ClickModel):
 
 def loadModelFromJson(model_desc):
     name = model_desc["model_name"]
-    model = {"cascade_model": CascadeModel, "user_browsing_model": UserBrowsingModel}.get(name, PositionBiasedModel)()
+    model = {"cascade_model": CascadeModel, "user_browsing_model": UserBrowsingModel,
+             "trust_bias_model": TrustBiasModel}.get(name, PositionBiasedModel)()
     model.eta = model_desc["eta"]
     model.click_prob = model_desc["click_prob"]
     model.exam_prob = model_desc["exam_prob"]
+    if name == "trust_bias_model":
+        model.trust_pos, model.trust_neg = [float(x) for x in model_desc["trust_pos"]], [float(x) for x in model_desc["trust_neg"]]
+        model.check_tables()
     return model
 
 
-# The click models the GPU simulates (include/ultr_hip.h: ULTR_CLICK_PBM / _CASCADE / _UBM), and how one gets there.
-CLICK_MODEL_IDS = {"position_biased_model": 0, "cascade_model": 1, "user_browsing_model": 2}
+# The click models the GPU simulates (include/ultr_hip.h: ULTR_CLICK_PBM / _CASCADE / _UBM / _TRUST), and how one gets there.
+CLICK_MODEL_IDS = {"position_biased_model": 0, "cascade_model": 1, "user_browsing_model": 2, "trust_bias_model": 3}
 
 
 def load_for_device(path, who):
@@ -151,17 +211,22 @@ def load_for_device(path, who):
     with open(path) as fin:
         desc = json.load(fin)
     if desc["model_name"] not in CLICK_MODEL_IDS:
-        raise NotImplementedError("%s simulates the position-biased, the cascade and the user-browsing model" % who)
+        raise NotImplementedError("%s simulates the position-biased, the cascade and the user-browsing model (and the trust-bias "
+                                  "model)" % who)
     return desc, loadModelFromJson(desc), CLICK_MODEL_IDS[desc["model_name"]]
 
 
 def device_tables(model, model_id, device):
     """(exam tensor, n_exam, cprob tensor) of `model` on `device` as the kernels read them: the examination table [n] for PBM /
-    cascade, a dense [n][n] image of the triangular rank x distance table for the user-browsing model; the click probabilities [n_rel]."""
+    cascade, a dense [n][n] image of the triangular rank x distance table for the user-browsing model, a dense [2][n] image for the
+    trust-bias model (row 0 alpha_k, row 1 beta_k: each the Python-float product rounded to float32 once); the click probabilities
+    [n_rel]."""
     import torch
     ep = model.exam_prob
     n = len(ep)
     if model_id == CLICK_MODEL_IDS["user_browsing_model"]:
         ep = [[(row[c] if c < len(row) else 0.0) for c in range(n)] for row in ep]
+    if model_id == CLICK_MODEL_IDS["trust_bias_model"]:
+        ep = [list(x) for x in model.affine_parameters(n)]
     return (torch.tensor(ep, dtype=torch.float32, device=device).contiguous(), n,
             torch.tensor(model.click_prob, dtype=torch.float32, device=device))

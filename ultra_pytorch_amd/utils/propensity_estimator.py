@@ -50,7 +50,9 @@ def ipw_from_click_count(click_count):
 
 
 class RandomizedPropensityEstimator(BasicPropensityEstimator):
-    """The table estimated from randomized click sessions (:69-146), or loaded from a file that holds one."""
+    """The table estimated from randomized click sessions (:69-146), or loaded from a file that holds one.  Under the trust-bias
+    model the experiment estimates the examination-only table (clicks on position 0 over clicks on position x): the weights that
+    are biased under that model whatever the table, kept as the baseline the affine correction is held against."""
 
     def __init__(self, file_name=None):
         self.click_model = None
@@ -70,7 +72,8 @@ class RandomizedPropensityEstimator(BasicPropensityEstimator):
         import torch
         from .. import hip_ops
         if getattr(click_model, "model_name", None) not in CLICK_MODEL_IDS:
-            raise NotImplementedError("RandomizedPropensityEstimator simulates the position-biased, the cascade and the user-browsing model")
+            raise NotImplementedError("RandomizedPropensityEstimator simulates the position-biased, the cascade and the user-browsing model "
+                                      "(and the trust-bias model)")
         L, label_lists = int(data_set.rank_list_size), data_set.labels
         if any(len(x) > L for x in label_lists):
             raise ValueError("a label list is longer than rank_list_size = %d" % L)
@@ -127,7 +130,7 @@ class OraclePropensityEstimator(BasicPropensityEstimator):
         name = getattr(self.click_model, "model_name", None)
         if name not in CLICK_MODEL_IDS:
             raise NotImplementedError("OraclePropensityEstimator answers for the position-biased, the cascade and the user-browsing "
-                                      "model (got %r)" % name)
+                                      "model, and for the trust-bias model (got %r)" % name)
         ep = self.click_model.exam_prob
         used = [x for row in ep for x in row] if name == "user_browsing_model" else list(ep)
         if any(float(x) == 0.0 for x in used):
@@ -136,7 +139,8 @@ class OraclePropensityEstimator(BasicPropensityEstimator):
     def weight_table(self, list_size):
         """The weights of every list of `list_size` positions as float32 numpy, each entry the reference's own expression in Python
         floats rounded to float32 once (what torch.as_tensor(list of floats) does, ipw_rank.py:138, prs_rank.py:116):
-          position-biased / cascade: ("position", w[list_size]),            w[r] = 1.0 / getExamProb(r) * getExamProb(0)
+          position-biased / cascade / trust-bias (its examination-only weights, PBM's expression):
+                                     ("position", w[list_size]),            w[r] = 1.0 / getExamProb(r) * getExamProb(0)
           user-browsing:             ("history", w[list_size, list_size]),  w[r][c] = 1.0 / getExamProb(r, c - 1) for c <= r, else 0
         (row = rank, column = rank of the last click before it + 1, column 0 = no click so far).  getExamProb fills the table, so
         its rules for ranks beyond the model's rows (click_models.py:174-185) are expanded here and the GPU only looks up."""
@@ -151,6 +155,23 @@ class OraclePropensityEstimator(BasicPropensityEstimator):
                     w[r, c] = np.float32(1.0 / cm.getExamProb(r, c - 1))
             return "history", w
         return "position", np.asarray([1.0 / cm.getExamProb(r) * cm.getExamProb(0) for r in range(L)], np.float32)
+
+    def affine_table(self, list_size):
+        """(alpha[list_size], beta[list_size]) as float32 numpy: P(click at rank k) = alpha_k click_prob[label] + beta_k, what the
+        affine correction (c - beta_k) / alpha_k of AffineRank divides by and subtracts.  The trust-bias model gives its two rows
+        (each the Python-float product rounded to float32 once), the position-biased model (exam[k], 0).  The cascade and the
+        user-browsing model raise NotImplementedError: their examination depends on the clicks of the list, no position table holds it."""
+        import numpy as np
+        cm, L = self.click_model, int(list_size)
+        if L <= 0:
+            raise ValueError("list_size must be positive")
+        if cm.model_name == "trust_bias_model":
+            alpha, beta = cm.affine_parameters(L)
+        elif cm.model_name == "position_biased_model":
+            alpha, beta = [cm.getExamProb(r) for r in range(L)], [0.0] * L
+        else:
+            raise NotImplementedError("affine_table: the examination of the %s depends on the clicks of the list" % cm.model_name)
+        return np.asarray(alpha, np.float32), np.asarray(beta, np.float32)
 
     def getPropensityForOneList(self, click_list, use_non_clicked_data=False):
         return self.click_model.estimatePropensityWeightsForOneList(click_list, use_non_clicked_data)
